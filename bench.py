@@ -1,17 +1,21 @@
 #!/usr/bin/env python
 """scenes/sec forward+backward of the FCAF3D sparse-voxel hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N>1: launched by torch.distributed.run)
 
 One step = forward_train + loss.backward() + gradient all-reduce (N>1) + grad-clip + AdamW step over one
 batch of `--batch` synthetic ScanNet-shaped scenes per GPU (100 000 points, 2 cm voxels, 18 classes,
 fcaf3d_scannet-3d-18class topology: MEResNet3D-34, 4 levels).  Scenes are resident in HBM before the
-timed region.  Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     — the dominant kernel (MFMA gather-GEMM sparse conv), algorithmic FLOPs / HIP-event time, and
+timed region.  Prints ONE JSON line on rank 0: `value` scenes/s and `ms_per_step` over the K timed steps.
+
+A plain run does only what that figure needs: set-up, the W warm-up steps and one window of 4 untimed steps in the timed
+region's pattern, the K timed steps (none of them probed), the outputs (--dump-outputs), the line.  --full adds
+  roofline     — the dominant kernel (MFMA gather-GEMM sparse conv), algorithmic FLOPs / HIP-event time of probed timed steps, and
                  `hbm_kernels`: GB/s of every bandwidth-bound kernel (compulsory bytes / HIP-event time) vs the 8 TB/s peak
   cpu_baseline — MinkowskiEngine's CPU algorithm restated in C/OpenMP (oracle/conv_oracle.c) on this host's cores,
                  with the Python/torch oracle's whole-step number beside it
-  config.{fwd_bwd_only, config4_global_batch_16, inference, data_parallel} — measured outside the timed region.
+  config.{fwd_bwd_only, config4_global_batch_16, forced_dp_n1, fp32_mfma_route, bf16_fast_mode, inference, the other
+  configurations} and config.host.micro — measured outside the timed region; and further settle windows (--settle-seconds).
 """
 import argparse
 import json
@@ -66,6 +70,10 @@ def parse():
     ap.add_argument('--extra-steps', type=int, default=5)
     ap.add_argument('--no-lookahead', action='store_true', help='plan every step in line (default: the next batch\'s coordinate phase runs on a '
                     'worker thread beside the current step, fcaf3d_amd/plan.py Lookahead)')
+    ap.add_argument('--full', action='store_true', help='besides the headline: the probed timed steps and roofline, settle windows past the '
+                    'first, the untimed extras, host micro-measurements and the cpu_baseline (each still subject to its --no-* switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps: what the last one computed as DIR/<name>.npy '
+                    '(dump_outputs)')
     return ap.parse_args()
 
 
@@ -135,6 +143,25 @@ def make_batches(args, rank, dev, n_batches=2):
         batches.append(dict(points=pts, gt_bboxes_3d=gts, gt_labels_3d=labs,
                             img_metas=[dict(box_type_3d=fa.DepthInstance3DBoxes)] * args.batch))
     return batches
+
+
+DUMP_SAMPLE = 1 << 22           # entries of each parameter / gradient sample: 16 MB in float32
+
+
+def dump_outputs(out_dir, params, losses, sample=DUMP_SAMPLE):
+    """What a training step hands its caller, as out_dir/<name>.npy (float32): `loss` and every loss entry, reduced as
+    runner.parse_losses reduces them, and the `params` / `grads` the step left — the same fixed sample (seed 0, sorted) of
+    `sample` entries of the parameters concatenated in module order, so that two builds compare entry for entry."""
+    from fcaf3d_amd.runner import parse_losses
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'loss': parse_losses(losses)}
+    out.update((k, parse_losses({k: v})) for k, v in losses.items() if 'loss' in k)
+    n = sum(p.numel() for p in params)
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, min(sample, n), replace=False))).to(params[0].device)
+    out['params'] = torch.cat([p.detach().reshape(-1) for p in params])[idx]
+    out['grads'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])[idx]
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), v.detach().float().cpu().numpy())
 
 
 class Breakdown:
@@ -701,6 +728,11 @@ def timed_region(fn, n, world, dev):
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run: no probed timed step and nothing measured after the timed region (the extras without a switch of their own
+        # test args.full below)
+        args.no_instrument = args.no_cpu_baseline = args.no_extras = args.no_fp32_route = args.no_force_dp = True
+        args.infer_steps = 0
     install_gc_log()
     host0 = host_state()
     # stdout carries ONE line, the JSON result: everything else that writes to file descriptor 1 during the run (RCCL's
@@ -776,6 +808,7 @@ def main():
     if not args.no_instrument and rank == 0:
         probe = ConvProbe()
         probe.install()
+    last_losses = [None]                         # the loss dict of the latest step (--dump-outputs)
 
     def step(i, probe_mode=None, which=None, prefetch=False):
         src = which if which is not None else batches
@@ -802,7 +835,7 @@ def main():
         EX.PROBE = probe.exec_steps if (probe and probe_mode == 'time' and EX.ENABLED) else None
         model.neck_with_head.head_overlap = head_overlap and not one_stream             # ... nor the head branch's stream
         n_exec = len(probe.exec_steps) if probe else 0
-        loss, _ = trainer(batch, next_batch=nxt)
+        loss, last_losses[0] = trainer(batch, next_batch=nxt)
         EX.PROBE = None
         if probe and probe_mode == 'time' and len(probe.exec_steps) > n_exec and probe._cur:
             probe._cur.clear()       # the step went through the executor (its brackets are inside fc_exec); a pruned finest level's
@@ -814,7 +847,8 @@ def main():
     # as the box waking up, it was device allocations and first-use costs inside the steps (r6_notes.md section 14: removed at the root
     # by --reserve-gb, the warmed probed step below and the cycle-free coordinate objects).  The guard stays: while the host's enqueue
     # time of forward + backward exceeds half of the step's wall time, keep stepping UNTIMED (windows of 4 steps, at most
-    # --settle-seconds), every rank in lockstep; what was done is reported in config.host.settle.
+    # --settle-seconds), every rank in lockstep; what was done is reported in config.host.settle.  A plain run (no --full) stops after
+    # the first window: its number of steps, and with it what --dump-outputs writes, does not depend on the host's speed.
     settle = dict(windows=0, extra_untimed_steps=0, seconds=0.0, host_share_first=None, host_share_last=None)
     if args.settle_seconds > 0 and not args.breakdown:
         t_settle = time.perf_counter()
@@ -838,7 +872,7 @@ def main():
                 t = torch.tensor([slow], device=dev)
                 torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
                 slow = float(t.item())
-            if slow == 0.0 or time.perf_counter() - t_settle > args.settle_seconds:
+            if slow == 0.0 or not args.full or time.perf_counter() - t_settle > args.settle_seconds:
                 break
         settle['seconds'] = round(time.perf_counter() - t_settle, 2)
     if exec_on and probe:
@@ -864,21 +898,24 @@ def main():
     # probed steps: the LAST step of the timed region and every `probe_every`-th before it.  r1-r4 probed the first step of each window
     # — with the next step's coordinate phase (its own stream) running beside the probed step's kernels and inside their brackets: 10 %
     # above the kernels' own durations in the rocprofv3 trace.  Nothing is enqueued behind the last step before the region's closing
-    # synchronise, so its brackets are the kernels' own time (r5: 135 -> ~125 us per operator against 122 us in the trace)
+    # synchronise, so its brackets are the kernels' own time (r5: 135 -> ~125 us per operator against 122 us in the trace).  A plain run
+    # has no probe: every timed step is the ordinary step (a probed step runs on one stream and plans its successor in line)
     pe = max(args.probe_every, 1)
     ph0 = list(trainer.phase_s)
     global SAMPLE_MAIN_THREAD
     SAMPLE_MAIN_THREAD = bool(args.sample_main_thread) and rank == 0          # (stays on for the extras' regions: a diagnostic run)
-    dt, loss = timed_region(lambda i: step(args.warmup + i, 'time' if (args.steps - 1 - i) % pe == 0 else None, prefetch=i < args.steps - 1),
-                            args.steps, world, dev)
+    dt, loss = timed_region(lambda i: step(args.warmup + i, 'time' if args.full and (args.steps - 1 - i) % pe == 0 else None,
+                                           prefetch=i < args.steps - 1), args.steps, world, dev)
     host_main = dict(host_enqueue_ms_per_step=round(LAST_HOST_S / args.steps * 1e3, 3),
                      host_blocked_ms_per_step=round(LAST_WAIT_S / args.steps * 1e3, 3),
                      host_busy_ms_per_step=round((LAST_HOST_S - LAST_WAIT_S) / args.steps * 1e3, 3),
                      process_cpu_ms_per_step=round(LAST_CPU_S / args.steps * 1e3, 3), thread_cpu_ms_per_step=LAST_THREADS, steps=LAST_STEPS, settle=settle,
                      phases_ms_per_step=[round((b - a) / args.steps * 1e3, 3) for a, b in zip(ph0, trainer.phase_s)],
-                     micro=host_micro(dev), pinned_to_gpu_numa_node=pinned, after=host_state(),
+                     micro=host_micro(dev) if args.full else None, pinned_to_gpu_numa_node=pinned, after=host_state(),
                      allocator_reserve_GB=round(reserved / 2 ** 30, 1))
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:          # before any untimed step below changes the parameters
+        dump_outputs(args.dump_outputs, trainer.params, last_losses[0])
     dp_log = getattr(trainer.averager, 'log', None)
     trainer.averager.log = None
     # untimed: FLOPs of every launch, one step per distinct batch.  EVERY rank steps (a step holds collectives: a
@@ -948,7 +985,7 @@ def main():
     # ---- extras, all OUTSIDE the timed region above (every rank runs them: they hold collectives) ------------------
     # (a) SURVEY 8(d) protocol: forward_train + backward only, synchronised around every iteration, median
     fb = []
-    for i in range(5):
+    for i in range(5 if args.full else 0):
         batch = batches[i % len(batches)]
         trainer.optimizer.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
@@ -958,10 +995,10 @@ def main():
         trainer.averager.finish()
         torch.cuda.synchronize()
         fb.append(time.perf_counter() - t0)
-    fb_med = float(np.median(fb))
+    fb_med = float(np.median(fb)) if fb else None
     # (b) BASELINE config 4: global batch 16 split over the ranks (2 scenes per GPU on 8), same step
     cfg4 = None
-    if world > 1 and 16 % world == 0 and args.workload == 'scannet-100k':
+    if args.full and world > 1 and 16 % world == 0 and args.workload == 'scannet-100k':
         per = 16 // world
         small = [{k: v[:per] for k, v in b.items()} for b in batches] if per <= args.batch else None
         if small is not None:
@@ -1126,13 +1163,13 @@ def main():
                                             (', the NEXT batch planned on a worker thread beside the current step (plan.Lookahead); exactly '
                                              f'{args.steps} plans inside the timed region' if lookahead else ', in line')),
                        'fwd_bwd_only': {'protocol': 'SURVEY 8(d): forward_train + backward (+ all-reduce), synchronised per iteration, median of 5',
-                                        'ms': round(fb_med * 1e3, 3), 'scenes_per_s': round(args.batch * world / fb_med, 3)},
+                                        'ms': round(fb_med * 1e3, 3), 'scenes_per_s': round(args.batch * world / fb_med, 3)} if fb else None,
                        'config4_global_batch_16': cfg4, 'forced_dp_n1': forced, 'config4_per_gpu': cfg4_1,
                        'fp32_mfma_route': fp32_route, 'bf16_fast_mode': bf16_fast, 'inference': infer, 'inference_pipelined': infer_pipe,
                        **extras,
                        'kernel_source_sha16': __import__('fcaf3d_amd.build', fromlist=['source_hash']).source_hash(),
                        'executor': bool(exec_on) and 'network body through the native launch-list executor (fcaf3d_amd/executor.py, '
-                                   'csrc/exec.hip), the probed step included (event brackets inside fc_exec)'},
+                                   'csrc/exec.hip)' + (', the probed step included (event brackets inside fc_exec)' if probe else '')},
         }
         out['roofline'] = rl
         if world > 1 and dp_log:

@@ -122,3 +122,39 @@ def test_bench_step_count_is_rank_independent():
         assert bench.count_steps(bench.parse(), 2) == 0
     finally:
         sys.argv = argv
+
+
+def test_bench_dump_outputs_writes_one_fixed_sample_of_the_step_results(tmp_path):
+    """bench.py --dump-outputs: the loss entries reduced as runner.parse_losses reduces them, and the parameters and gradients
+    (zeros for a parameter without one) at the same entries of one seeded sample, in module order; float32, the same from call
+    to call; a sample as large as the parameters is all of them.  A plain command line leaves both new options off."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '2']
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 4
+    finally:
+        sys.argv = argv
+    torch.manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(40, 30)), torch.nn.Parameter(torch.randn(7)), torch.nn.Parameter(torch.randn(3, 5))]
+    params[0].grad, params[2].grad = torch.randn(40, 30), torch.randn(3, 5)
+    losses = dict(loss_a=torch.tensor(0.5), loss_b=[torch.tensor([1.0, 3.0]), torch.tensor(2.0)], num_pos=torch.tensor(9.0))
+    for d, n in (('a', 100), ('b', 100), ('all', 10 ** 6)):
+        bench.dump_outputs(str(tmp_path / d), params, losses, sample=n)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['grads.npy', 'loss.npy', 'loss_a.npy', 'loss_b.npy', 'params.npy']
+    for f in files:
+        x = np.load(tmp_path / 'a' / f)
+        assert x.dtype == np.float32 and np.array_equal(x, np.load(tmp_path / 'b' / f))
+    assert float(np.load(tmp_path / 'a' / 'loss_b.npy')) == 4.0 and float(np.load(tmp_path / 'a' / 'loss.npy')) == 4.5
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params]).numpy()
+    flat_g = torch.cat([params[0].grad.reshape(-1), torch.zeros(7), params[2].grad.reshape(-1)]).numpy()
+    assert np.array_equal(np.load(tmp_path / 'all' / 'params.npy'), flat_p)
+    assert np.array_equal(np.load(tmp_path / 'all' / 'grads.npy'), flat_g)
+    pos = np.array([np.flatnonzero(flat_p == v)[0] for v in np.load(tmp_path / 'a' / 'params.npy')])
+    assert len(pos) == 100 and (np.diff(pos) > 0).all()
+    assert np.array_equal(np.load(tmp_path / 'a' / 'grads.npy'), flat_g[pos])

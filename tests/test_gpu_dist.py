@@ -209,7 +209,7 @@ def test_bench_n_ranks_on_one_gpu_prints_the_contract_line(ranks, batch):
     env = dict(os.environ, FC_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(ranks), '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--steps', '3', '--warmup', '2',
-           '--batch', str(batch), '--no-cpu-baseline', '--infer-steps', '0', '--no-extras', '--no-fp32-route']
+           '--batch', str(batch), '--no-cpu-baseline', '--infer-steps', '0', '--no-extras', '--no-fp32-route', '--full']
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -223,3 +223,35 @@ def test_bench_n_ranks_on_one_gpu_prints_the_contract_line(ranks, batch):
     assert dp['buckets'] >= 2 and len(dp['last_step_launch_ms_after_first_grad']) == dp['buckets'] and dp['backend'] == 'gloo'
     assert 'worker thread' in out['config']['coordinate_phase']
     print(f'bench.py --gpus {ranks} (gloo, one GPU):', out['value'], 'scenes/s;', dp)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line times exactly K steps (`ms_per_step`), runs none of
+    the untimed extras and one settle window only, and DIR holds the last timed step's losses and parameter / gradient samples as
+    float32 .npy files, 64 MB at most."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = str(tmp_path / 'outputs')
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2',
+           '--dump-outputs', out_dir]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0
+    assert abs(out['value'] * out['ms_per_step'] - 2e3) <= 2.0          # value = 2 scenes per ms_per_step
+    assert out['roofline'] is None and out['cpu_baseline'] is None
+    c = out['config']
+    assert all(c[k] is None for k in ('fwd_bwd_only', 'forced_dp_n1', 'fp32_mfma_route', 'bf16_fast_mode', 'inference'))
+    assert c['host']['micro'] is None and c['host']['settle']['windows'] == 1
+    files = sorted(os.listdir(out_dir))
+    assert files == sorted(['loss.npy', 'loss_centerness.npy', 'loss_bbox.npy', 'loss_cls.npy', 'params.npy', 'grads.npy'])
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in files}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert abs(float(a['loss']) - c['final_loss']) <= 1e-4
+    assert abs(float(a['loss']) - float(a['loss_centerness'] + a['loss_bbox'] + a['loss_cls'])) <= 1e-5 * abs(float(a['loss']))
+    assert a['params'].shape == a['grads'].shape == (1 << 22,) and np.abs(a['grads']).max() > 0

@@ -6,4 +6,4 @@ N=${1:-128}; T=${2:-90}; shift 2
 for i in $(seq $N); do (timeout $T python3 -c "while True: pass" > /dev/null 2>&1 &) ; done
 sleep 3
 uptime
-python bench.py --no-cpu-baseline --infer-steps 0 --no-fp32-route --no-extras --no-force-dp "$@"
+python bench.py --full --no-cpu-baseline --infer-steps 0 --no-fp32-route --no-extras --no-force-dp "$@"
