@@ -63,8 +63,6 @@ def lib():
             raise RuntimeError(f'{LIB_PATH} speaks ABI version {l.fc_abi_version()}, this host code was written for {ABI_VERSION}: rebuild '
                                'with `python -m fcaf3d_amd.build`')
         _lib = l
-        if os.environ.get('FC_PRIO_OFF') or os.environ.get('FC_PRIO_MODE'):     # A/B switches of the MFMA-block wave priority
-            l.fc_debug_set_prio(-1 if os.environ.get('FC_PRIO_OFF') else int(os.environ['FC_PRIO_MODE']))      # (conv.hip: g_fc_prio)
     return _lib
 
 

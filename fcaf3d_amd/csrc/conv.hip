@@ -12,7 +12,7 @@
 // Replaces MinkowskiEngine's ConvolutionForward/Backward (and ConvolutionTranspose, 1x1 mm) called
 // from me_resnet.py:19-21,56-62, BasicBlock, fcaf3d_neck_with_head.py:52,60-69,83-85,257-263.
 #include "fc_common.h"
-#include <cstdlib>
+#include "../../include/fcaf3d_hip.h"
 #ifdef FC_TRACE
 __device__ unsigned long long* g_trace_buf_lds;
 __device__ int g_trace_cap_lds;
@@ -38,7 +38,7 @@ __device__ __attribute__((aligned(16))) float g_zero_row[64];   // what an absen
 // same box, instruction-identical otherwise: +2.4...3.4 % on the 441k-row launches, +3 % on the 64k-row level, +4 % on
 // the 3.5k-row pair mode, +1...4 % on k_wgrad_multi; the one-offset weight-gradient kernels LOSE 2...7 % and the LDS-DMA
 // kernel up to 9 %, so those stay at priority 0.  Static per-workgroup priorities (by block index, by hardware wave slot):
-// +1 % or -10 %.  g_fc_prio = -1 switches it off (A/B: tools/nbench --prio -1, FC_PRIO_OFF=1; not a C-ABI entry point).
+// +1 % or -10 %.  g_fc_prio = -1 switches it off (A/B: tools/nbench --prio -1; not a C-ABI entry point).
 __device__ int g_fc_prio;
 extern "C" int fc_debug_set_prio(int mode) {
   FC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_fc_prio), &mode, sizeof(mode)));
@@ -56,24 +56,18 @@ extern "C" int fc_set_bf16_fast(int on) {
 }
 
 // r6: how the split kernels cut an fp32 operand (conv_x6.h): 2 = two fp16 pieces, three products ("h3", the default), 0 = three
-// bf16 pieces, six products (r3-r5).  Process-global (FC_SPLIT_MODE / fc_set_split_mode): weight images are built in the mode
+// bf16 pieces, six products (r3-r5).  Process-global (fc_set_split_mode): weight images are built in the mode
 // that is current when fc_x6_weight_image(s) runs and MUST be read in that mode — whoever switches rebuilds them (functional.py
 // set_split_mode does).  The bf16 fast mode reads plane 0 of a SIX-product image: fc_set_bf16_fast(1) implies mode 0 while it is on.
-static int g_split_mode = -1;
-static inline int split_mode() {
-  if (g_split_mode < 0) {
-    const char* e = getenv("FC_SPLIT_MODE");
-    g_split_mode = (e && atoi(e) == 0) ? 0 : 2;
-  }
-  return g_bf16_fast ? 0 : g_split_mode;
-}
+static int g_split_mode = 2;
+static inline int split_mode() { return g_bf16_fast ? 0 : g_split_mode; }
 extern "C" int fc_set_split_mode(int mode) {
   if (mode != 0 && mode != 2) return FC_EINVAL;
   g_split_mode = mode;
   return FC_OK;
 }
 extern "C" int fc_get_split_mode(void) { return split_mode(); }
-static int g_h3r = -1;                           // which h3 launches run the register-operand kernel (launch_conv_mfma)
+static int g_h3r = 1;                            // which h3 launches run the register-operand kernel (launch_conv_mfma)
 extern "C" int fc_debug_set_h3r(int mode) {
   if (mode < 0 || mode > 2) return FC_EINVAL;
   g_h3r = mode;
@@ -617,6 +611,8 @@ __global__ __launch_bounds__(256, 3) void k_conv_mfma_p(const float* __restrict_
       };
       read_frag(0, 0);
       if (prio) __builtin_amdgcn_s_setprio(1);
+      // (r2: sched_group_barrier pins that issue the LDS reads of step q+1 ahead of step q's MFMAs measured +-1 % on 50 of 58
+      // launch shapes and -10.5 % at the VGPR limit: the fragment reads are not what the loop waits for.)
 #pragma unroll
       for (int q = 0; q < BKT / 8; ++q) {
         if (q + 1 < BKT / 8) read_frag(q + 1, (q + 1) & 1);
@@ -629,20 +625,6 @@ __global__ __launch_bounds__(256, 3) void k_conv_mfma_p(const float* __restrict_
             for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae, fb[q & 1][j][e], acc[i][j], 0, 0, 0);
           }
         }
-#ifdef FC_SGB
-        // experiment (-DFC_SGB=4, r2): pin "the LDS reads of step q+1 go out FIRST, interleaved with the head of step q's
-        // MFMAs" (the compiler otherwise sinks them behind the 16 MFMAs and waits for them on the spot; with the pin the
-        // waits become counted lgkmcnt(2/4)).  Measured: +-1 % on 50 of 58 launch shapes, 441k rows 64->128 +1.3 %,
-        // 128->64 -3.2 %, 64->64 (256 x 64 tile, at its VGPR limit) -10.5 %: the fragment reads are not what the loop waits for.
-        if (q + 1 < BKT / 8) {
-#pragma unroll
-          for (int g = 0; g < FC_SGB; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, TM * TN * 4 - 2 * FC_SGB, 0);
-        }
-#endif
       }
       if (prio) __builtin_amdgcn_s_setprio(0);
     }
@@ -1325,7 +1307,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad_col(const float* __restrict_
 }
 
 // generic fallback (any Cin/Cout): one thread per (row, cout).  Used for the Cin=3 stem and as the
-// cross-check path of the parity tests (flags & 1).
+// cross-check path of the parity tests (FC_CONV_FMA).
 __global__ void k_conv_fma(const float* __restrict__ in, const float* __restrict__ W, const int* __restrict__ nbr,
                            float* __restrict__ out, int64_t n_out, int K, int Cin, int Cout, int wt) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1346,33 +1328,32 @@ __global__ void k_conv_fma(const float* __restrict__ in, const float* __restrict
 
 extern "C" {
 
-#define FC_CONV_WT (1 << 23)   // fc_conv_fwd / fc_conv_fwd_pairs(_tiles): W[k] is stored transposed, (Cout, Cin) row-major
 // The deeper-pipelined LDS kernel (k_conv_mfma_p) holds 3 workgroups per CU (768 slots) where k_conv_mfma holds 4 (1024): it
 // wins on launches of many rounds and on launches that fit 768 slots anyway, and loses a round in between (r2: +5.5 / +7 %
 // on the 441k / 55k-row levels, +5 % on the 862-row pair mode, -12 % on the 3.5k-row pair mode with its 972 workgroups).
-// flags bit18 forces it on, bit17 off.
-// flags bit21: the LDS-DMA kernel (k_conv_glds, 2 workgroups per CU) instead.  Returns 0 / 1 / 2 = k_conv_mfma / _p / k_conv_glds.
+// FC_CONV_PIPE_ON forces it on, FC_CONV_PIPE_OFF off.
+// FC_CONV_GLDS: the LDS-DMA kernel (k_conv_glds, 2 workgroups per CU) instead.  Returns 0 / 1 / 2 = k_conv_mfma / _p / k_conv_glds.
 static inline int conv_pipe(int flags, dim3 grid) {
-  if (flags & (1 << 24)) return (flags & (1 << 26)) ? 4 : 3;     // split-bf16 kernel (conv_x6.h); bit26: W is a pre-split image
-  if (flags & (1 << 21)) return 2;
-  if (flags & (1 << 18)) return 1;
-  if (flags & (1 << 17)) return 0;
+  if (flags & FC_CONV_SPLIT) return (flags & FC_CONV_IMAGE) ? 4 : 3;     // split-bf16 kernel (conv_x6.h); W is a pre-split image
+  if (flags & FC_CONV_GLDS) return 2;
+  if (flags & FC_CONV_PIPE_ON) return 1;
+  if (flags & FC_CONV_PIPE_OFF) return 0;
   const int64_t wgs = (int64_t)grid.x * grid.y * grid.z;
   if (wgs >= 1536 || wgs <= 768) return 1;
   // in between: offset-split launches of a dense table go to the LDS-DMA kernel (r2 nbench, same box: 6.9k rows 256->256
   // 251 -> 232 us, 256->128 139 -> 128 us, 14.9k rows 128->128 163 -> 146 us; unsplit and pair-list launches: neutral)
-  return (grid.z > 1 && !(flags & (1 << 22))) ? 2 : 0;
+  return (grid.z > 1 && !(flags & FC_CONV_GLDS_OFF)) ? 2 : 0;
 }
 
 static void conv_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool* mfma, int* bm, int* bn, int* S) {
-  *mfma = !(flags & 1) && (Cin % BK == 0) && (Cout % 64 == 0) && K <= 32;
+  *mfma = !(flags & FC_CONV_FMA) && (Cin % BK == 0) && (Cout % 64 == 0) && K <= 32;
   *bn = (Cout % 128 == 0) ? 128 : 64;
   const int64_t wg128 = fc_cdiv(n_out, 128) * (Cout / *bn);
   // measured on the benchmark's layers (tools/convbench.py): 128-row tiles win at every size once the grid
   // is topped up to ~1024 workgroups by splitting over kernel offsets
   *bm = (n_out > 64 && wg128 >= 4) ? 128 : 64;
   // 64-wide outputs on big maps: 256 x 64 tiles, 4 waves along the rows (r2: +6 % on the 441k-row level, 88 / 95 TF)
-  if (*bn == 64 && Cout == 64 && fc_cdiv(n_out, 256) >= 1024 && !(flags & (1 << 24))) *bm = 256;      // (split-bf16: 128 x 64 at 4 waves / SIMD is ahead, 613 vs 628 us)
+  if (*bn == 64 && Cout == 64 && fc_cdiv(n_out, 256) >= 1024 && !(flags & FC_CONV_SPLIT)) *bm = 256;      // (split-bf16: 128 x 64 at 4 waves / SIMD is ahead, 613 vs 628 us)
   const int64_t tiles = fc_cdiv(n_out, *bm) * (Cout / *bn);
   int s = 1;
   // split over kernel offsets: the LARGEST split that still fits one resident round (1024 workgroup slots) — one workgroup
@@ -1384,8 +1365,9 @@ static void conv_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool* 
     if (s > K) s = K;
     if (s < 1) s = 1;
   }
-  // tuning overrides: flags[4:5] BM (1=64, 2=128), flags[6:7] BN (1=64, 2=128), flags[8:15] S
-  int fbm = (flags >> 4) & 3, fbn = (flags >> 6) & 3, fs = (flags >> 8) & 255;
+  // tuning overrides: BM (1=64, 2=128, 3=256), BN (1=64, 2=128), S
+  int fbm = (flags >> FC_CONV_BM_SHIFT) & FC_CONV_TILE_MASK, fbn = (flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK,
+      fs = (flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK;
   if (fbm) *bm = fbm == 1 ? 64 : (fbm == 2 ? 128 : 256);
   if (fbn && (Cout % (fbn == 1 ? 64 : 128) == 0)) *bn = fbn == 1 ? 64 : 128;
   if (*bm == 256) *bn = 64;                      // the 4 x 1 wave arrangement: 256 x 64 tiles
@@ -1395,7 +1377,7 @@ static void conv_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool* 
     if (*mfma && K > 1 && t2 < 384) { s = (int)(1024 / t2); if (s > K) s = K; if (s < 1) s = 1; }
   }
   if (fs) s = fs > K ? K : fs;
-  if ((flags & (1 << 24)) && *mfma && *bm == 64) {     // the split-bf16 kernel has 128- and 256-row tiles only
+  if ((flags & FC_CONV_SPLIT) && *mfma && *bm == 64) {     // the split-bf16 kernel has 128- and 256-row tiles only
     *bm = 128;
     const int64_t t3 = fc_cdiv(n_out, 128) * (Cout / *bn);
     if (!fs) { s = 1; if (K > 1 && t3 < 384) { s = (int)(1024 / t3); if (s > K) s = K; } }
@@ -1411,7 +1393,7 @@ static int launch_conv_mfma(int pipe, int bm, int bn, dim3 grid, const float* in
                             int64_t n_in_rows = -1) {
   if (epi && (pipe < 3 || bm < 128 || cnt || grid.z != 1)) return FC_EINVAL;      // the statistics epilogue lives in k_conv_x6
   // buffer addressing (k_conv_x6 BUF; gathering launches on a weight image): the gathered operand must end below the 2 GB its
-  // descriptor spans; n_in < 0: the caller asks for (flags bit27) or only knows flat addresses
+  // descriptor spans; n_in < 0: the caller asks for (FC_CONV_FLAT) or only knows flat addresses
   const bool bufok = nbr && n_in >= 0 && (uint64_t)n_in * (uint64_t)Cin * 4u < (1ull << 31) - 4096u &&
                      (uint64_t)K * (uint64_t)n_rows * 4u < (1ull << 31) - 4096u;      // (r6: the neighbour table goes through a descriptor too)
   X6Epi e6 = {};
@@ -1439,9 +1421,8 @@ static int launch_conv_mfma(int pipe, int bm, int bn, dim3 grid, const float* in
   if (wt && pipe == 2) pipe = 0;                 // the LDS-DMA image cannot be transposed in flight
   // r6: h3 launches on 128 x 128 tiles take the register-operand kernel (conv_h3r.h): +1...11 % per launch there (tools/nbench, same
   // box), while the 64-column tiles LOSE 7-14 % on the 441k-row maps — a lane-per-row load touches 32 cache lines per instruction
-  // where the LDS staging touches 8, and those launches are bound by the gather.  FC_H3R / fc_debug_set_h3r: 0 never, 1 (default)
+  // where the LDS staging touches 8, and those launches are bound by the gather.  fc_debug_set_h3r: 0 never, 1 (default)
   // 128-column tiles, 2 every 128-row tile.
-  if (g_h3r < 0) g_h3r = getenv("FC_H3R") ? atoi(getenv("FC_H3R")) : 1;
   if (h3 && bm == 128 && !g_bf16_fast && (g_h3r == 2 || (g_h3r == 1 && bn == 128))) {
 #define FC_LAUNCH_H3R(BN_)                                                                                               \
   do {                                                                                                                  \
@@ -1499,7 +1480,7 @@ static int launch_conv_mfma(int pipe, int bm, int bn, dim3 grid, const float* in
 }
 
 static inline bool is_stem(const int* nbr, int K, int Cin, int Cout, int flags) {
-  return !(flags & 1) && !(flags & FC_CONV_WT) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27;
+  return !(flags & FC_CONV_FMA) && !(flags & FC_CONV_WT) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27;
 }
 
 int64_t fc_conv_fwd_ws_bytes(int64_t n_out, int K, int Cin, int Cout, int flags) {
@@ -1541,9 +1522,9 @@ static int conv_fwd_impl(const float* in, const float* W, const int* nbr, const 
   if (wt && !nbr) return FC_EINVAL;
   bool mfma_ok; int bm, bn, S;
   conv_plan(n_out, K, Cin, Cout, flags, &mfma_ok, &bm, &bn, &S);
-  if (stats && (!mfma_ok || !(flags & (1 << 24)))) return FC_EINVAL;      // see fc_conv_stats_blocks
+  if (stats && (!mfma_ok || !(flags & FC_CONV_SPLIT))) return FC_EINVAL;      // see fc_conv_stats_blocks
   if (!mfma_ok) {
-    if (out_index || (flags & (1 << 26))) return FC_EINVAL;      // sorted-row tables and weight images are MFMA-path features
+    if (out_index || (flags & FC_CONV_IMAGE)) return FC_EINVAL;      // sorted-row tables and weight images are MFMA-path features
     k_conv_fma<<<(unsigned)fc_cdiv(n_out * Cout, 256), 256, 0, stream>>>(in, W, nbr, out, n_out, K, Cin, Cout, wt ? 1 : 0);
     FC_CHECK_LAUNCH();
     return FC_OK;
@@ -1552,7 +1533,7 @@ static int conv_fwd_impl(const float* in, const float* W, const int* nbr, const 
   float* dst = S > 1 ? (float*)ws : out;
   dim3 grid((unsigned)fc_cdiv(n_out, bm), Cout / bn, S);
   int rc = launch_conv_mfma(conv_pipe(flags, grid), bm, bn, grid, in, W, nbr, out_index, nullptr, dst, n_out, K, Cin, Cout, stream, wt,
-                            S > 1 ? nullptr : epi, (flags & (1 << 27)) ? -1 : n_in, n_in);
+                            S > 1 ? nullptr : epi, (flags & FC_CONV_FLAT) ? -1 : n_in, n_in);
   if (rc != FC_OK) return rc;
   if (S > 1) return stats ? sum_parts_stats(dst, out, n_out, Cout, S, *epi, stream) : sum_parts(dst, out, n_out, Cout, S, stream);
   return FC_OK;
@@ -1562,7 +1543,7 @@ static int conv_fwd_impl(const float* in, const float* W, const int* nbr, const 
 // fc_conv_fwd_pairs_tiles_stats: stats[blocks][2][Cout], column sums of the result and of its square per row block); 0: this launch
 // has no statistics epilogue (not the split-bf16 MFMA route).  pairs != 0: the per-offset pair-list route.
 int64_t fc_conv_stats_blocks(int64_t n_out, int K, int Cin, int Cout, int flags, int pairs) {
-  if (n_out < 1 || !(flags & (1 << 24))) return 0;
+  if (n_out < 1 || !(flags & FC_CONV_SPLIT)) return 0;
   if (pairs) return (Cin % 32 == 0 && Cout % 64 == 0) ? fc_cdiv(n_out, fc_stat_rb(n_out)) : 0;
   bool mfma_ok; int bm, bn, S;
   conv_plan(n_out, K, Cin, Cout, flags, &mfma_ok, &bm, &bn, &S);
@@ -1594,13 +1575,13 @@ int fc_conv_fwd_bn_bwd_stats(const float* in, const float* W, const int* nbr, co
   return conv_fwd_impl(in, W, nbr, out_index, out, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream, &e);
 }
 
-// flags: bit0 = force the generic FMA kernel.
+// flags: FC_CONV_* (include/fcaf3d_hip.h).
 int fc_conv_fwd(const float* in, const float* W, const int* nbr, const int* out_index, float* out, int64_t n_in,
                 int64_t n_out, int K, int Cin, int Cout, int flags, void* ws, int64_t ws_bytes, hipStream_t stream) {
   return conv_fwd_impl(in, W, nbr, out_index, out, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream);
 }
 
-// Pre-split weight image for the split-bf16 kernel (flags bit24 | bit26 of fc_conv_fwd / fc_conv_fwd_pairs*): R = reduction
+// Pre-split weight image for the split-bf16 kernel (FC_CONV_SPLIT | FC_CONV_IMAGE of fc_conv_fwd / fc_conv_fwd_pairs*): R = reduction
 // size (Cin of the launch), C = its columns (Cout of the launch); transposed != 0: W[k] is stored (C, R) row-major.
 int64_t fc_x6_weight_image_bytes(int K, int R, int C) { return (int64_t)K * R * C * 6; }
 
@@ -1651,12 +1632,12 @@ static int conv_fwd_pairs_impl(const float* in, const float* W, const int* pair_
   const bool wt = (flags & FC_CONV_WT) != 0;
   // (r5, measured null: 64-column tiles for the few-thousand-row pair-list launches — 4 workgroups per CU, finer rounds — 373.6 /
   // 372.5 / 372.2 scenes/s at <= 1k / 4k / 16k rows against 375.4: profiles/r5_notes.md)
-  const bool wide = (Cout % 128 == 0) && !(((flags >> 6) & 3) == 1);
+  const bool wide = (Cout % 128 == 0) && !(((flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK) == 1);
   const int bn = wide ? 128 : 64;
   dim3 grid((unsigned)fc_cdiv(n_out, 128), Cout / bn, K);
   if (live_tiles > 0) grid = dim3((unsigned)live_tiles, Cout / bn, 1);       // linear list of the live (offset, tile) pairs
   {
-    int rc = launch_conv_mfma((live_tiles > 0 || (flags & (1 << 24))) ? conv_pipe(flags, grid) : ((flags & (1 << 21)) ? 2 : ((flags & (1 << 18)) ? 1 : 0)), 128, bn, grid, in, W, pair_in, nullptr, pair_cnt, part, n_out, K, Cin, Cout, stream, wt, nullptr, (flags & (1 << 27)) ? -1 : n_in, n_in);
+    int rc = launch_conv_mfma((live_tiles > 0 || (flags & FC_CONV_SPLIT)) ? conv_pipe(flags, grid) : ((flags & FC_CONV_GLDS) ? 2 : ((flags & FC_CONV_PIPE_ON) ? 1 : 0)), 128, bn, grid, in, W, pair_in, nullptr, pair_cnt, part, n_out, K, Cin, Cout, stream, wt, nullptr, (flags & FC_CONV_FLAT) ? -1 : n_in, n_in);
     if (rc != FC_OK) return rc;
   }
   if (epi) {
@@ -1679,7 +1660,7 @@ int fc_conv_fwd_pairs_tiles(const float* in, const float* W, const int* pair_in,
 int fc_conv_fwd_pairs_tiles_stats(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
                                   float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
                                   void* ws, int64_t ws_bytes, float* stats, hipStream_t stream) {
-  if (stats && !(flags & (1 << 24))) return FC_EINVAL;
+  if (stats && !(flags & FC_CONV_SPLIT)) return FC_EINVAL;
   X6Epi e = {};
   e.stats = stats;
   return conv_fwd_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
@@ -1691,7 +1672,7 @@ int fc_conv_fwd_pairs_tiles_bn_bwd_stats(const float* in, const float* W, const 
                                          void* ws, int64_t ws_bytes, float* stats, const float* bn_x, const float* mean,
                                          const float* var, const float* gamma, const float* beta, float eps, int act,
                                          const float* add, const float* bn_y, hipStream_t stream) {
-  if (!stats || !bn_x || !mean || !var || act < 0 || act > 2 || !(flags & (1 << 24))) return FC_EINVAL;
+  if (!stats || !bn_x || !mean || !var || act < 0 || act > 2 || !(flags & FC_CONV_SPLIT)) return FC_EINVAL;
   X6Epi e = {stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y};
   return conv_fwd_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
                              &e);
@@ -2166,7 +2147,7 @@ extern "C" {
 static void wgrad_tiles(int Cin, int Cout, int flags, int* bm, int* bn) {
   *bm = 64;                                  // measured: 64-channel Cin tiles beat 128 on every benchmark layer
   *bn = (Cout % 128 == 0) ? 128 : 64;
-  int fbm = (flags >> 4) & 3, fbn = (flags >> 6) & 3;      // tuning overrides
+  int fbm = (flags >> FC_CONV_BM_SHIFT) & FC_CONV_TILE_MASK, fbn = (flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK;      // tuning overrides
   if (fbm == 1) *bm = 64;
   if (fbm == 2 && Cin % 128 == 0) *bm = 128;
   if (fbn == 1) *bn = 64;
@@ -2175,32 +2156,26 @@ static void wgrad_tiles(int Cin, int Cout, int flags, int* bm, int* bn) {
 
 // several offsets per workgroup (k_wgrad_multi): every dense table with >= 4096 rows (r2 nbench, one-offset kernel -> multi:
 // 55k rows 128->128 504 -> 446 us, 6.9k rows 256->256 278 -> 247, 256->128 148 -> 135, 441k rows 128->64 2121 -> 2003, 64->64
-// 1086 -> 1051); flags bit29 disables it, bit30 restricts it to its first rule (Cin = 64, >= 32768 rows)
+// 1086 -> 1051); FC_CONV_WGRAD_MULTI_OFF disables it, FC_CONV_WGRAD_MULTI_FIRST restricts it to its first rule (Cin = 64, >= 32768 rows)
 #define WGRAD_KO 3
-// split-bf16 weight gradients: rows loaded 16 B per lane and transposed by ds_read_b64_tr_b16 (k_wgrad_x6t, r4) or the register
-// transposition of r3 (k_wgrad_x6; FC_WGRAD_TR=0) — bit-identical results
-// (r5: the r3 register-transposing kernel k_wgrad_x6 and its FC_WGRAD_TR switch are gone; FC_WGRAD_TR64=0 keeps 64 x 64-channel
-// pair lists and the table-free dense GEMMs on the fp32 MFMA kernel)
-static inline bool wgrad_tr64() {
-  static const bool on = !(getenv("FC_WGRAD_TR64") && atoi(getenv("FC_WGRAD_TR64")) == 0);
-  return on;
-}
+// split-bf16 weight gradients: rows loaded 16 B per lane and transposed by ds_read_b64_tr_b16 (k_wgrad_x6t, r4; the register
+// transposition of r3, k_wgrad_x6, is gone since r5), every pair-list and table-free dense shape included
 static inline bool wgrad_multi_ok(int64_t n_out, int K, int Cin, int Cout, int flags, bool dense_table) {
-  return dense_table && !(flags & 1) && !(flags & (1 << 29)) && K % WGRAD_KO == 0 &&
-         Cin % 64 == 0 && Cout % 64 == 0 && n_out >= 4096 && (!(flags & (1 << 30)) || (Cin == 64 && n_out >= 32768));
+  return dense_table && !(flags & FC_CONV_FMA) && !(flags & FC_CONV_WGRAD_MULTI_OFF) && K % WGRAD_KO == 0 &&
+         Cin % 64 == 0 && Cout % 64 == 0 && n_out >= 4096 && (!(flags & FC_CONV_WGRAD_MULTI_FIRST) || (Cin == 64 && n_out >= 32768));
 }
 
 static void wgrad_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool dense_table, int* S, int64_t* rows_per_split) {
-  if (!(flags & 1) && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {     // stem: 4096 rows per block
+  if (!(flags & FC_CONV_FMA) && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {     // stem: 4096 rows per block
     int64_t m = n_out > 0 ? n_out : 1;
     *rows_per_split = 1024;                      // (r2: 512 rows per block is slower — more partial tiles to write and reduce)
     *S = (int)fc_cdiv(m, 1024);
     return;
   }
-  bool mfma_ok = !(flags & 1) && (Cin % 64 == 0) && (Cout % 64 == 0);
+  bool mfma_ok = !(flags & FC_CONV_FMA) && (Cin % 64 == 0) && (Cout % 64 == 0);
   int tbm, tbn;
   wgrad_tiles(Cin, Cout, flags, &tbm, &tbn);
-  if ((flags & (1 << 24)) && !dense_table && Cin % 128 == 0) tbm = 128;      // split-bf16 pair-list kernel: 128-channel tiles
+  if ((flags & FC_CONV_SPLIT) && !dense_table && Cin % 128 == 0) tbm = 128;      // split-bf16 pair-list kernel: 128-channel tiles
   int64_t tiles = mfma_ok ? (int64_t)K * (Cin / tbm) * (Cout / tbn) : (int64_t)K;
   // aim for ~1728 workgroups (r2 sweep: 2048 rounded UP left a nearly empty last round on most layers — 128->128 on 55k
   // rows 559 us at 38 splits, 448 at 32), at least 512 rows per split, at most 256 splits
@@ -2213,15 +2188,14 @@ static void wgrad_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool 
     // (r3) 23.34, half 23.70, a quarter 28.63, two rounds 23.25 — the main stream's kernels find a slot sooner.  With the
     // transposing-read kernel (k_wgrad_x6t, 1.4x faster per launch) half a round of the wide variant is ahead: 256 / 512
     // 22.26-22.35 ms, 192 / 512 22.41, 384 / 512 22.65, 128 / 512 23.36 (same box)
-    static const int round_wide = getenv("FC_WGRAD_ROUND_WIDE") ? atoi(getenv("FC_WGRAD_ROUND_WIDE")) : 256;
-    static const int round_narrow = getenv("FC_WGRAD_ROUND_NARROW") ? atoi(getenv("FC_WGRAD_ROUND_NARROW")) : 512;
+    constexpr int round_wide = 256, round_narrow = 512;
     s = (wide ? round_wide : round_narrow) / tiles;     // the 128-column variant holds 2 workgroups per CU (registers)
   }
   int64_t max_by_rows = fc_cdiv(n_out > 0 ? n_out : 1, mfma_ok ? 512 : 2048);
   if (s > max_by_rows) s = max_by_rows;
   if (s > 256) s = 256;
   if (s < 1) s = 1;
-  if ((flags >> 8) & 255) s = (flags >> 8) & 255;         // tuning override
+  if ((flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK) s = (flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK;         // tuning override
   int64_t rps = fc_align(fc_cdiv(n_out > 0 ? n_out : 1, s), 64);
   s = fc_cdiv(n_out > 0 ? n_out : 1, rps);
   *S = (int)s;
@@ -2311,15 +2285,14 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
   wgrad_plan(n_out, K, Cin, Cout, flags, dense_table, &S, &rps);
   if (ws_bytes < (int64_t)S * elems * (int64_t)sizeof(float)) return FC_EWS;
   float* part = (S == 1) ? gW : (float*)ws;
-  bool mfma_ok = !(flags & 1) && (Cin % 64 == 0) && (Cout % 64 == 0);
+  bool mfma_ok = !(flags & FC_CONV_FMA) && (Cin % 64 == 0) && (Cout % 64 == 0);
   if (cnt && !mfma_ok) return FC_EINVAL;       // pair lists are an MFMA-path feature
   // h3 (conv_x6.h): the k_wgrad_x6t launches below split both operands into two fp16 pieces, scaled by their amax words
-  const bool x6t = mfma_ok && (flags & (1 << 24)) &&
-                   (wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table) ||
-                    (cnt && (Cin % 128 == 0 || Cout % 128 == 0 || wgrad_tr64())) || (!nbr && !cnt && wgrad_tr64()));
+  const bool x6t = mfma_ok && (flags & FC_CONV_SPLIT) &&
+                   (wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table) || cnt || (!nbr && !cnt));
   const bool h3 = x6t && split_mode() == 2;
-  // buffer addressing of both operands (wgrad_x6.h): below 2 GB each, row indices below 2^24; flags bit27: flat addresses (A/B, tests)
-  const int wbuf = (!(flags & (1 << 27)) && (uint64_t)n_in * (uint64_t)Cin * 4u < (1ull << 31) - 4096u && (uint64_t)n_out * (uint64_t)Cout * 4u < (1ull << 31) - 4096u &&
+  // buffer addressing of both operands (wgrad_x6.h): below 2 GB each, row indices below 2^24; FC_CONV_FLAT: flat addresses (A/B, tests)
+  const int wbuf = (!(flags & FC_CONV_FLAT) && (uint64_t)n_in * (uint64_t)Cin * 4u < (1ull << 31) - 4096u && (uint64_t)n_out * (uint64_t)Cout * 4u < (1ull << 31) - 4096u &&
                     n_in < (1 << 24) && n_out < (1 << 24) && (uint64_t)K * (uint64_t)n_out * 4u < (1ull << 31) - 4096u) ? 1 : 0;
   const unsigned *am_a = nullptr, *am_g = nullptr;
   if (h3) {
@@ -2327,13 +2300,13 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
     if (rc == FC_OK) rc = operand_amax(gout, n_out * (int64_t)Cout, 1, stream, &am_g);
     if (rc != FC_OK) return rc;
   }
-  if (!(flags & 1) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {
+  if (!(flags & FC_CONV_FMA) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {
     size_t smem = (size_t)(STEM_ROWS * STEM_JP + STEM_ROWS * 64) * sizeof(float);
     k_stem_wgrad<<<(unsigned)S, 256, smem, stream>>>(in, gout, nbr, part, n_out, K, rps);
   } else if (mfma_ok && wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table)) {
     const int bn = (Cout % 128 == 0) ? 128 : 64;
     dim3 grid((unsigned)S, (unsigned)((K / WGRAD_KO) * (Cin / 64) * (Cout / bn)));
-    if (flags & (1 << 24)) {                     // split-bf16 (wgrad_x6.h)
+    if (flags & FC_CONV_SPLIT) {                 // split-bf16 (wgrad_x6.h)
       if (g_bf16_fast && bn == 128) k_wgrad_x6t<64, 128, WGRAD_KO, false, 1><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
       else if (g_bf16_fast) k_wgrad_x6t<64, 64, WGRAD_KO, false, 1><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
       else if (h3 && bn == 128) k_wgrad_x6t<64, 128, WGRAD_KO, false, 2><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, am_a, am_g, wbuf);
@@ -2343,10 +2316,10 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
     } else
     if (bn == 128) k_wgrad_multi<128, WGRAD_KO><<<grid, 256, 0, stream>>>(in, gout, nbr, part, n_out, K, Cin, Cout, rps);
     else k_wgrad_multi<64, WGRAD_KO><<<grid, 256, 0, stream>>>(in, gout, nbr, part, n_out, K, Cin, Cout, rps);
-  } else if (mfma_ok && cnt && (flags & (1 << 24)) && (Cin % 128 == 0 || Cout % 128 == 0 || wgrad_tr64())) {
+  } else if (mfma_ok && cnt && (flags & FC_CONV_SPLIT)) {
     // split-bf16 over the pair lists (r3 nbench: 128 x 128 tiles 119 -> 95 us on 15k rows 128->128, 111 -> 89 / 109 -> 87 on
     // the 256- and 512-channel levels; 64 x 64 tiles — one accumulator per wave, a dependent MFMA chain — lost to the fp32
-    // kernel with the r3 kernel and win with k_wgrad_x6t: wgrad_tr64()).  128-channel Cin tiles only while they still fill the
+    // kernel with the r3 kernel and win with k_wgrad_x6t).  128-channel Cin tiles only while they still fill the
     // chip (862 rows, 512->128: 216 workgroups of 128 x 128 tiles 49 us, fp32 36 us)
     const int bn = (Cout % 128 == 0) ? 128 : 64;
     int bm = (Cin % 128 == 0) ? 128 : 64;
@@ -2363,7 +2336,7 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
     else if (bn == 128) FC_WX6(64, 128);
     else FC_WX6(64, 64);
 #undef FC_WX6
-  } else if (mfma_ok && !nbr && !cnt && (flags & (1 << 24)) && wgrad_tr64()) {
+  } else if (mfma_ok && !nbr && !cnt && (flags & FC_CONV_SPLIT)) {
     // table-free dense GEMM gW = in^T gout over the rows (K = 1): the same kernel with the row itself as the index
     const int bn = (Cout % 128 == 0) ? 128 : 64;
     int bm = (Cin % 128 == 0) ? 128 : 64;
@@ -2385,10 +2358,11 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
     wgrad_tiles(Cin, Cout, flags, &bm, &bn);
     if (cnt) bm = 64;
     dim3 grid((unsigned)S, (unsigned)(K * (Cin / bm) * (Cout / bn)));
-    const bool deep = (flags & (1 << 19)) && bm == 64 && nbr;          // 64-row chunks (tuning flag)
+    const bool deep = (flags & FC_CONV_WGRAD_DEEP) && bm == 64 && nbr;          // 64-row chunks (tuning flag)
     // k_wgrad_mfma_p where it measured ahead (r2 nbench, same box: pair lists with 128-wide gout tiles +3..7 %; 64-wide
-    // tiles -5 %, dense tables -7..13 %).  bit16: never, bit20: wherever it applies (tests / A-B).
-    const bool wpipe = bm == 64 && !(flags & (1 << 19)) && !(flags & (1 << 16)) && ((flags & (1 << 20)) || (cnt && bn == 128));
+    // tiles -5 %, dense tables -7..13 %).  FC_CONV_WGRAD_PIPE_OFF: never, _ON: wherever it applies (tests / A-B).
+    const bool wpipe = bm == 64 && !(flags & FC_CONV_WGRAD_DEEP) && !(flags & FC_CONV_WGRAD_PIPE_OFF) &&
+                       ((flags & FC_CONV_WGRAD_PIPE_ON) || (cnt && bn == 128));
     if (wpipe && cnt) {
       if (bn == 128) k_wgrad_mfma_p<128, true, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
       else k_wgrad_mfma_p<64, true, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
@@ -2430,7 +2404,7 @@ int fc_conv_wgrad_pairs(const float* in, const float* gout, const int* pair_in, 
                         float* gW, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, void* ws,
                         int64_t ws_bytes, hipStream_t stream) {
   if (!pair_in || !pair_out || !pair_cnt) return FC_EINVAL;
-  return conv_wgrad_impl(in, gout, pair_in, pair_out, pair_cnt, gW, n_in, n_out, K, Cin, Cout, flags & ~(1 << 19), ws,
+  return conv_wgrad_impl(in, gout, pair_in, pair_out, pair_cnt, gW, n_in, n_out, K, Cin, Cout, flags & ~FC_CONV_WGRAD_DEEP, ws,
                          ws_bytes, stream);
 }
 

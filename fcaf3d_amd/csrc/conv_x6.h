@@ -40,22 +40,11 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // Round-to-nearest-even pieces (r4; v_cvt_pk_bf16_f32 converts and packs a pair in one instruction): x1 = RN8(x),
 // x2 = RN8(x - x1), x3 = x - x1 - x2 — still EXACT (the second residual has at most 7 significant bits: |x - x1| <= 2^-9 of
 // x's binade top, its low end is x's last bit), with |x2| <= 2^-8 |x|, |x3| <= 2^-17 |x| and residuals of either sign: the
-// three dropped products sum to <= 2^-24 |a b| and carry no common sign (the truncating split of r3, -DFC_X6_TRUNC: <= 2^-21,
-// all with the sign of a b).  9 VALU per pair (3 cvt_pk, 2 shift/and pairs, 2 packed subtractions), r3: 11.
+// three dropped products sum to <= 2^-24 |a b| and carry no common sign (the truncating split of r3, oracle/x6_oracle.py
+// split3_trunc: <= 2^-21, all with the sign of a b).  9 VALU per pair (3 cvt_pk, 2 shift/and pairs, 2 packed subtractions), r3: 11.
 typedef __bf16 x6_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned x6_hi2(unsigned u0, unsigned u1) { return __builtin_amdgcn_perm(u1, u0, 0x07060302u); }
-#ifdef FC_X6_TRUNC
-__device__ __forceinline__ void x6_split2(float x0, float x1, unsigned& p0, unsigned& p1, unsigned& p2) {
-  const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-  p0 = x6_hi2(u0, u1);
-  const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-  const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-  p1 = x6_hi2(v0, v1);
-  const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-  p2 = x6_hi2(__float_as_uint(s0), __float_as_uint(s1));
-}
-#else
 __device__ __forceinline__ unsigned x6_rn2(float x0, float x1) {
   const x6_f32x2 v = {x0, x1};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, x6_bf16x2));
@@ -67,7 +56,6 @@ __device__ __forceinline__ void x6_split2(float x0, float x1, unsigned& p0, unsi
   const float s0 = r0 - __uint_as_float(p1 << 16), s1 = r1 - __uint_as_float(p1 & 0xffff0000u);
   p2 = x6_rn2(s0, s1);
 }
-#endif
 
 // ---- r6: TWO fp16 pieces per operand, THREE products ("h3") -------------------------------------------------------------------
 // An fp16 carries 11 significant bits.  With round-to-nearest pieces  h = RN11(s x),  l = RN11(s x - h)  the residual s x - h is
@@ -111,25 +99,11 @@ __device__ __forceinline__ void h3_split2(float x0, float x1, unsigned& p0, unsi
   p1 = h3_rn2(r0, r1);
 }
 
-// (-DFC_H3_SPLIT_MIX, not the default — see below.)  The same two pieces from UNSCALED inputs in five instructions per pair instead of eight: v_fma_mixlo / mixhi_f16 round
-// fma(x, s, -0) = s x to fp16 straight into the halves of p0, v_fma_mix_f32 forms the residual fma(x, s, -h) = s x - h exactly in
-// fp32 from the fp16 half (no conversion back), one packed conversion makes p1.  Bit for bit h3_split2(s x0, s x1, ...)
-// (scratch/mix_probe.hip: 4.2 M heavy-tailed values at three scales, signed zeros included).  On this SIMD a wave's VALU time adds
-// to its neighbours' matrix time, and the split is most of the staging's VALU (r6_notes.md section 9).
+// h3_split2 of scaled inputs.  (r6: a five-instruction sequence of v_fma_mixlo / mixhi_f16 and v_fma_mix_f32 on the unscaled
+// inputs, bit for bit the same pieces, ran the step at 476.2 / 476.4 scenes/s against 478.5 / 478.1 — like the packed fp32
+// instructions, VOP3P mix instructions are no bargain beside MFMAs; r6_notes.md section 9.)
 __device__ __forceinline__ void h3_split2s(float x0, float x1, float s, unsigned& p0, unsigned& p1) {
-#ifndef FC_H3_SPLIT_MIX                        // default: the conversion-based sequence.  Measured (ABAB, one box): the five-instruction
-  h3_split2(x0 * s, x1 * s, p0, p1);           // mix sequence below runs the step at 476.2 / 476.4 scenes/s against 478.5 / 478.1 — like the
-  return;                                      // packed fp32 instructions, VOP3P mix instructions are no bargain beside MFMAs
-#endif
-  unsigned h = 0u;
-  const float nz = -0.0f;
-  asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "+v"(h) : "v"(x0), "v"(s), "s"(nz));
-  asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(h) : "v"(x1), "v"(s), "s"(nz));
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(x1), "v"(s), "v"(h));
-  p0 = h;
-  p1 = h3_rn2(r0, r1);
+  h3_split2(x0 * s, x1 * s, p0, p1);
 }
 
 // Weight slab in LDS and in a pre-split weight image: per 64-column group three planes of 64 rows x 64 B.  Column c of the

@@ -29,7 +29,6 @@ constexpr int OPW = 24;            // int64 words per operator
 constexpr int MAPW = 20;           // int64 words per kernel-map descriptor
 constexpr int NSTREAM = 3;
 constexpr int MAX_EVENTS = 64;
-constexpr int CONV_X6 = (1 << 24) | (1 << 26), WGRAD_X6 = 1 << 24;
 
 // one event set per DEVICE (an event belongs to the device that was current when it was created; a process that drives
 // detectors on two devices must not share them — ADVICE r4).  fc_exec is NOT re-entrant per device: one thread per device at a
@@ -193,7 +192,7 @@ inline T* P(const Ctx& c, int64_t idx) { return idx < 0 ? nullptr : reinterpret_
 // segment of a segmented run, so nothing is remembered from the launch.
 int64_t stats_blocks_of(const Ctx& c, const int64_t* pop) {
   const int Cin = (int)pop[8], Cout = (int)pop[9];
-  const int fl = c.flags | CONV_X6;
+  const int fl = c.flags | FC_CONV_SPLIT | FC_CONV_IMAGE;
   if (pop[4] < 0) return fc_conv_stats_blocks(c.dims[pop[7]], 1, Cin, Cout, fl, 0);
   const int64_t* m = c.maps + pop[4] * MAPW;
   const bool bwd = pop[5] != 0;
@@ -249,7 +248,7 @@ int run_op_impl(Ctx& c, const int64_t* op) {
     case OP_CONV: {  // in, img, map (-1: dense GEMM over n rows), dir, out, n(dim, dense only), Cin, Cout, statistics table + 1 | 0,
                      // [BatchNorm-backward form of the table:] bn_x + 1 | 0, mean, var, gamma, beta, eps, act, add + 1 | 0, bn_y + 1 | 0
       const int Cin = (int)op[8], Cout = (int)op[9];
-      const int fl = c.flags | CONV_X6;
+      const int fl = c.flags | FC_CONV_SPLIT | FC_CONV_IMAGE;
       float* stats = (op[10] > 0 && stats_blocks_of(c, op) > 0) ? P<float>(c, op[10] - 1) : nullptr;
       const float* bnx = (stats && op[11] > 0) ? P<const float>(c, op[11] - 1) : nullptr;
       const float *bmean = P<const float>(c, op[12]), *bvar = P<const float>(c, op[13]), *bga = P<const float>(c, op[14]),
@@ -359,7 +358,7 @@ int run_op_impl(Ctx& c, const int64_t* op) {
     }
     case OP_WGRAD: {  // in, gout, map (-1: dense), gW, n(dim, dense only), Cin, Cout, amax word of in + 1 | 0, of gout + 1 | 0
       const int Cin = (int)op[7], Cout = (int)op[8];
-      const int fl = c.flags | WGRAD_X6;
+      const int fl = c.flags | FC_CONV_SPLIT;
       if (!c.dry && (op[9] > 0 || op[10] > 0))
         fc_conv_amax_hint(op[9] > 0 ? P<const unsigned>(c, op[9] - 1) : nullptr, op[10] > 0 ? P<const unsigned>(c, op[10] - 1) : nullptr);
       if (op[4] < 0) {

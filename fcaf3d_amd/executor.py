@@ -61,7 +61,7 @@ def _f(x):
 
 def supported(det):
     bb, nh = det.backbone, det.neck_with_head
-    if not (ENABLED and Fn.X6 and Fn.X6_CONV and Fn.X6_WGRAD and not (Fn.FLAGS & 1) and Fn.STEM_COL and Fn.DGRAD_WT):
+    if not (ENABLED and Fn.X6 and not (Fn.FLAGS & Fn.CONV_FMA) and Fn.STEM_COL and Fn.DGRAD_WT):
         return False
     if getattr(bb.BLOCK, 'expansion', 1) != 1 or det.spatial_sort:
         return False

@@ -293,8 +293,6 @@ class Fcaf3DNeckWithHead(nn.Module):
             loss_bbox=torch.mean(torch.stack(loss_bbox)),
             loss_cls=torch.mean(torch.stack(loss_cls)))
 
-    early_targets = os.environ.get('FC_EARLY_TARGETS', '1') != '0'
-
     def _targets(self, cmaps, gt_bboxes, gt_labels, pre=None):
         """Locations, assigned targets and per-scene normalisers of one batch — everything the loss needs that does not
         depend on the network's outputs: locations = voxel corners of the head's coordinate sets (:276-277), targets from
@@ -324,7 +322,7 @@ class Fcaf3DNeckWithHead(nn.Module):
         """Called by the detector as soon as the head's coordinate sets exist (SingleStageSparse3DDetector._sparse_input, on
         the coordinate stream): `loss()` then finds the assignment done.  Identity of the coordinate-map objects is the key."""
         self._prepared = None
-        if self.early_targets and hasattr(self.assigner, 'assign_batched') and len(cmaps) == self.assigner.n_scales \
+        if hasattr(self.assigner, 'assign_batched') and len(cmaps) == self.assigner.n_scales \
                 and (pre is not None or cmaps[0].coords.is_cuda):
             self._prepared = (tuple(id(cm) for cm in cmaps), cmaps, self._targets(cmaps, gt_bboxes, gt_labels, pre))
 

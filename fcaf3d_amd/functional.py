@@ -6,7 +6,25 @@ import torch
 
 from . import _lib as L
 
-FLAGS = int(os.environ.get('FC_FLAGS', '0'), 0)   # bit0: force the generic FMA conv kernels (parity cross-check); tuning bits: conv.hip
+# bits of the convolution `flags` word: the one Python mirror of include/fcaf3d_hip.h FC_CONV_* (tests/test_cabi.py compares them)
+CONV_FMA = 1 << 0                        # the generic FMA kernels (parity cross-check)
+CONV_BM_SHIFT, CONV_BN_SHIFT, CONV_TILE_MASK = 4, 6, 3      # tuning fields: tile rows / columns (1 = 64, 2 = 128, 3 = 256 rows)
+CONV_S_SHIFT, CONV_S_MASK = 8, 255       # ... and the number of partial sums
+CONV_WGRAD_PIPE_OFF = 1 << 16            # kernel variants (tools/nbench, tools/convbench.py, tests/test_gpu_ops.py)
+CONV_PIPE_OFF = 1 << 17
+CONV_PIPE_ON = 1 << 18
+CONV_WGRAD_DEEP = 1 << 19
+CONV_WGRAD_PIPE_ON = 1 << 20
+CONV_GLDS = 1 << 21
+CONV_GLDS_OFF = 1 << 22
+CONV_WT = 1 << 23                        # W[k] is stored (Cout, Cin): the backward-data pass on the layer's own kernel
+CONV_SPLIT = 1 << 24                     # split-bf16 / fp16 kernels (csrc/conv_x6.h, csrc/wgrad_x6.h)
+CONV_IMAGE = 1 << 26                     # with CONV_SPLIT: W is a pre-split weight image
+CONV_FLAT = 1 << 27                      # with CONV_SPLIT: flat 64-bit addresses instead of buffer descriptors
+CONV_WGRAD_MULTI_OFF = 1 << 29
+CONV_WGRAD_MULTI_FIRST = 1 << 30
+
+FLAGS = int(os.environ.get('FC_FLAGS', '0'), 0)   # kernel-variant bits of every convolution launch (CONV_* above)
 
 # Weight-gradient kernels are leaves of the backward graph: with WGRAD_ASYNC they are enqueued on a second HIP
 # stream and overlap the backward-data chain on the main stream (the many small layers of the backbone do not
@@ -20,7 +38,7 @@ _join_queued = False
 def wgrad_stream(device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _wg_streams:
-        _wg_streams[idx] = torch.cuda.Stream(device=idx, priority=int(os.environ.get('FC_WGRAD_PRIO', '0')))
+        _wg_streams[idx] = torch.cuda.Stream(device=idx, priority=0)
     return _wg_streams[idx]
 
 
@@ -85,28 +103,25 @@ def gather_rows(src, idx):
 
 # ---- convolution -----------------------------------------------------------------------------------
 def _mfma_shape(Cin, Cout):
-    return not (FLAGS & 1) and Cin % 32 == 0 and Cout % 64 == 0
+    return not (FLAGS & CONV_FMA) and Cin % 32 == 0 and Cout % 64 == 0
 
 
 def _pair_conv(kmap, n_rows, Cin, Cout):
     """run this convolution per offset over the exact pair lists? (small, sparsely occupied 27-offset maps)"""
     from . import sparse as SP
-    return (kmap is not None and kmap.use_pairs and n_rows <= SP.PAIR_CONV_ROWS and not (FLAGS & 1)
+    return (kmap is not None and kmap.use_pairs and n_rows <= SP.PAIR_CONV_ROWS and not (FLAGS & CONV_FMA)
             and Cin % 32 == 0 and Cout % 64 == 0)
 
 
 STEM_COL = os.environ.get('FC_STEM_COL', '1') != '0'      # stem: save the gathered inputs in forward, stream them in the weight gradient
-CONV_WT = 1 << 23          # flags bit of fc_conv_fwd / fc_conv_fwd_pairs_tiles: W[k] is stored (Cout, Cin) — see conv.hip
 DGRAD_WT = os.environ.get('FC_DGRAD_TRANSPOSE', '0') != '1'      # backward-data reads the layer's own kernel (no transpose launch)
 
 
 # fp32 convolutions on the bf16 matrix pipe by exact three-way operand splitting (csrc/conv_x6.h): forward and backward-data
 # of every MFMA-shaped layer.  The kernel reads the weights as a pre-split image, rebuilt when the weights change.
 X6 = os.environ.get('FC_X6', '1') != '0'
-X6_CONV = os.environ.get('FC_X6_CONV', '1') != '0'        # A/B switches: forward / backward-data only, weight gradient only
-X6_WGRAD = os.environ.get('FC_X6_WGRAD', '1') != '0'
-CONV_X6 = (1 << 24) | (1 << 26)          # forward / backward-data: split-bf16 kernel, weights as a pre-split image
-WGRAD_X6 = 1 << 24                       # weight gradient: split-bf16 kernels
+CONV_X6 = CONV_SPLIT | CONV_IMAGE        # forward / backward-data: split-bf16 kernel, weights as a pre-split image
+WGRAD_X6 = CONV_SPLIT                    # weight gradient: split-bf16 kernels
 
 
 def split_mode():
@@ -203,14 +218,14 @@ class _SparseConv(torch.autograd.Function):
         n_in = feats.shape[0]
         out = torch.empty((n_out, Cout), dtype=torch.float32, device=feats.device)
         col = stats = None
-        if (STEM_COL and training and kmap is not None and Cin == 3 and Cout == 64 and K <= 27 and not (FLAGS & 1)
+        if (STEM_COL and training and kmap is not None and Cin == 3 and Cout == 64 and K <= 27 and not (FLAGS & CONV_FMA)
                 and ctx.needs_input_grad[1]):
             # stem in training: keep the gathered inputs (n_out, 84) for the weight gradient (conv.hip: k_stem_fwd / k_stem_wgrad_col)
             col = torch.empty((n_out, 84), dtype=torch.float32, device=feats.device)
             L.call('fc_stem_conv_fwd', L.ptr(feats), L.ptr(weight), L.ptr(kmap.nbr), L.ptr(out), L.ptr(col), n_in, n_out, K,
                    L.stream())
         else:
-            x6 = X6 and X6_CONV and _mfma_shape(Cin, Cout)
+            x6 = X6 and _mfma_shape(Cin, Cout)
             w, fl = (_x6_image(weight, False), FLAGS | CONV_X6) if x6 else (weight, FLAGS)
             pairs = _pair_conv(kmap, n_out, Cin, Cout)
             stats = _stats_table(n_out, K, Cin, Cout, fl, pairs, feats.device)[0] if (want_stats and BN_FUSE and x6) else None
@@ -243,7 +258,7 @@ class _SparseConv(torch.autograd.Function):
             # the (Cout -> Cin) operator of the backward-data pass: the kernels read the layer's own (K, Cin, Cout) kernel as
             # its transpose (flags CONV_WT; r2: 50 transpose launches and 0.34 ms per step gone); identity maps (dense GEMMs)
             # still take a transposed copy
-            if X6 and X6_CONV and _mfma_shape(Cout, Cin):
+            if X6 and _mfma_shape(Cout, Cin):
                 wt, fl = _x6_image(weight, True), FLAGS | CONV_X6
             elif DGRAD_WT and kmap is not None:
                 wt, fl = weight, FLAGS | CONV_WT
@@ -279,10 +294,10 @@ class _SparseConv(torch.autograd.Function):
                     ws = L.workspace(L.query('fc_stem_conv_wgrad_ws_bytes', n_out, K), dev)
                     L.call('fc_stem_conv_wgrad', L.ptr(col), L.ptr(gout), L.ptr(g), n_out, K, L.ptr(ws), ws.numel(), L.stream())
                     return g
-                fl = FLAGS | WGRAD_X6 if (X6 and X6_WGRAD) else FLAGS      # split-bf16 where the library has a kernel for the shape (wgrad_x6.h)
+                fl = FLAGS | WGRAD_X6 if X6 else FLAGS      # split-bf16 where the library has a kernel for the shape (wgrad_x6.h)
                 wsb = L.query('fc_conv_wgrad_ws_bytes', n_out, K, Cin, Cout, fl)
                 ws = L.workspace(wsb, dev)
-                if kmap is not None and kmap.use_pairs and not (FLAGS & 1) and Cin % 64 == 0 and Cout % 64 == 0:
+                if kmap is not None and kmap.use_pairs and not (FLAGS & CONV_FMA) and Cin % 64 == 0 and Cout % 64 == 0:
                     pi, po, _, cnt = kmap.pairs()
                     L.call('fc_conv_wgrad_pairs', L.ptr(feats), L.ptr(gout), L.ptr(pi), L.ptr(po), L.ptr(cnt), L.ptr(g), n_in,
                            n_out, K, Cin, Cout, fl, L.ptr(ws), ws.numel(), L.stream())
@@ -397,7 +412,7 @@ import os as _os
 BN_FUSE = _os.environ.get('FC_BN_FUSE', '1') != '0'
 # matrices up to this size take the two-launch BatchNorm path (measured r1: equal speed up to 1 M elements, fewer host
 # launches; at 4 M the <=64-block grid is slower than the general path)
-BN_SMALL_ELEMS = int(_os.environ.get('FC_BN_SMALL_ELEMS', 1024 * 1024))
+BN_SMALL_ELEMS = 1024 * 1024
 
 
 class _BNTrainSmall(torch.autograd.Function):

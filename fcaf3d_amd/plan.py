@@ -1,6 +1,6 @@
 """The coordinate phase of one step through the two native calls of csrc/plan.hip (r6).
 
-`plan_step(det, points, ...)` replaces, for the standard FCAF3D topologies (BasicBlock backbone, default routing switches), what
+`plan_step(det, points, ...)` replaces, for the standard FCAF3D topologies (BasicBlock backbone), what
 `SingleStageSparse3DDetector.voxelize` + `SparseTensor(...)` + `plan_maps` did with ~420 launches and ~25 blocking read-backs driven
 from Python (reference: the collate + ME.SparseTensor + every kernel-map build inside extract_feat,
 mmdet3d/models/detectors/single_stage_sparse.py:32-40): `fc_plan_levels` (one read-back) + `fc_plan_maps` (one read-back).  The
@@ -47,13 +47,6 @@ def _mark(tag):
 
 def _f64_bits(v):
     return int(np.array([v], dtype=np.float64).view(np.int64)[0])
-
-
-def default_switches():
-    """the native plan implements the DEFAULT routing switches of sparse.py; an A/B switch set to anything else takes the
-    per-operator path"""
-    return (SP.SORT_ROWS and not SP.SORT_DENSE and SP.SORT_DENSE_MAX_ROWS == 0 and SP.STRUCTURED_MAPS and not SP.PAIRS_DENSE
-            and SP.WGRAD_PAIRS)
 
 
 class _Arenas:
@@ -103,7 +96,7 @@ class Planner:
     def applicable(self, points):
         det = self.det
         bb = det.backbone
-        if not ENABLED or not default_switches() or getattr(bb.BLOCK, 'expansion', 1) == 4:
+        if not ENABLED or getattr(bb.BLOCK, 'expansion', 1) == 4:
             return False
         p0 = points[0]
         if not (torch.is_tensor(p0) or hasattr(p0, 'voxelize_into')):

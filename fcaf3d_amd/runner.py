@@ -218,7 +218,7 @@ class TrainStep:
         # (the flat optimizer writes through raw pointers and does not); then the images are rebuilt before use.
         from . import functional as Fn
         self.images = None
-        if self.flat is not None and Fn.X6 and os.environ.get('FC_X6_PREBUILD', '1') != '0':
+        if self.flat is not None and Fn.X6:
             from .nn import MinkowskiConvolution
             ws = [m.kernel for m in model.modules() if isinstance(m, MinkowskiConvolution) and m.kernel.requires_grad]
             self.images = Fn.WeightImages(ws)

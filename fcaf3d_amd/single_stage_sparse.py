@@ -1,6 +1,5 @@
 """Detector shell — host-side mirror of mmdet3d/models/detectors/single_stage_sparse.py:9-62 and the
 `forward(return_loss=...)` dispatch of detectors/base.py:45-60."""
-import os
 import torch
 from torch import nn
 
@@ -78,10 +77,12 @@ class SingleStageSparse3DDetector(nn.Module):
         if not (hasattr(p0, 'is_cuda') and p0.is_cuda):
             return False
         dev = p0.device
-        from .sparse import plan_stream
+        from .sparse import map_stream
         main = torch.cuda.current_stream(dev)
         want_targets = bool(gt) and hasattr(self.neck_with_head, 'prepare_targets')
-        return la.submit(points, self.training, want_targets, plan_stream(dev), main, wait_main=not self.inputs_resident)
+        # the plan runs on the coordinate stream itself: r6 measured a stream of its own at 24.2 ms per 8-scene step against 20.9 — a
+        # fifth busy stream falls into the slow mode of profiles/r5_notes.md section 16 (profiles/r6_notes.md section 2)
+        return la.submit(points, self.training, want_targets, map_stream(dev), main, wait_main=not self.inputs_resident)
 
     def _sparse_input(self, points, gt=None):
         from . import plan as PL
@@ -170,7 +171,7 @@ class SingleStageSparse3DDetector(nn.Module):
     def extract_feat(self, points, img_metas, gt=None):
         """gt (training only, optional): (gt_bboxes_3d, gt_labels_3d) — lets the target assignment start with the maps"""
         if self.async_maps:
-            with on_map_stream(points[0].device, self.inputs_resident and os.environ.get('FC_MAP_WAIT') != '1'):
+            with on_map_stream(points[0].device, self.inputs_resident):
                 x = self._sparse_input(points, gt)
         else:
             x = self._sparse_input(points, gt)

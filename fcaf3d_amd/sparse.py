@@ -43,23 +43,6 @@ def map_stream(device):
     return _side[(key, prio)]
 
 
-_plan_side = {}
-
-
-def plan_stream(device):
-    """the stream of the lookahead plan (plan.Lookahead): the coordinate stream itself.  r6 measured a stream of its own (FC_PLAN_STREAM=own:
-    the main stream then never waits for a part of the NEXT batch's plan at the end of a coordinate phase) at 24.2 ms per 8-scene step
-    against 20.9 on the coordinate stream, with identical kernel durations in the rocprofv3 trace — a FIFTH busy stream of the process
-    beside main / head / weight-gradient / coordinate falls into the slow mode of profiles/r5_notes.md section 16 deterministically
-    (profiles/r6_notes.md section 2), so the step keeps to four."""
-    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-    if os.environ.get('FC_PLAN_STREAM') != 'own':
-        return map_stream(key)
-    if key not in _plan_side:
-        _plan_side[key] = torch.cuda.Stream(device=key, priority=map_stream(key).priority)
-    return _plan_side[key]
-
-
 _inputs_ready = {}
 
 
@@ -122,19 +105,13 @@ def _next_pow2(n):
     return p
 
 
-SORT_ROWS = True      # process conv rows in occupancy-mask order on sparse 27-offset maps
-SORT_MIN_ROWS = int(os.environ.get('FC_SORT_MIN_ROWS', '8192'))
-SORT_DENSE = os.environ.get('FC_SORT_DENSE', '0') != '0'     # mask-sorted rows also on the generated / union (neck) maps
-# ... r3 A/B: only on the dense maps with at most this many rows (the 55k-row neck level issues 1.14x its useful MFMA work
-# in natural order and 1.02x in mask order, and its argsort is cheap — unlike the 441k-row level's)
-SORT_DENSE_MAX_ROWS = int(os.environ.get('FC_SORT_DENSE_MAX_ROWS', '0'))
-STRUCTURED_MAPS = os.environ.get('FC_STRUCTURED_MAPS', '1') != '0'   # generated sets: maps by index arithmetic (r3), A/B switch
-PAIRS_DENSE = os.environ.get('FC_PAIRS_DENSE', '0') != '0'   # pair lists (exact work) also on small dense maps (77 % occupied at 6.9k rows)
-WGRAD_PAIRS = os.environ.get('FC_WGRAD_PAIRS', '1') != '0'    # weight gradients reduce over exact pair lists there
-# ... and with at most this many result rows the convolution itself runs per offset over the pair lists
+# conv rows in occupancy-mask order on sparse 27-offset maps with at least this many result rows (below it the masks do not group
+# well enough to pay for themselves, tools/convbench.py); the native plan reads the same value
+SORT_MIN_ROWS = 8192
+# with at most this many result rows a pair-list map runs the convolution itself per offset over the pair lists
 # (r6, three-product kernels: 8 192 — the 14.7k-row level on its mask-sorted table — 462.9 scenes/s against 456.1 at 16 384 and 452.5 at
 # 2 048, same box; the six-product kernels of r3-r5 were level at 16 384 / 8 192: profiles/r5_notes.md section 7)
-PAIR_CONV_ROWS = int(os.environ.get('FC_PAIR_CONV_ROWS', '8192'))
+PAIR_CONV_ROWS = 8192
 _offs_cache = {}
 
 
@@ -444,23 +421,21 @@ class CoordMap(_Lazy):
             offs = kernel_offsets(kernel_size, self.stride, self.coords.device)
             K = offs.shape[0]
             nbr = torch.empty((K, out_map.n), dtype=torch.int32, device=self.coords.device)
-            if out_map is self and kernel_size == 3 and self._gen_parent is not None and STRUCTURED_MAPS:
+            if out_map is self and kernel_size == 3 and self._gen_parent is not None:
                 par = self._gen_parent                       # generated set: from the parent level's own k3 table
                 L.call('fc_kernel_map_children', L.ptr(par.kernel_map(par, 3).nbr), par.n, L.ptr(nbr), L.stream())
             else:
                 L.call('fc_kernel_map', L.ptr(out_map.coords), out_map.n, L.ptr(self.keys), L.ptr(self.vals), self.cap,
                        L.ptr(offs), K, L.ptr(nbr), L.stream())
             km = KernelMap(nbr, self.n, out_map.n)
-            # generated / union sets are ~94 % dense (2x2x2 blocks): nothing to skip there
-            # ... and below ~8k rows the masks do not group well enough to pay for themselves (tools/convbench.py)
-            # (r2: the generated / union sets are 77 % / 88 % / 94 % occupied; mask order would issue 1.10x / 1.02x / 1.00x the
+            # generated / union sets are ~94 % dense (2x2x2 blocks): nothing to skip there, and the weight gradient runs on the dense
+            # table.  (r2: the generated / union sets are 77 % / 88 % / 94 % occupied; mask order would issue 1.10x / 1.02x / 1.00x the
             # useful MFMA work instead of 1.30x / 1.14x / 1.07x and the isolated kernels gain 3...10 %, but in the full step
             # the extra argsort + permuted tables + scattered output rows cancel it exactly: 233.5 vs 233.5 scenes/s on the
-            # same box.  FC_SORT_DENSE=1 turns it on.)
+            # same box.)
             dense = self.dense_hint and out_map.dense_hint
-            km.sort_rows = (SORT_ROWS and K == 27 and out_map.n >= SORT_MIN_ROWS
-                            and (SORT_DENSE or not dense or out_map.n <= SORT_DENSE_MAX_ROWS))
-            km.use_pairs = WGRAD_PAIRS and K == 27 and (not dense or (PAIRS_DENSE and out_map.n <= PAIR_CONV_ROWS))
+            km.sort_rows = K == 27 and out_map.n >= SORT_MIN_ROWS and not dense
+            km.use_pairs = K == 27 and not dense
             self._kmaps.setdefault(out_map, {})[kernel_size] = km
         return km
 
@@ -475,7 +450,7 @@ class CoordMap(_Lazy):
         if ent is not None:
             return (self if ent[0] is None else ent[0]), ent[1], ent[2]
         dev = self.coords.device
-        if other._gen_parent is not None and STRUCTURED_MAPS:
+        if other._gen_parent is not None:
             # `other` is a generated children set: where each of MY voxels sits in it follows from its parent level's hash
             # (8 * parent row + child bits); if all of them are inside — the usual case, the backbone level inside the
             # generated set — the union IS `other`, with one probe pass and one count read-back and no hash of `other`

@@ -168,22 +168,57 @@ int fc_argsort27(const int* keys, int64_t n, int* order, void* ws, int64_t ws_by
 
 /* ---- sparse convolution ------------------------------------------------------------------- */
 
-/* flags bit24 (fc_conv_fwd, fc_conv_fwd_pairs, fc_conv_fwd_pairs_tiles): the same fp32 convolution (torch.float32 in and
- * out, as ME.MinkowskiConvolution computes it, me_resnet.py:56-62) on the bf16 matrix pipe by EXACT operand splitting —
- * x = x1 + x2 + x3 with three 8-bit pieces, six bf16 x bf16 products (each exact in the fp32 accumulator) per fp32 product
- * (the three dropped ones: <= 2^-24 of the product with the round-to-nearest split of r4);
- * results sit at fp32 rounding level against fp64, like the fp32 MFMA's (csrc/conv_x6.h, tests/test_gpu_ops.py).  128- and 256-row tiles.
- * flags bit26 (with bit24): `W` is not the fp32 kernel but its pre-split image built by fc_x6_weight_image — for the
- * backward-data pass the image of the transposed operator (then bit23 is not needed).
- * fc_x6_weight_image: image of W (K, R, C) — or, transposed != 0, of the operator W[k]^T where W[k] is stored (C, R) —
- * for a launch with Cin = R, Cout = C; R % 32 == 0, C % 64 == 0; fc_x6_weight_image_bytes(K, R, C) = 6 K R C bytes.
- * flags bit27 (with bit24 | bit26, r5): flat 64-bit addresses for the gathered rows and the image.  Without it a gathering launch
- * whose `in` ends below 2 GB (n_in Cin 4 bytes) reads both through buffer descriptors — a lane's row is a 32-bit byte offset
- * computed once per kernel offset, an absent neighbour an offset past the descriptor's end (the load returns zeros): the same
- * loads, bit-identical results, a third fewer address instructions per stage (csrc/conv_x6.h BUF).  Larger operands and
- * table-free launches (nbr == NULL) take the flat route by themselves.  The descriptor route addresses the weight image with
- * 32-bit offsets: a caller whose image reaches 4 GB (6 K Cin Cout bytes; 42 MB for the largest layer of the reference's networks)
- * sets bit27. */
+/* Bits of the `flags` word of the convolution entry points (fc_conv_fwd*, fc_conv_fwd_pairs*, fc_conv_wgrad*, the ws / stats size
+ * queries) and of fc_exec_run's cfg[1].  0 is the default route; tools/nbench and tools/convbench.py sweep the variant bits. */
+/* force the generic FMA kernels instead of the MFMA kernels (the parity cross-check) */
+#define FC_CONV_FMA (1 << 0)
+/* tuning fields, 0 = the plan's choice: bits 4-5 tile rows (1 = 64, 2 = 128, 3 = 256 x 64 tiles), bits 6-7 tile columns
+ * (1 = 64, 2 = 128), bits 8-15 S, the number of partial sums (offsets per split for a convolution, row ranges for a weight gradient) */
+#define FC_CONV_BM_SHIFT 4
+#define FC_CONV_BN_SHIFT 6
+#define FC_CONV_TILE_MASK 3
+#define FC_CONV_S_SHIFT 8
+#define FC_CONV_S_MASK 255
+/* weight gradient: never the deeper-pipelined kernel k_wgrad_mfma_p (the r1 kernel) */
+#define FC_CONV_WGRAD_PIPE_OFF (1 << 16)
+/* convolution: the deeper-pipelined LDS kernel k_conv_mfma_p off / on (else chosen by the number of workgroups) */
+#define FC_CONV_PIPE_OFF (1 << 17)
+#define FC_CONV_PIPE_ON (1 << 18)
+/* weight gradient over a table: 64-row chunks (ignored by fc_conv_wgrad_pairs) */
+#define FC_CONV_WGRAD_DEEP (1 << 19)
+/* weight gradient: k_wgrad_mfma_p wherever it applies */
+#define FC_CONV_WGRAD_PIPE_ON (1 << 20)
+/* convolution: the LDS-DMA kernel k_conv_glds (2 workgroups per CU) */
+#define FC_CONV_GLDS (1 << 21)
+/* convolution: offset-split launches of a dense table stay off the LDS-DMA kernel */
+#define FC_CONV_GLDS_OFF (1 << 22)
+/* fc_conv_fwd / fc_conv_fwd_pairs(_tiles), nbr != NULL: W[k] is stored TRANSPOSED, (Cout, Cin) row-major — the backward-data pass
+ * run on the layer's own (K, Cin, Cout) kernel without a transposed copy */
+#define FC_CONV_WT (1 << 23)
+/* the same fp32 convolution (torch.float32 in and out, as ME.MinkowskiConvolution computes it, me_resnet.py:56-62) on the matrix
+ * pipe by EXACT operand splitting — x = x1 + x2 + x3 with three 8-bit pieces, six bf16 x bf16 products (each exact in the fp32
+ * accumulator) per fp32 product (the three dropped ones: <= 2^-24 of the product with the round-to-nearest split of r4), or in
+ * split mode 2 two fp16 pieces and three products; results sit at fp32 rounding level against fp64, like the fp32 MFMA's
+ * (csrc/conv_x6.h, tests/test_gpu_ops.py).  128- and 256-row tiles.  Weight gradients: the split kernels (csrc/wgrad_x6.h)
+ * where one exists for the shape, the fp32 MFMA kernels otherwise. */
+#define FC_CONV_SPLIT (1 << 24)
+/* with FC_CONV_SPLIT: `W` is not the fp32 kernel but its pre-split image built by fc_x6_weight_image — for the backward-data pass
+ * the image of the transposed operator (then FC_CONV_WT is not needed) */
+#define FC_CONV_IMAGE (1 << 26)
+/* with FC_CONV_SPLIT (r5): flat 64-bit addresses for the gathered rows and the image.  Without it a gathering launch whose `in`
+ * ends below 2 GB (n_in Cin 4 bytes) reads both through buffer descriptors — a lane's row is a 32-bit byte offset computed once per
+ * kernel offset, an absent neighbour an offset past the descriptor's end (the load returns zeros): the same loads, bit-identical
+ * results, a third fewer address instructions per stage (csrc/conv_x6.h BUF).  Larger operands and table-free launches
+ * (nbr == NULL) take the flat route by themselves.  The descriptor route addresses the weight image with 32-bit offsets: a caller
+ * whose image reaches 4 GB (6 K Cin Cout bytes; 42 MB for the largest layer of the reference's networks) sets this bit. */
+#define FC_CONV_FLAT (1 << 27)
+/* weight gradient over a dense table: no multi-offset kernel k_wgrad_multi / restrict it to its first rule (Cin = 64, >= 32768 rows) */
+#define FC_CONV_WGRAD_MULTI_OFF (1 << 29)
+#define FC_CONV_WGRAD_MULTI_FIRST (1 << 30)
+
+/* fc_x6_weight_image: image of W (K, R, C) — or, transposed != 0, of the operator W[k]^T where W[k] is stored (C, R) —
+ * for a launch with Cin = R, Cout = C; R % 32 == 0, C % 64 == 0; fc_x6_weight_image_bytes(K, R, C) = 6 K R C bytes
+ * (the operand of FC_CONV_IMAGE launches of ME.MinkowskiConvolution, me_resnet.py:56-62). */
 int64_t fc_x6_weight_image_bytes(int K, int R, int C);
 int fc_x6_weight_image(const float* W, void* img, int K, int R, int C, int transposed, hipStream_t stream);
 /* The images of many kernels in ONE launch (all convolutions of a model — me_resnet.py:56-62, fcaf3d_neck_with_head.py:52,60-69 —
@@ -199,9 +234,7 @@ int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, hipStr
  * its backward-data pass (call with the transposed table and fc_transpose_weight'ed kernel), and with
  * nbr == NULL (K = 1, identity) the dense GEMMs of MinkowskiGenerativeConvolutionTranspose (:60-66)
  * and of the 1x1 head convolutions (:83-85, :257-263).  out[o] = sum_k in[nbr[k][o]] @ W[k].
- * flags bit0: force the generic FMA kernel instead of the MFMA kernel.  flags bit23 (also fc_conv_fwd_pairs /
- * _pairs_tiles; needs nbr != NULL): W[k] is stored TRANSPOSED, (Cout, Cin) row-major — the backward-data pass run on the
- * layer's own (K, Cin, Cout) kernel without a transposed copy.  Layers with too few rows to fill
+ * `flags`: the FC_CONV_* bits above.  Layers with too few rows to fill
  * the chip are split over kernel offsets into `ws` and summed in a fixed order (deterministic).
  * out_index (nullable): `nbr` is a table permuted into occupancy-mask order (fc_permute_nbr) and tile row t
  * belongs to output row out_index[t] — tiles of similar rows skip the offsets none of them has. */
@@ -231,7 +264,7 @@ int fc_conv_fwd_pairs_tiles(const float* in, const float* W, const int* pair_in,
  * block of their result, the column sums of the result and of its square — stats[fc_conv_stats_blocks(...)][2][Cout] — written
  * by whichever kernel produces the final rows (the MFMA tile epilogue, or the fixed-order sum of an offset-split / pair-list
  * launch).  fc_bn_train_fwd(part = stats) turns them into the batch statistics without reading the matrix again.  Split-bf16
- * route only (flags bits 24 | 26); fc_conv_stats_blocks returns 0 where a launch has no statistics epilogue.  stats == NULL:
+ * route only (FC_CONV_SPLIT | FC_CONV_IMAGE); fc_conv_stats_blocks returns 0 where a launch has no statistics epilogue.  stats == NULL:
  * exactly the plain entry points. */
 int64_t fc_conv_stats_blocks(int64_t n_out, int K, int Cin, int Cout, int flags, int pairs);
 int fc_conv_fwd_stats(const float* in, const float* W, const int* nbr, const int* out_index, float* out, int64_t n_in,
@@ -260,9 +293,9 @@ int fc_conv_fwd_pairs_tiles_bn_bwd_stats(const float* in, const float* W, const 
 
 /* backward-weights of ME.MinkowskiConvolution (autograd of me_resnet.py:19-21, :56-62 and fcaf3d_neck_with_head.py:52,
  * :60-69; `gW[k] += in[i]^T (x) gout[o]`): gW[k] = sum_o in[nbr[k][o]]^T (x) gout[o];
- * deterministic two-level reduction.  flags bit24 (both entry points): the split-bf16 kernels (csrc/wgrad_x6.h: fp32 in, fp32
- * accumulate, six exact bf16 x bf16 products per fp32 product) where one exists for the shape — dense tables that qualify for
- * the multi-offset kernel, pair lists with a 128-wide Cin or Cout; the fp32 MFMA kernels otherwise. */
+ * deterministic two-level reduction.  FC_CONV_SPLIT (both entry points): the split kernels (csrc/wgrad_x6.h: fp32 in, fp32
+ * accumulate, exact products) where one exists for the shape — dense tables that qualify for the multi-offset kernel, pair
+ * lists, table-free GEMMs; the fp32 MFMA kernels otherwise. */
 int64_t fc_conv_wgrad_ws_bytes(int64_t n_out, int K, int Cin, int Cout, int flags);
 int fc_conv_wgrad(const float* in, const float* gout, const int* nbr, const int* row_index, float* gW, int64_t n_in,
                   int64_t n_out, int K, int Cin, int Cout, int flags, void* ws, int64_t ws_bytes, hipStream_t stream);
@@ -469,7 +502,7 @@ int fc_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float
 
 /* SURVEY.md 8(f) rank 4 "bf16 fast mode" (No reference counterpart: the reference trains in fp32 throughout, configs/fcaf3d/fcaf3d.py:30-33
  * sets no fp16 hook).  A process-global, flagged NON-PARITY switch: while on, the split-bf16 convolution launches that read a
- * weight image (flags bits 24 | 26, 128-row tiles) and the split-bf16 weight-gradient launches multiply ONLY the leading bf16
+ * weight image (FC_CONV_SPLIT | FC_CONV_IMAGE, 128-row tiles) and the split-bf16 weight-gradient launches multiply ONLY the leading bf16
  * piece of either operand (the operand rounded to nearest bf16; fp32 accumulate) — one MFMA product instead of six.  Default
  * off; `bench.py` reports it as `config.bf16_fast_mode` with "parity": false, never as `value`. */
 int fc_set_bf16_fast(int on);
@@ -514,7 +547,7 @@ int fc_debug_set_h3r(int mode);
  * Operators [op_begin, op_end) run on streams[0] (caller's), streams[1] (head branch of the neck), streams[2] (weight
  * gradients), ordered by library-owned events.  ws / ws_bytes: one scratch buffer per stream; a sizing pass runs first: if a
  * buffer is too small NOTHING is launched, ws_need[3] receives the sizes and the call returns -2.
- * cfg[0]: the two-launch BatchNorm is used up to this many elements; cfg[1]: kernel-variant flags (as `flags` above);
+ * cfg[0]: the two-launch BatchNorm is used up to this many elements; cfg[1]: kernel-variant flags (the FC_CONV_* bits);
  * cfg[2] != 0: bracket every convolution operator with a HIP-event pair on its stream — fc_exec_probe_read(ms, meta, cap), called
  * after the device has drained, returns the number of brackets since the last read-out and writes their durations (ms) and
  * {map index | -1, direction, n_in, n_out, K, Cin, Cout, pair-list route} (8 int64 each): bench.py's live roofline measurement

@@ -46,10 +46,25 @@ def test_every_prototype_cites_its_reference_interface():
     assert not missing, missing
 
 
+def test_conv_flag_constants_mirror_the_header():
+    """every FC_CONV_* bit / field of the convolution `flags` word in include/fcaf3d_hip.h has its Python twin in
+    fcaf3d_amd.functional (CONV_*), with the same value"""
+    import re
+    import fcaf3d_amd.functional as Fn
+    from fcaf3d_amd._lib import HEADER
+    hdr = {}
+    for m in re.finditer(r'^#define FC_(CONV_\w+) \(?(\d+)(?: << (\d+))?\)?$', open(HEADER).read(), flags=re.M):
+        hdr[m.group(1)] = int(m.group(2)) << int(m.group(3) or 0)
+    assert len(hdr) == 19, hdr
+    assert (hdr['CONV_FMA'], hdr['CONV_WT'], hdr['CONV_SPLIT'], hdr['CONV_IMAGE'], hdr['CONV_FLAT']) == (1, 1 << 23, 1 << 24, 1 << 26, 1 << 27)
+    py = {k: v for k, v in vars(Fn).items() if re.fullmatch(r'CONV_[A-Z0-9_]+', k) and k not in ('CONV_X6',)}
+    assert py == hdr
+
+
 def test_statistics_table_sizes_fit_the_executors_arena_bound():
     """fc_conv_stats_blocks (pure host function) against the bound fcaf3d_amd/executor.py allocates a statistics table with:
     rows * (C / 8) * 4 + 8 * C + 256 bytes must hold blocks * 2 * C floats for every route and size (r5)."""
-    X6 = (1 << 24) | (1 << 26)
+    from fcaf3d_amd.functional import CONV_X6 as X6
     for C in (64, 128, 256, 512):
         for n in (1, 15, 16, 17, 100, 1023, 1024, 1025, 4095, 4096, 4097, 8192, 16384, 50000, 437248):
             for K, pairs in ((27, 0), (27, 1), (1, 0)):

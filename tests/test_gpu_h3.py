@@ -100,7 +100,7 @@ def test_register_operand_kernel_is_bit_identical(n_points, Cin, Cout, q):
     """csrc/conv_h3r.h: the gathered operand split in registers (one row per lane) instead of staged through LDS — the same pieces
     and products in the same order per accumulator: forward and backward-data bit for bit (dense tables, mask-sorted tables, pair
     lists, ragged tiles; buffer and flat addressing); the statistics epilogue agrees to rounding (other summation order).  The weight
-    gradient rides along: k_wgrad_x6t reads its rows through buffer descriptors or flat addresses (flags bit27) — the same bits."""
+    gradient rides along: k_wgrad_x6t reads its rows through buffer descriptors or flat addresses (CONV_FLAT) — the same bits."""
     from fcaf3d_amd import _lib as L
     import fcaf3d_amd.functional as Fn
     from tests.test_gpu_ops import _stats_case
@@ -113,7 +113,7 @@ def test_register_operand_kernel_is_bit_identical(n_points, Cin, Cout, q):
         for mode in (0, 2):
             for flat in (False, True):
                 L.call('fc_debug_set_h3r', mode)
-                Fn.FLAGS = f0 | ((1 << 27) if flat else 0)
+                Fn.FLAGS = f0 | (Fn.CONV_FLAT if flat else 0)
                 xx, ww = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
                 y, tab = Fn.sparse_conv(xx, ww, km, cm.n, True, want_stats=True)
                 y.backward(g)

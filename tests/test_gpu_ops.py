@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import fcaf3d_amd.functional as Fn
 from oracle import loss_oracle as lo
 from oracle import me_oracle as mo
 
@@ -165,7 +166,7 @@ def test_conv_mfma_small_tiles(Cin, Cout):
 
 
 def test_conv_backward_data_with_a_transposed_weight_copy():
-    """default: the backward-data pass reads the layer's own kernel as its transpose (flags bit23, every other conv test
+    """default: the backward-data pass reads the layer's own kernel as its transpose (CONV_WT, every other conv test
     here); this is the other route — fc_transpose_weight + the plain operand — on a dense-table and a pair-list map"""
     import fcaf3d_amd.functional as Fn
     assert Fn.DGRAD_WT
@@ -236,15 +237,19 @@ def test_conv_mfma_large_tiles(Cin, Cout):
     _conv_case(_dev(), 100000, Cin, Cout, 3, 1, 0, B=1)
 
 
-@pytest.mark.parametrize('flags,what', [(3 << 4, '256x64 LDS tile (4x1 waves)'), (1 << 29, 'one-offset dense weight gradient'),
-                                        (1 << 18, 'deeper-pipelined LDS kernel forced on'),
-                                        ((1 << 18) | (2 << 4), 'deeper-pipelined LDS kernel, 128-row tiles'),
-                                        ((1 << 18) | (3 << 4), 'deeper-pipelined LDS kernel, 256x64 tiles'),
-                                        (1 << 21, 'LDS-DMA kernel (global_load_lds, two stage buffers)'),
-                                        ((1 << 21) | (3 << 4), 'LDS-DMA kernel, 256x64 tiles'),
-                                        (1 << 17, 'r1 LDS kernel forced'), (1 << 16, 'r1 weight-gradient kernel'),
-                                        (1 << 20, 'pipelined weight-gradient kernel wherever it applies'),
-                                        ((1 << 16) | (1 << 29), 'r1 weight-gradient kernel, one offset per workgroup')])
+_BM128, _BM256 = 2 << Fn.CONV_BM_SHIFT, 3 << Fn.CONV_BM_SHIFT
+
+
+@pytest.mark.parametrize('flags,what', [(_BM256, '256x64 LDS tile (4x1 waves)'),
+                                        (Fn.CONV_WGRAD_MULTI_OFF, 'one-offset dense weight gradient'),
+                                        (Fn.CONV_PIPE_ON, 'deeper-pipelined LDS kernel forced on'),
+                                        (Fn.CONV_PIPE_ON | _BM128, 'deeper-pipelined LDS kernel, 128-row tiles'),
+                                        (Fn.CONV_PIPE_ON | _BM256, 'deeper-pipelined LDS kernel, 256x64 tiles'),
+                                        (Fn.CONV_GLDS, 'LDS-DMA kernel (global_load_lds, two stage buffers)'),
+                                        (Fn.CONV_GLDS | _BM256, 'LDS-DMA kernel, 256x64 tiles'),
+                                        (Fn.CONV_PIPE_OFF, 'r1 LDS kernel forced'), (Fn.CONV_WGRAD_PIPE_OFF, 'r1 weight-gradient kernel'),
+                                        (Fn.CONV_WGRAD_PIPE_ON, 'pipelined weight-gradient kernel wherever it applies'),
+                                        (Fn.CONV_WGRAD_PIPE_OFF | Fn.CONV_WGRAD_MULTI_OFF, 'r1 weight-gradient kernel, one offset per workgroup')])
 def test_conv_kernel_variants_behind_flags(flags, what):
     """every flag-selected kernel variant (conv.hip; the defaults are chosen by measurement) against the oracle,
     forward + backward-data + backward-weights, on a strided and an unstrided map"""
@@ -254,7 +259,7 @@ def test_conv_kernel_variants_behind_flags(flags, what):
 
 def test_pair_list_convolution_linear_live_tile_launch():
     """fc_conv_fwd_pairs_tiles (3-D grid and the linear list of live (offset, tile) workgroups) == the generic FMA kernel
-    (flags bit0; itself checked against the oracle by the tests above — a transitive check, stated here on purpose)."""
+    (CONV_FMA; itself checked against the oracle by the tests above — a transitive check, stated here on purpose)."""
     from fcaf3d_amd import _lib as L
     from fcaf3d_amd.sparse import CoordMap
     dev = _dev()
@@ -282,7 +287,7 @@ def test_pair_list_convolution_linear_live_tile_launch():
 @pytest.mark.parametrize('Cin,Cout', [(64, 64), (128, 128), (256, 128), (128, 64)])
 def test_dense_table_weight_gradient_kernels(Cin, Cout):
     """fc_conv_wgrad over a dense neighbour table: the multi-offset kernel (default from 4096 rows), the one-offset kernels
-    (flags bit29, and bit29 + bit16) and the row-range split override == the generic FMA kernel (flags bit0)."""
+    (CONV_WGRAD_MULTI_OFF, and with CONV_WGRAD_PIPE_OFF) and the row-range split override == the generic FMA kernel (CONV_FMA)."""
     from fcaf3d_amd import _lib as L
     from fcaf3d_amd.sparse import CoordMap
     dev = _dev()
@@ -303,8 +308,9 @@ def test_dense_table_weight_gradient_kernels(Cin, Cout):
         L.call('fc_conv_wgrad', L.ptr(x), L.ptr(go), L.ptr(km.nbr), None, L.ptr(gw), n, n, K, Cin, Cout, flags, L.ptr(ws), ws.numel(),
                L.stream())
         return gw.cpu()
-    ref = run(1)
-    for fl in (0, 1 << 29, (1 << 29) | (1 << 16), 1 << 30, 3 << 8, (5 << 8) | (1 << 29)):
+    ref = run(Fn.CONV_FMA)
+    off, s = Fn.CONV_WGRAD_MULTI_OFF, Fn.CONV_S_SHIFT
+    for fl in (0, off, off | Fn.CONV_WGRAD_PIPE_OFF, Fn.CONV_WGRAD_MULTI_FIRST, 3 << s, (5 << s) | off):
         got = run(fl)
         _close(got, ref, what=f'dense-table wgrad {Cin}->{Cout} flags={fl:#x}')
         assert torch.equal(got, run(fl)), f'weight gradient not repeatable bit for bit, flags={fl:#x}'
@@ -459,12 +465,12 @@ def test_generate_union_interp_prune():
     assert sum(len(p) for p in perms) == pm.n
 
 
-def test_generated_set_maps_by_index_arithmetic_equal_the_hash_path():
+def test_generated_set_maps_by_index_arithmetic_equal_hashed_sets_of_the_same_rows():
     """r3: the k3 kernel map of a generated children set (fc_kernel_map_children, from the parent level's table) and the
     rows of a backbone level inside it (fc_child_rows, from the parent level's hash) against (a) the generic hash-probe
-    path on the same sets (FC_STRUCTURED_MAPS off) and (b) the oracle's kernel map — exact; two generations deep, as the
-    neck chains them; and a union that really adds rows still takes the generic path."""
-    import fcaf3d_amd.sparse as SP
+    path on sets over the same coordinates built by CoordMap.from_coords (no parent link: fc_kernel_map / the union probe)
+    and (b) the oracle's kernel map — exact; two generations deep, as the neck chains them; and a union that really adds
+    rows still takes the generic path."""
     from fcaf3d_amd.sparse import CoordMap
     dev = _dev()
     _, c_ref, _ = _scene_coords(13, n_points=8000)
@@ -474,19 +480,20 @@ def test_generated_set_maps_by_index_arithmetic_equal_the_hash_path():
     mid, _, _ = mo.unique_first(c8)                                    # stride 8: every voxel lies in a child of `top`
 
     def build(structured):
-        SP.STRUCTURED_MAPS = structured
         cm_top, _, _ = CoordMap.from_coords(torch.from_numpy(top).to(dev), 16, 2)
         g1 = cm_top.generate()
+        if not structured:                                             # the same rows, hashed: no _gen_parent
+            g1, _, _ = CoordMap.from_coords(g1.coords.clone(), 8, 2)
         cm_mid, _, _ = CoordMap.from_coords(torch.from_numpy(mid).to(dev), 8, 2)
         u, rows, swapped = cm_mid.union(g1)
         g2 = u.generate()
+        if not structured:
+            g2, _, _ = CoordMap.from_coords(g2.coords.clone(), 4, 2)
+        assert (g1._gen_parent is not None) == (g2._gen_parent is not None) == structured
         return (g1.kernel_map(g1, 3).nbr.cpu().numpy(), rows.cpu().numpy(), swapped, u is g1,
                 g2.kernel_map(g2, 3).nbr.cpu().numpy(), g1.coords.cpu().numpy(), g2.coords.cpu().numpy(), g1._keys is None)
-    try:
-        a = build(True)
-        b = build(False)
-    finally:
-        SP.STRUCTURED_MAPS = True
+    a = build(True)
+    b = build(False)
     assert a[2] and a[3] and b[2] and b[3], 'the strided level lies inside the generated set'
     assert a[7] and not b[7], 'structured path must not build the generated set\'s hash; the generic path does'
     for x, y in zip(a[:7], b[:7]):
@@ -874,7 +881,7 @@ def test_non_finite_activations_on_the_split_route():
                                                   (3000, 64, 64, 8), (777, 128, 64, 2)])
 def test_buffer_and_flat_addressing_are_bit_identical(n_points, Cin, Cout, q):
     """csrc/conv_x6.h BUF (r5): gathering launches on a weight image read the rows and the image through buffer descriptors (32-bit
-    row offsets, absent neighbours = an offset past the descriptor: zeros); flags bit27 = the flat 64-bit addresses operands of
+    row offsets, absent neighbours = an offset past the descriptor: zeros); CONV_FLAT = the flat 64-bit addresses operands of
     2 GB and more take.  Forward and backward-data, dense tables and pair lists, full and ragged tiles: the same bits."""
     import fcaf3d_amd.functional as Fn
     dev = _dev()
@@ -884,7 +891,7 @@ def test_buffer_and_flat_addressing_are_bit_identical(n_points, Cin, Cout, q):
     f0 = Fn.FLAGS
     try:
         for flat in (False, True):
-            Fn.FLAGS = f0 | ((1 << 27) if flat else 0)
+            Fn.FLAGS = f0 | (Fn.CONV_FLAT if flat else 0)
             xx = x.clone().requires_grad_(True)
             y = Fn.sparse_conv(xx, w, km, cm.n)
             y.backward(g)

@@ -31,7 +31,7 @@ def main():
     ap.add_argument('--only', default='')
     ap.add_argument('--bm256', action='store_true')
     ap.add_argument('--unsorted', action='store_true', help='use the plain neighbour table (no occupancy-mask row order)')
-    ap.add_argument('--flags', type=int, default=0, help='extra flags for the default run (bit16: BK=32, bit17: BK=64)')
+    ap.add_argument('--flags', type=int, default=0, help='extra flags for the default run (fcaf3d_amd.functional CONV_* bits)')
     ap.add_argument('--default-only', action='store_true')
     ap.add_argument('--pairconv', action='store_true', help='forward: per-offset gather-GEMM over the pair lists')
     ap.add_argument('--pairs', action='store_true', help='with --wgrad: reduce over the exact pair lists')
@@ -93,7 +93,7 @@ def main():
                     if a.wgrad and bm == 2 and (Cin % 128 or a.pairs):
                         continue
                     for Sw in ((0, 2, 4, 8, 16, 32, 64, 128) if a.wgrad else (0,)):
-                        fl = (bm << 4) | (bn << 6) | ((S or Sw) << 8)
+                        fl = (bm << Fn.CONV_BM_SHIFT) | (bn << Fn.CONV_BN_SHIFT) | ((S or Sw) << Fn.CONV_S_SHIFT)
                         Fn.FLAGS = fl
                         try:
                             if a.wgrad and a.pairs:

@@ -9,7 +9,7 @@
 // Scenes follow fcaf3d_amd/synthetic.py (room 6 x 5 x 2.7 m, floor + walls + 15 cuboids, 100 000 points, 5 mm noise,
 // 2 cm voxels); coordinate sets and kernel maps are built on the HOST with ME's rules (first-occurrence row order,
 // floor-strided sets, generative 2x2x2 children) — only the convolution kernels under test run on the GPU.
-// Every case is checked against the library's generic FMA kernel (flags bit0) before it is timed.
+// Every case is checked against the library's generic FMA kernel (FC_CONV_FMA) before it is timed.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <algorithm>
@@ -337,7 +337,7 @@ int main(int argc, char** argv) {
       // reference: generic FMA kernel
       std::vector<float> ref;
       if (check) {
-        FC(fc_conv_fwd(d_in.p, d_w.p, d_nbr.p, nullptr, d_ref.p, n_in, n_out, K, Cin, Cout, 1, nullptr, 0, 0));
+        FC(fc_conv_fwd(d_in.p, d_w.p, d_nbr.p, nullptr, d_ref.p, n_in, n_out, K, Cin, Cout, FC_CONV_FMA, nullptr, 0, 0));
         ref = d_ref.down((size_t)n_out * Cout);
       }
       // fp64 on the host for 48 sampled output rows: how far each route is from the exact result (rms / max, of the output scale)
@@ -358,37 +358,38 @@ int main(int argc, char** argv) {
       }
       struct Run { const char* what; int flags; int tbl; bool wt = false; bool img = false; int smode = 0; bool hint = false; };   // smode: fc_set_split_mode (image runs); hint: amax precomputed     // tbl: 0 plain table, 1 mask-sorted, 2 pair lists, 3 live-tile pair lists
       std::vector<Run> runs;
-      const int X6 = 1 << 24, WTF = 1 << 23;
+      const int X6 = FC_CONV_SPLIT, WTF = FC_CONV_WT;
+      const int BM128 = 2 << FC_CONV_BM_SHIFT, BM256 = 3 << FC_CONV_BM_SHIFT, BN64 = 1 << FC_CONV_BN_SHIFT;
       runs.push_back({"plain ", 0, 0});
       if (!cs.dense) { runs.push_back({"sorted", 0, 1}); if (!x6_only) runs.push_back({"pairs ", 0, 2}); runs.push_back({"pairsL", 0, 3}); }
       runs.push_back({"plainT", WTF, 0, true});
       if (!x6_only) {
-        runs.push_back({"pipe  ", 1 << 18, 0});
-        if (!cs.dense) { runs.push_back({"pipeS ", 1 << 18, 1}); runs.push_back({"pipeL ", 1 << 18, 3}); }
-        if (Cout == 64) { runs.push_back({"256x64", 3 << 4, 0}); if (!cs.dense) runs.push_back({"256x64s", 3 << 4, 1}); }
-        runs.push_back({"glds  ", 1 << 21, 0});
-        if (!cs.dense) { runs.push_back({"gldsS ", 1 << 21, 1}); runs.push_back({"gldsL ", 1 << 21, 3}); }
-        if (Cout == 64) { runs.push_back({"glds256", (1 << 21) | (3 << 4), 0}); runs.push_back({"glds128", (1 << 21) | (2 << 4), 0}); }
+        runs.push_back({"pipe  ", FC_CONV_PIPE_ON, 0});
+        if (!cs.dense) { runs.push_back({"pipeS ", FC_CONV_PIPE_ON, 1}); runs.push_back({"pipeL ", FC_CONV_PIPE_ON, 3}); }
+        if (Cout == 64) { runs.push_back({"256x64", BM256, 0}); if (!cs.dense) runs.push_back({"256x64s", BM256, 1}); }
+        runs.push_back({"glds  ", FC_CONV_GLDS, 0});
+        if (!cs.dense) { runs.push_back({"gldsS ", FC_CONV_GLDS, 1}); runs.push_back({"gldsL ", FC_CONV_GLDS, 3}); }
+        if (Cout == 64) { runs.push_back({"glds256", FC_CONV_GLDS | BM256, 0}); runs.push_back({"glds128", FC_CONV_GLDS | BM128, 0}); }
       }
       // the split-bf16 kernel: weights split in the staging (x6), transposed weights (x6T), pre-split weight image (x6I), row orders
-      const int X6I = X6 | (1 << 26);
+      const int X6I = X6 | FC_CONV_IMAGE;
       runs.push_back({"x6    ", X6, 0});
       runs.push_back({"x6T   ", X6 | WTF, 0, true});
       runs.push_back({"x6I   ", X6I, 0, false, true});
       if (!cs.dense) { runs.push_back({"x6S   ", X6, 1}); runs.push_back({"x6IS  ", X6I, 1, false, true}); runs.push_back({"x6L   ", X6, 3}); runs.push_back({"x6IL  ", X6I, 3, false, true}); }
-      if (Cout == 64) { runs.push_back({"x6 128", X6 | (2 << 4), 0}); runs.push_back({"x6I128", X6I | (2 << 4), 0, false, true}); }
+      if (Cout == 64) { runs.push_back({"x6 128", X6 | BM128, 0}); runs.push_back({"x6I128", X6I | BM128, 0, false, true}); }
       // r6: the two-piece fp16 split (mode 2): same launches, image rebuilt in that mode; "+a": the operand's amax word handed in
       runs.push_back({"h3I   ", X6I, 0, false, true, 2});
       runs.push_back({"h3I+a ", X6I, 0, false, true, 2, true});
       if (!cs.dense) { runs.push_back({"h3IS  ", X6I, 1, false, true, 2}); runs.push_back({"h3IS+a", X6I, 1, false, true, 2, true}); runs.push_back({"h3IL  ", X6I, 3, false, true, 2}); runs.push_back({"h3IL+a", X6I, 3, false, true, 2, true}); }
-      if (Cout == 64) runs.push_back({"h3I256+a", X6I | (3 << 4), 0, false, true, 2, true});       // 256 x 64 tiles
+      if (Cout == 64) runs.push_back({"h3I256+a", X6I | BM256, 0, false, true, 2, true});       // 256 x 64 tiles
       if (Cout % 128 == 0 && n64) {      // r6: 64-column tiles on the launches that leave CUs empty with 128-column tiles
-        runs.push_back({"x6I n64", X6I | (1 << 6), 0, false, true});
-        if (!cs.dense) { runs.push_back({"x6ISn64", X6I | (1 << 6), 1, false, true}); runs.push_back({"x6ILn64", X6I | (1 << 6), 3, false, true}); }
+        runs.push_back({"x6I n64", X6I | BN64, 0, false, true});
+        if (!cs.dense) { runs.push_back({"x6ISn64", X6I | BN64, 1, false, true}); runs.push_back({"x6ILn64", X6I | BN64, 3, false, true}); }
       }
       static const char* snames[] = {"S=1", "S=2", "S=3", "S=4", "S=5", "S=6", "S=7", "S=8", "S=9", "S=10", "S=12", "S=14"};
       static const int svals[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14};
-      if (s_sweep) for (int q = 0; q < 12; ++q) runs.push_back({snames[q], svals[q] << 8, cs.dense ? 0 : 1});
+      if (s_sweep) for (int q = 0; q < 12; ++q) runs.push_back({snames[q], svals[q] << FC_CONV_S_SHIFT, cs.dense ? 0 : 1});
       for (const Run& r : runs) {
         const int fl = r.flags;
         const float* wp = r.img ? (const float*)d_img.p : (r.wt ? d_wt.p : d_w.p);
@@ -464,7 +465,7 @@ int main(int argc, char** argv) {
       std::vector<float> ref;
       if (check) {
         int64_t wb = ws_for(fc_conv_wgrad_ws_bytes(n_out, K, Cin, Cout, 1));
-        FC(fc_conv_wgrad(d_in.p, d_gout.p, d_nbr.p, nullptr, d_gwref.p, n_in, n_out, K, Cin, Cout, 1, d_ws.p, wb, 0));
+        FC(fc_conv_wgrad(d_in.p, d_gout.p, d_nbr.p, nullptr, d_gwref.p, n_in, n_out, K, Cin, Cout, FC_CONV_FMA, d_ws.p, wb, 0));
         ref = d_gwref.down(hw.size());
       }
       std::vector<int> wg_s = {0};
@@ -474,9 +475,10 @@ int main(int argc, char** argv) {
         for (int pairs = (s_sweep && !cs.dense ? 1 : 0); pairs < (cs.dense ? 1 : 2); ++pairs) {
           if (reg == 3 && pairs) continue;
           if (x6_only && (reg == 2 || reg == 3)) continue;
-          for (int smode = 0; smode <= (reg == 4 ? 3 : 0); smode += (smode == 2 ? 1 : 2)) {       // 3: mode 2 with flat addresses (flags bit27)
+          for (int smode = 0; smode <= (reg == 4 ? 3 : 0); smode += (smode == 2 ? 1 : 2)) {       // 3: mode 2 with flat addresses (FC_CONV_FLAT)
           FC(fc_set_split_mode(smode == 3 ? 2 : smode));
-          const int fl = ((reg == 2) << 16) | ((reg == 3) << 30) | ((reg == 4) << 24) | (fsw << 8) | ((smode == 3) << 27);
+          const int fl = (reg == 2 ? FC_CONV_WGRAD_PIPE_OFF : 0) | (reg == 3 ? FC_CONV_WGRAD_MULTI_FIRST : 0) | (reg == 4 ? FC_CONV_SPLIT : 0) |
+                         (fsw << FC_CONV_S_SHIFT) | (smode == 3 ? FC_CONV_FLAT : 0);
           int64_t wb = ws_for(fc_conv_wgrad_ws_bytes(n_out, K, Cin, Cout, fl));
           std::function<void()> fn;
           if (pairs) fn = [&, wb, fl]() { FC(fc_conv_wgrad_pairs(d_in.p, d_gout.p, d_pi.p, d_po.p, d_cnt.p, d_gw.p, n_in, n_out, K, Cin, Cout, fl, d_ws.p, wb, 0)); };
