@@ -1,6 +1,8 @@
 """The members of the reference's GT box container that the FCAF3D path touches
-(mmdet3d/core/bbox/structures/base_box3d.py:36-70, depth_box3d.py:41-48) and `bbox3d2result`
+(mmdet3d/core/bbox/structures/base_box3d.py:36-70, depth_box3d.py:41-48), the ones test-time augmentation maps results back
+with (clone / flip / scale / cat), `bbox3d_mapping_back` (mmdet3d/core/bbox/transforms.py:4-23) and `bbox3d2result`
 (mmdet3d/core/bbox/transforms.py:49-75)."""
+import numpy as np
 import torch
 
 
@@ -49,6 +51,49 @@ class DepthInstance3DBoxes:
 
     def __len__(self):
         return self.tensor.shape[0]
+
+    def clone(self):
+        """base_box3d.py:330-339"""
+        return type(self)(self.tensor.clone(), box_dim=self.box_dim, with_yaw=self.with_yaw)
+
+    def flip(self, bev_direction='horizontal'):
+        """depth_box3d.py:189-197, in place: horizontal x -> -x, yaw -> -yaw + pi; vertical y -> -y, yaw -> -yaw (the yaw only
+        when the boxes carry one)"""
+        assert bev_direction in ('horizontal', 'vertical')
+        if bev_direction == 'horizontal':
+            self.tensor[:, 0::7] = -self.tensor[:, 0::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6] + np.pi
+        else:
+            self.tensor[:, 1::7] = -self.tensor[:, 1::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6]
+
+    def scale(self, scale_factor):
+        """base_box3d.py:215-222, in place"""
+        self.tensor[:, :6] *= scale_factor
+        self.tensor[:, 7:] *= scale_factor
+
+    @classmethod
+    def cat(cls, boxes_list):
+        """base_box3d.py:290-312: never shares storage with its inputs"""
+        assert isinstance(boxes_list, (list, tuple))
+        if len(boxes_list) == 0:
+            return cls(torch.empty(0))
+        return cls(torch.cat([b.tensor for b in boxes_list], dim=0), box_dim=boxes_list[0].tensor.shape[1],
+                   with_yaw=boxes_list[0].with_yaw)
+
+
+def bbox3d_mapping_back(bboxes, scale_factor, flip_horizontal, flip_vertical):
+    """mmdet3d/core/bbox/transforms.py:4-23: boxes found on an augmented copy back in the frame of the original scene — flip
+    horizontal, flip vertical, then scale by 1 / scale_factor"""
+    new_bboxes = bboxes.clone()
+    if flip_horizontal:
+        new_bboxes.flip('horizontal')
+    if flip_vertical:
+        new_bboxes.flip('vertical')
+    new_bboxes.scale(1 / scale_factor)
+    return new_bboxes
 
 
 def bbox3d2result(bboxes, scores, labels):

@@ -6,6 +6,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
+# post-processing kernels that never run in the training step (test-time augmentation merge): compiled into the same library, kept
+# out of csrc/ so that source_hash() — the hash every profile under profiles/ was taken on — does not cover them
+CSRC_POST = os.path.join(HERE, 'csrc_post')
+# the C ABI header: csrc/plan.hip returns its FC_ABI_VERSION, so every object depends on it (a stale object would report the old
+# version and _lib.lib() would refuse the library)
+ABI_HEADER = os.path.join(os.path.dirname(HERE), 'include', 'fcaf3d_hip.h')
 LIB = os.path.join(HERE, 'libfcaf3d_hip.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-Wno-unused-result']
@@ -16,7 +22,12 @@ FILE_FLAGS = {'conv.hip': ['-fno-slp-vectorize'], 'norm.hip': ['-fno-slp-vectori
 
 
 def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith('.hip'))
+    """(directory, file name) of every .hip the library is built from: csrc/ then csrc_post/, each in name order"""
+    return [(d, f) for d in (CSRC, CSRC_POST) if os.path.isdir(d) for f in sorted(os.listdir(d)) if f.endswith('.hip')]
+
+
+def _headers():
+    return [os.path.join(d, f) for d in (CSRC, CSRC_POST) if os.path.isdir(d) for f in sorted(os.listdir(d)) if f.endswith('.h')] + [ABI_HEADER]
 
 
 def source_hash():
@@ -40,11 +51,11 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
+    hdrs = _headers()
     objs, jobs = [], []
-    for s in _sources():
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(CSRC, s[:-4] + '.o')
+    for d, s in _sources():
+        src = os.path.join(d, s)
+        obj = os.path.join(d, s[:-4] + '.o')
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
             jobs.append([HIPCC] + FLAGS + FILE_FLAGS.get(s, []) + ['-c', src, '-o', obj])
@@ -77,11 +88,11 @@ def build_tools(verbose=True):
     tdir = os.path.join(tools, 'trace')
     os.makedirs(tdir, exist_ok=True)
     objs = []
-    for s in _sources():
+    for d, s in _sources():
         obj = os.path.join(tdir, s[:-4] + '.o')
         objs.append(obj)
-        src = os.path.join(CSRC, s)
-        if _stale(obj, [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]):
+        src = os.path.join(d, s)
+        if _stale(obj, [src] + _headers()):
             run([HIPCC] + FLAGS + ['-DFC_TRACE', '-c', src, '-o', obj])
     tlib = os.path.join(tdir, 'libfcaf3d_hip.so')
     run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', tlib] + objs)

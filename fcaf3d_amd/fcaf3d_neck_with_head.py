@@ -408,7 +408,129 @@ class Fcaf3DNeckWithHead(nn.Module):
         on the whole batch (one segmented sort), then every (scene, class) segment goes through ONE pair of NMS launches and
         one read-back of the survivor counts.  Candidates reach the NMS in the order of the per-scene loop (scene, level,
         then descending max score where top-k bites, row order where it does not), all sorts are stable: same results."""
-        B, Lv = len(img_metas), len(centernesses)
+        B = len(img_metas)
+        P, PB, ordr, kept, kcount, n_max, C, yaw_flag = self._first_stage(centernesses, bbox_preds, cls_scores, points, B)
+        dev = P.device
+        valid = torch.arange(n_max, device=dev)[None, :] < kcount[:, None]
+        done = None
+        if defer:
+            done = torch.cuda.Event()
+            done.record()                                  # everything this batch needs is enqueued up to here
+
+        def finish(post=None):
+            # from here on the sizes are data: `nonzero` and `tolist` wait for everything enqueued above.  Deferred (two batches
+            # in flight): on the read-back stream behind THIS batch's event — a synchronisation of the main stream would wait for
+            # the next batch's forward pass, which is already enqueued there
+            if done is not None:
+                rb = _readback_stream(dev)
+                rb.wait_event(done)
+                with torch.cuda.stream(rb):
+                    res = collect()
+                    return post(res) if post is not None else res
+            res = collect()
+            return post(res) if post is not None else res
+
+        def collect():
+            sc_seg, p = torch.nonzero(valid, as_tuple=True)     # (scene, class)-major, ascending position = descending score
+            idx = ordr[sc_seg, kept[sc_seg, p].long()]
+            out_scene, out_cls = sc_seg // C, sc_seg % C
+            out_boxes = PB[out_scene, idx]
+            out_scores = P[out_scene, idx, out_cls]
+            sizes = count_ids(out_scene, B).tolist()          # the one read-back
+            results, o = [], 0
+            for i, n in enumerate(sizes):
+                b = out_boxes[o:o + n]
+                if yaw_flag:
+                    box_dim, with_yaw = 7, True
+                else:
+                    box_dim, with_yaw, b = 6, False, b[:, :6]
+                results.append((img_metas[i]['box_type_3d'](b, box_dim=box_dim, with_yaw=with_yaw, origin=(.5, .5, .5)),
+                                out_scores[o:o + n], out_cls[o:o + n]))
+                o += n
+            return results
+        return finish if defer else finish()
+
+    # set to a list: get_bboxes_aug appends a (start, end) pair of device events around its merge stage (tools/ttabench.py)
+    merge_events = None
+
+    def get_bboxes_aug(self, centernesses, bbox_preds, cls_scores, points, img_metas, rescale=False):
+        """Test-time augmentation (merge_augs.py:7-91 for a batch): the head outputs are those of B * A scenes, augmentation a of
+        scene b at position a * B + b; img_metas[a][b] its meta (pcd_scale_factor / pcd_horizontal_flip / pcd_vertical_flip;
+        absent: 1 / False / False).  Returns B (boxes, scores, labels) in the original frames, by descending score.
+        Batched route: the first stage of `_get_bboxes_batched` on all B * A scenes; per (scene, class) the A survivor lists
+        merged and mapped back (csrc_post/merge.hip, reading the first stage's tables in place); the merge NMS on those segments;
+        per scene the C survivor lists merged by descending score and cut to max_num.  Two read-backs: the merged sizes (they
+        size the NMS workspace: a static bound A * nms_pre * levels would take GBs) and the final counts."""
+        A, B = len(img_metas), len(img_metas[0])
+        assert all(len(m) == B for m in img_metas), 'every augmentation must hold the same scenes'
+        flat = [m for ms in img_metas for m in ms]
+        assert len(centernesses[0]) == len(flat)
+        if not (self.batched_decode and self.test_cfg.nms_pre > 0 and all(
+                isinstance(v, SceneList) for group in (centernesses, bbox_preds, cls_scores, points) for v in group)):
+            from .merge_augs import merge_aug_single
+            per = self.get_bboxes(centernesses, bbox_preds, cls_scores, points, flat)
+            return [merge_aug_single([dict(boxes_3d=per[a * B + b][0], scores_3d=per[a * B + b][1], labels_3d=per[a * B + b][2])
+                                      for a in range(A)], img_metas_b, self.test_cfg)
+                    for b, img_metas_b in enumerate(zip(*img_metas))]
+        from .merge_augs import (MERGE_TO_BOTTOM, MERGE_WITH_YAW, aug_params, merge_cfg, merge_sorted_segments,
+                                 transform_word)
+        P, PB, ordr, kept, kcount, n_max, C, yaw_flag = self._first_stage(centernesses, bbox_preds, cls_scores, points, A * B)
+        dev = P.device
+        nms_thr, rotated, max_num = merge_cfg(self.test_cfg, yaw_flag)
+        mc = kcount.view(A, B, C).sum(0)                                       # survivors per merged (scene, class) segment
+        s1, tot = torch.stack((mc.max(), mc.sum(1).max())).tolist()           # read-back 1: the merged sizes
+        S1 = max(1, s1)
+        ev = None
+        if self.merge_events is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        # ---- (scene, class): the A survivor lists, mapped back, into one descending list --------------------------------
+        a_, b_, c_ = np.meshgrid(np.arange(A), np.arange(B), np.arange(C), indexing='ij')
+        s_ = a_ * B + b_                                                       # the augmented scene
+        xf = np.array([transform_word(*aug_params(m)) for m in flat], dtype=np.int64)
+        desc1 = np.stack((s_ * C + c_, s_ * n_max, s_ * n_max * C + c_, xf[s_]), -1).transpose(1, 2, 0, 3)   # (B, C, A, 4)
+        desc1 = L.upload(np.ascontiguousarray(desc1.reshape(-1, 4)), dev)
+        flags = MERGE_TO_BOTTOM | (MERGE_WITH_YAW if yaw_flag else 0)
+        mb, ms, _, mcount = merge_sorted_segments(desc1, A, kcount, P, PB, max_total=S1, stride_out=S1, keep=kept,
+                                                  keep_stride=n_max, order=ordr, order_stride=n_max, score_stride=C,
+                                                  flags=flags)
+        # ---- merge NMS on every (scene, class) segment, in scene chunks whose masks fit NMS_WS_BUDGET ----------------------
+        seg_bytes = S1 * ((S1 + 63) // 64) * 8
+        per = max(1, min(B, self.NMS_WS_BUDGET // max(1, C * seg_bytes)))
+        keep_l, kc_l = [], []
+        for b0 in range(0, B, per):
+            b1 = min(B, b0 + per)
+            k_, c_n = _nms_run(mb[b0 * C:b1 * C], mcount[b0 * C:b1 * C], nms_thr, rotated)
+            keep_l.append(k_)
+            kc_l.append(c_n)
+        keep2 = keep_l[0] if len(keep_l) == 1 else torch.cat(keep_l)
+        kc2 = kc_l[0] if len(kc_l) == 1 else torch.cat(kc_l)
+        # ---- scene: the C class lists into one descending list, cut to max_num ---------------------------------------------
+        g = np.arange(B * C, dtype=np.int64)
+        desc2 = np.stack((g, g * S1, g * S1, np.full_like(g, transform_word(1.0, False, False))), -1)
+        desc2 = L.upload(desc2, dev)
+        S2 = max(1, tot if max_num is None else min(tot, max_num))
+        fb, fs, fsrc, fcount = merge_sorted_segments(desc2, C, kc2, ms, mb, max_total=tot, stride_out=S2, keep=keep2,
+                                                     keep_stride=S1, cap=-1 if max_num is None else max_num)
+        if ev is not None:
+            ev[1].record()
+            self.merge_events.append(ev)
+        counts = fcount.tolist()                                               # read-back 2: the final counts
+        results = []
+        for b, n in enumerate(counts):
+            bx = fb[b, :n]
+            box_dim, with_yaw = (7, True) if yaw_flag else (6, False)
+            results.append((img_metas[0][b]['box_type_3d'](bx[:, :box_dim], box_dim=box_dim, with_yaw=with_yaw),
+                            fs[b, :n], fsrc[b, :n, 0].long()))
+        return results
+
+    def _first_stage(self, centernesses, bbox_preds, cls_scores, points, B):
+        """The per-scene decode + per-class NMS of `_get_bboxes_batched` for B scenes, up to the survivor tables — shared with
+        `get_bboxes_aug`, whose B * A augmented scenes go through it as one batch.  Returns (P, PB, ordr, kept, kcount, n_max, C,
+        yaw_flag): P (B, n_max, C) scores and PB (B, n_max, 7) gravity-centre boxes of the candidate slots, ordr (B * C, n_max) the
+        descending-score order of every (scene, class) segment, kept (B * C, n_max) the NMS survivors' positions in it, kcount
+        (B * C,) int32 their number (device)."""
+        Lv = len(centernesses)
         cfg = self.test_cfg
         dev = centernesses[0].full.device
         sc_l, mx_l, bx_l, sg_l = [], [], [], []
@@ -461,44 +583,7 @@ class Fcaf3DNeckWithHead(nn.Module):
             kcount_l.append(c_)
         kept = kept_l[0] if len(kept_l) == 1 else torch.cat(kept_l)
         kcount = kcount_l[0] if len(kcount_l) == 1 else torch.cat(kcount_l)
-        valid = torch.arange(n_max, device=dev)[None, :] < kcount[:, None]
-        done = None
-        if defer:
-            done = torch.cuda.Event()
-            done.record()                                  # everything this batch needs is enqueued up to here
-
-        def finish(post=None):
-            # from here on the sizes are data: `nonzero` and `tolist` wait for everything enqueued above.  Deferred (two batches
-            # in flight): on the read-back stream behind THIS batch's event — a synchronisation of the main stream would wait for
-            # the next batch's forward pass, which is already enqueued there
-            if done is not None:
-                rb = _readback_stream(dev)
-                rb.wait_event(done)
-                with torch.cuda.stream(rb):
-                    res = collect()
-                    return post(res) if post is not None else res
-            res = collect()
-            return post(res) if post is not None else res
-
-        def collect():
-            sc_seg, p = torch.nonzero(valid, as_tuple=True)     # (scene, class)-major, ascending position = descending score
-            idx = ordr[sc_seg, kept[sc_seg, p].long()]
-            out_scene, out_cls = sc_seg // C, sc_seg % C
-            out_boxes = PB[out_scene, idx]
-            out_scores = P[out_scene, idx, out_cls]
-            sizes = count_ids(out_scene, B).tolist()          # the one read-back
-            results, o = [], 0
-            for i, n in enumerate(sizes):
-                b = out_boxes[o:o + n]
-                if yaw_flag:
-                    box_dim, with_yaw = 7, True
-                else:
-                    box_dim, with_yaw, b = 6, False, b[:, :6]
-                results.append((img_metas[i]['box_type_3d'](b, box_dim=box_dim, with_yaw=with_yaw, origin=(.5, .5, .5)),
-                                out_scores[o:o + n], out_cls[o:o + n]))
-                o += n
-            return results
-        return finish if defer else finish()
+        return P, PB, ordr, kept, kcount, n_max, C, yaw_flag
 
     def _get_bboxes_single(self, centernesses, bbox_preds, cls_scores, points, img_meta):
         mlvl_bboxes, mlvl_scores = [], []

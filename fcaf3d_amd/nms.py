@@ -18,15 +18,16 @@ def _run(boxes_seg, counts, thresh, rotated):
     return keep, kcount
 
 
-def nms_bev(boxes, scores, thresh, rotated=True):
-    """boxes (N,7) [x,y,z,dx,dy,dz,heading], scores (N,) -> LongTensor of kept indices, by descending score."""
+def nms_bev(boxes, scores, thresh, rotated=True, stable=False):
+    """boxes (N,7) [x,y,z,dx,dy,dz,heading], scores (N,) -> LongTensor of kept indices, by descending score.
+    stable=True: equal scores keep their input order (the test-time augmentation merge, merge_augs.py)."""
     assert boxes.shape[1] == 7
     if not boxes.is_cuda:
         raise RuntimeError('BEV NMS runs on the GPU only (HIP)')
     n = boxes.shape[0]
     if n == 0:
         return torch.zeros(0, dtype=torch.long, device=boxes.device)
-    order = scores.sort(0, descending=True)[1]
+    order = scores.sort(dim=0, descending=True, stable=True)[1] if stable else scores.sort(0, descending=True)[1]
     sorted_boxes = boxes[order].contiguous().unsqueeze(0)
     counts = torch.tensor([n], dtype=torch.int32, device=boxes.device)
     keep, kcount = _run(sorted_boxes, counts, thresh, rotated)

@@ -7,13 +7,16 @@ a whole scene at once — so that feeding hundreds of scenes/s does not hang on 
   IndoorPointSample         transforms_3d.py:821-895                       -> indoor_point_sample
   RandomFlip3D              transforms_3d.py:59-170  (+ depth_box3d.py:178-208, depth_points.py:28-33)  -> flip_bev
   GlobalRotScaleTrans       transforms_3d.py:493-645 (+ depth_box3d.py:113-176, base_box3d.py:149-222)  -> rot_scale_trans
+  MultiScaleFlipAug3D       test_time_aug.py:10-107  (test-time augmentation; collate_aug batches its outputs)
 
 Boxes are Depth-mode (m,7) `[x, y, z_bottom, dx, dy, dz, yaw]` tensors (`DepthInstance3DBoxes.tensor`); points (n,3+C).
 The deterministic parts take their parameters explicitly (parity-tested against the reference's own box / point classes,
 tests/golden/pipeline.npz); `TrainAugment` draws them the way the reference's classes do.  Everything is plain torch:
 elementwise work on one scene, nothing here deserves a kernel.
 """
+import copy
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -351,15 +354,17 @@ def _boxes_of(results):
 
 @PIPELINES.register_module()
 class RandomFlip3D:
-    """transforms_3d.py:59-170 with sync_2d=False: one uniform draw for the (absent) 2D flip of mmdet's RandomFlip, then
-    one per BEV direction."""
+    """transforms_3d.py:59-170 with sync_2d=False: one uniform draw for the (absent) 2D flip of mmdet's RandomFlip — taken only
+    when `flip` is not set yet, as mmdet's RandomFlip does (MultiScaleFlipAug3D sets it) — then one per BEV direction whose
+    flag is not preset (transforms_3d.py:144-151)."""
 
     def __init__(self, sync_2d=True, flip_ratio_bev_horizontal=0.0, flip_ratio_bev_vertical=0.0, **unused):
         assert not sync_2d, 'FCAF3D flips point clouds only (sync_2d=False)'
         self.h, self.v = flip_ratio_bev_horizontal, flip_ratio_bev_vertical
 
     def __call__(self, results):
-        np.random.rand()                                        # mmdet RandomFlip.__call__: the image flip draw
+        if 'flip' not in results:
+            np.random.rand()                                    # mmdet RandomFlip.__call__: the image flip draw
         if 'pcd_horizontal_flip' not in results:
             results['pcd_horizontal_flip'] = bool(np.random.rand() < self.h)
         if 'pcd_vertical_flip' not in results:
@@ -455,6 +460,66 @@ class Compose:
             if results is None:
                 return None
         return results
+
+
+@PIPELINES.register_module()
+class MultiScaleFlipAug3D:
+    """mmdet3d/datasets/pipelines/test_time_aug.py:10-107: one deep copy of `results` per augmentation, in the loop order img_scale
+    -> pts_scale_ratio -> flip ([True] if flip else [False]) -> pcd_horizontal_flip ([False, True] if flip and
+    pcd_horizontal_flip else [False]) -> pcd_vertical_flip (likewise) -> flip_direction, with scale / flip / pcd_scale_factor /
+    flip_direction / pcd_horizontal_flip / pcd_vertical_flip set before `transforms` run on it.  Returns a dict of lists
+    (collate_aug turns B of them into points[a][b], img_metas[a][b])."""
+
+    def __init__(self, transforms, img_scale, pts_scale_ratio, flip=False, flip_direction='horizontal',
+                 pcd_horizontal_flip=False, pcd_vertical_flip=False):
+        self.transforms = Compose(transforms)
+        self.img_scale = img_scale if isinstance(img_scale, list) else [img_scale]
+        self.pts_scale_ratio = pts_scale_ratio if isinstance(pts_scale_ratio, list) else [float(pts_scale_ratio)]
+        assert all(isinstance(s, tuple) for s in self.img_scale)
+        assert all(isinstance(s, float) for s in self.pts_scale_ratio)
+        self.flip = flip
+        self.pcd_horizontal_flip = pcd_horizontal_flip
+        self.pcd_vertical_flip = pcd_vertical_flip
+        self.flip_direction = flip_direction if isinstance(flip_direction, list) else [flip_direction]
+        assert all(isinstance(d, str) for d in self.flip_direction)
+        if not self.flip and self.flip_direction != ['horizontal']:
+            warnings.warn('flip_direction has no effect when flip is set to False')
+        if self.flip and not any(t['type'] in ('RandomFlip3D', 'RandomFlip') for t in transforms):
+            warnings.warn('flip has no effect when RandomFlip is not in transforms')
+
+    def __call__(self, results):
+        aug_data = []
+        flip_aug = [True] if self.flip else [False]
+        h_aug = [False, True] if self.flip and self.pcd_horizontal_flip else [False]
+        v_aug = [False, True] if self.flip and self.pcd_vertical_flip else [False]
+        for scale in self.img_scale:
+            for pts_scale_ratio in self.pts_scale_ratio:
+                for flip in flip_aug:
+                    for h in h_aug:
+                        for v in v_aug:
+                            for direction in self.flip_direction:
+                                _results = copy.deepcopy(results)
+                                _results['scale'] = scale
+                                _results['flip'] = flip
+                                _results['pcd_scale_factor'] = pts_scale_ratio
+                                _results['flip_direction'] = direction
+                                _results['pcd_horizontal_flip'] = h
+                                _results['pcd_vertical_flip'] = v
+                                aug_data.append(self.transforms(_results))
+        out = {key: [] for key in aug_data[0]}
+        for data in aug_data:
+            for key, val in data.items():
+                out[key].append(val)
+        return out
+
+
+def collate_aug(samples):
+    """B outputs of a pipeline ending in MultiScaleFlipAug3D (dicts of A-long lists) -> dict(points=points[a][b],
+    img_metas=img_metas[a][b]): the layout of forward_test / aug_test (detectors/base.py:14-43)"""
+    A = len(samples[0]['points'])
+    assert all(len(s['points']) == A for s in samples), 'every scene must have the same augmentations'
+    return dict(points=[[s['points'][a] for s in samples] for a in range(A)],
+                img_metas=[[s['img_metas'][a] for s in samples] for a in range(A)])
 
 
 def _pre_pipeline(self, index, points_file=None):

@@ -257,13 +257,28 @@ class SingleStageSparse3DDetector(nn.Module):
         return lambda: finish(bbox3d2result_batch)
 
     def aug_test(self, points, img_metas, imgs=None, rescale=False):
-        pass
+        """Test-time augmentation (a stub in the reference: single_stage_sparse.py:61-62; GroupFree3D's groupfree3dnet.py:83-105 for
+        one scene): points[a][b] / img_metas[a][b] = augmentation a of scene b (pipelines.MultiScaleFlipAug3D + collate_aug).  The
+        B * A augmented scenes are ONE batch through the forward pass; the results are merged on the device
+        (Fcaf3DNeckWithHead.get_bboxes_aug: merge_aug_bboxes_3d per scene).  Returns B result dicts, as simple_test does.
+        Meant for eval mode: in train mode BatchNorm's batch statistics would mix the augmented copies."""
+        A = len(points)
+        assert A >= 1 and len(img_metas) == A, 'points[a][b] and img_metas[a][b]: one list per augmentation'
+        B = len(points[0])
+        assert all(len(p) == B for p in points) and all(len(m) == B for m in img_metas), \
+            'every augmentation must hold the same B scenes'
+        flat_points = [p for pa in points for p in pa]
+        flat_metas = [m for ma in img_metas for m in ma]
+        x = self.extract_feat(flat_points, flat_metas)
+        bbox_list = self.neck_with_head.get_bboxes_aug(*x, img_metas, rescale=rescale)
+        return bbox3d2result_batch(bbox_list)
 
     def forward_test(self, points, img_metas, img=None, **kwargs):
-        # base.py:14-43: one (non-augmented) sample per list entry
+        # base.py:14-43: points[a][b], img_metas[a][b] — one augmentation goes to simple_test, more to aug_test
         if isinstance(points[0], (list, tuple)):
-            assert len(points) == 1, 'test-time augmentation is a stub in the reference (aug_test: pass)'
-            return self.simple_test(points[0], img_metas[0], **kwargs)
+            if len(points) == 1:
+                return self.simple_test(points[0], img_metas[0], **kwargs)
+            return self.aug_test(points, img_metas, **kwargs)
         return self.simple_test(points, img_metas, **kwargs)
 
     def forward(self, return_loss=True, **kwargs):

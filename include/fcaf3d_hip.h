@@ -31,9 +31,10 @@ extern "C" {
 /* Version of this ABI (No reference counterpart): bumped whenever a prototype or the meaning of a flag bit changes — r5 -> 5
  * (flags bit27 went from "input is pre-split planes" to "flat addressing", fc_x6_planes / fc_conv_x6d removed: ADVICE r5),
  * r6 -> 6 (fc_compact_rows takes the output capacity; fc_plan_*, fc_argsort27 added), r6 -> 7 (fc_set_split_mode / fc_get_split_mode / fc_amax /
- * fc_conv_amax_hint / fc_amax_out_hint added; weight images are mode-dependent and fc_x6_weight_images writes their amax word).  A caller built against another
+ * fc_conv_amax_hint / fc_amax_out_hint added; weight images are mode-dependent and fc_x6_weight_images writes their amax word), -> 8
+ * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation).  A caller built against another
  * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 7
+#define FC_ABI_VERSION 8
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -483,6 +484,33 @@ int fc_nms_bev(const float* boxes, const int* counts_dev, int nseg, int stride, 
 /* pcdet_nms boxes_iou_bev_gpu (iou3d_nms_kernel.cu:251-265): (n,m) BEV IoU matrix. */
 int fc_boxes_iou_bev(const float* boxes_a, int n, const float* boxes_b, int m, int rotated, float* out,
                      hipStream_t stream);
+
+/* ---- test-time augmentation merge (fcaf3d_amd/csrc_post/merge.hip) ------------------------------------------------ */
+
+/* `flags` of fc_merge_sorted_segments: FC_MERGE_TO_BOTTOM converts gravity-centre input boxes to the bottom-centre tensor of
+ * DepthInstance3DBoxes first (base_box3d.py:62-66); FC_MERGE_WITH_YAW lets the flips touch the yaw column (depth_box3d.py:189-197).
+ * Bits of a segment descriptor's word [3] above its fp32 scale: the flips of that input segment. */
+#define FC_MERGE_TO_BOTTOM 1
+#define FC_MERGE_WITH_YAW 2
+#define FC_MERGE_XF_FLIP_H (1ull << 32)
+#define FC_MERGE_XF_FLIP_V (1ull << 33)
+/* merge_aug_bboxes_3d (mmdet3d/core/post_processing/merge_augs.py:36-47, the concatenation of the mapped-back results of every
+ * augmentation in augmentation order, and :65-89, the class-major lists sorted by descending score and cut to max_num) as a
+ * stable k-way merge: output segment o takes the input segments g = o*K + k, k = 0..K-1, each sorted by descending score.
+ * desc (nseg_out*K, 4) int64 per input segment: [0] row r of counts_dev / keep / ord it reads, [1] box row base, [2] score
+ * element base, [3] transform = fp32 bit pattern of the scale (bits 0-31) | FC_MERGE_XF_FLIP_H | FC_MERGE_XF_FLIP_V.  Element p
+ * of segment g (p < counts_dev[r]) is table row t = ord[r*ord_stride + keep[r*keep_stride + p]] (keep / ord nullable: identity),
+ * its score scores[desc[2] + t*score_stride], its box boxes[(desc[1] + t)*7 .. +7], mapped back as bbox3d_mapping_back
+ * (core/bbox/transforms.py:4-23): flip horizontal, flip vertical, then the first six columns times the scale.  The result is
+ * exactly `cat` in input-segment order + sort(descending=True, stable=True) + the first min(cap, stride_out) rows (cap < 0: no
+ * cap): out_boxes (nseg_out, stride_out, 7), out_scores (nseg_out, stride_out), out_src (nseg_out, stride_out, 2) = (k, p)
+ * (nullable), out_count (nseg_out) int32.  max_total: a host bound of the elements of any output segment (sizes the grid and
+ * the workspace; elements beyond it are dropped).  No atomics: deterministic.  K <= 4096. */
+int64_t fc_merge_sorted_segments_ws_bytes(int nseg_out, int max_total);
+int fc_merge_sorted_segments(const int64_t* desc, int nseg_out, int K, const int* counts_dev, const int* keep, int keep_stride,
+                             const int64_t* ord, int ord_stride, const float* scores, int score_stride, const float* boxes,
+                             int flags, int max_total, int cap, float* out_boxes, float* out_scores, int* out_src,
+                             int* out_count, int stride_out, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 /* ---- optimizer (the reference's recipe, configs/fcaf3d/fcaf3d.py:30-31) --------------------------------- */
 
