@@ -41,7 +41,7 @@ def parse_header(path=HEADER):
     return protos
 
 
-ABI_VERSION = 8          # include/fcaf3d_hip.h FC_ABI_VERSION
+ABI_VERSION = 9          # include/fcaf3d_hip.h FC_ABI_VERSION
 _lib = None
 _protos = None
 

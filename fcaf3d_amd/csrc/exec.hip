@@ -23,8 +23,10 @@ namespace {
 enum : int64_t {
   OP_STEM_FWD = 1, OP_COL_STATS, OP_NORM_FWD, OP_MAXPOOL_FWD, OP_CONV, OP_BN_FWD, OP_UNION_FWD, OP_HEAD_FWD, OP_RECORD, OP_WAIT,
   OP_HEAD_BWD, OP_WGRAD, OP_BN_BWD, OP_NORM_BWD, OP_MAXPOOL_BWD, OP_STEM_WGRAD, OP_GATHER, OP_ADD, OP_SMALL_GRADS,
-  OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR
+  OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD, OP_INV_ROWS
 };
+// (r7: OP_NORM_FWD, OP_MAXPOOL_FWD, OP_UNION_FWD, OP_NORM_BWD, OP_MAXPOOL_BWD are no longer emitted and have no case below — the stem's tail runs as
+// OP_NORM_POOL_FWD / OP_POOL_NORM_BWD, the unions inside OP_BN_FWD; the numbers stay so that the others keep theirs)
 constexpr int OPW = 24;            // int64 words per operator
 constexpr int MAPW = 20;           // int64 words per kernel-map descriptor
 constexpr int NSTREAM = 3;
@@ -214,7 +216,7 @@ int run_op_impl(Ctx& c, const int64_t* op) {
     static const int ko = getenv("FC_KO_OPS") ? atoi(getenv("FC_KO_OPS")) : 0;
     const int64_t o = op[0];
     if (!c.dry && (((ko & 1) && (o == OP_WGRAD || o == OP_STEM_WGRAD)) || ((ko & 2) && o == OP_CONV) ||
-                   ((ko & 4) && (o == OP_BN_FWD || o == OP_BN_BWD || o == OP_NORM_FWD || o == OP_NORM_BWD || o == OP_COL_STATS))))
+                   ((ko & 4) && (o == OP_BN_FWD || o == OP_BN_BWD || o == OP_COL_STATS || o == OP_NORM_POOL_FWD || o == OP_POOL_NORM_BWD))))
       return 0;
   }
 #endif
@@ -231,19 +233,6 @@ int run_op_impl(Ctx& c, const int64_t* op) {
       if (!want_ws(c, s, fc_col_stats_ws_bytes(n, C, nseg))) return 0;
       return fc_col_stats(P<const float>(c, op[2]), P<const int>(c, op[3]), op[3] >= 0 ? 4 : 0, n, C, nseg, P<float>(c, op[7]),
                           P<float>(c, op[8]), P<float>(c, op[9]), c.ws[s], c.ws_bytes[s], st);
-    }
-    case OP_NORM_FWD: {   // x, seg, n(dim), C, mean, var, eps, gamma, beta, res, act, y
-      if (c.dry) return 0;
-      return fc_norm_act_fwd(P<const float>(c, op[2]), P<const int>(c, op[3]), op[3] >= 0 ? 4 : 0, c.dims[op[4]], (int)op[5],
-                             P<const float>(c, op[6]), P<const float>(c, op[7]), (float)as_double(op[8]), P<const float>(c, op[9]),
-                             P<const float>(c, op[10]), P<const float>(c, op[11]), (int)op[12], P<float>(c, op[13]), st);
-    }
-    case OP_MAXPOOL_FWD: {  // in, map, C, out, arg, amax word of out + 1 | 0
-      const int64_t* m = c.maps + op[3] * MAPW;
-      if (c.dry) return 0;
-      if (op[7] > 0) fc_amax_out_hint(P<unsigned>(c, op[7] - 1));
-      return fc_maxpool_fwd(P<const float>(c, op[2]), reinterpret_cast<const int*>(m[3]), m[1], (int)m[2], (int)op[4], P<float>(c, op[5]),
-                            P<int>(c, op[6]), st);
     }
     case OP_CONV: {  // in, img, map (-1: dense GEMM over n rows), dir, out, n(dim, dense only), Cin, Cout, statistics table + 1 | 0,
                      // [BatchNorm-backward form of the table:] bn_x + 1 | 0, mean, var, gamma, beta, eps, act, add + 1 | 0, bn_y + 1 | 0
@@ -292,16 +281,19 @@ int run_op_impl(Ctx& c, const int64_t* op) {
                                         bga, bbe, beps, bact, badd, bny, st);
       return fc_conv_fwd_stats(in, img, tab, oidx, out, n_in, n_out, K, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], stats, st);
     }
-    case OP_BN_FWD: {  // x, n(dim), C, eps, gamma, beta, res, act, momentum, y, mean, var, cnt, rmean, rvar, nbt, train
+    case OP_BN_FWD: {  // x, n(dim), C, eps, gamma, beta, res, act, momentum, y, mean, var, cnt, rmean, rvar, nbt, train, [19-21 below],
+                       // word 22: inverse row map + 1 | 0, word 23: tensor + 1 whose rows are added behind the activation (the neck's sparse sum)
       const int64_t n = c.dims[op[3]];
       const int C = (int)op[4];
       const float eps = (float)as_double(op[5]), mom = (float)as_double(op[10]);
+      const int* add_inv = op[22] > 0 ? P<const int>(c, op[22] - 1) : nullptr;
+      const float* add_src = op[22] > 0 ? P<const float>(c, op[23] - 1) : nullptr;
       if (!op[18]) {      // eval mode: the running statistics are the statistics
         if (c.dry) return 0;
         if (op[21] > 0) fc_amax_out_hint(P<unsigned>(c, op[21] - 1));
-        return fc_norm_act_fwd(P<const float>(c, op[2]), nullptr, 0, n, C, P<const float>(c, op[15]), P<const float>(c, op[16]), eps,
-                               P<const float>(c, op[6]), P<const float>(c, op[7]), P<const float>(c, op[8]), (int)op[9], P<float>(c, op[11]),
-                               st);
+        return fc_norm_act_add_fwd(P<const float>(c, op[2]), nullptr, 0, n, C, P<const float>(c, op[15]), P<const float>(c, op[16]), eps,
+                                   P<const float>(c, op[6]), P<const float>(c, op[7]), P<const float>(c, op[8]), (int)op[9], add_inv, add_src,
+                                   P<float>(c, op[11]), st);
       }
       // training: statistics from the producer's epilogue when the operator names one (word 19 = producer index + 1, word 20 =
       // column groups per channel) and that launch has a statistics epilogue; else computed from x (fc_bn_train_fwd)
@@ -314,19 +306,10 @@ int run_op_impl(Ctx& c, const int64_t* op) {
       }
       if (!want_ws(c, s, fc_bn_train_ws_bytes(n, C))) return 0;
       if (op[21] > 0) fc_amax_out_hint(P<unsigned>(c, op[21] - 1));         // word 21: amax word of y + 1 | 0 (h3: y feeds a convolution)
-      return fc_bn_train_fwd(P<const float>(c, op[2]), n, C, eps, P<const float>(c, op[6]), P<const float>(c, op[7]),
-                             P<const float>(c, op[8]), (int)op[9], mom, P<float>(c, op[11]), P<float>(c, op[12]), P<float>(c, op[13]),
-                             P<float>(c, op[14]), P<float>(c, op[15]), P<float>(c, op[16]), P<long long>(c, op[17]), part, nbp,
-                             op[20] > 0 ? (int)op[20] : 1, c.bn_small_elems, c.ws[s], c.ws_bytes[s], st);
-    }
-    case OP_UNION_FWD: {  // fa, fb, rows, n_a(dim), n_b(dim), n_union(dim), C, out:  out[:n_a] = fa, rest 0, out[rows[i]] += fb[i]
-      if (c.dry) return 0;
-      const int64_t n_a = c.dims[op[5]], n_b = c.dims[op[6]], n_u = c.dims[op[7]];
-      const int C = (int)op[8];
-      float* out = P<float>(c, op[9]);
-      FC_HIP(hipMemcpyAsync(out, P<const float>(c, op[2]), sizeof(float) * n_a * C, hipMemcpyDeviceToDevice, st));
-      if (n_u > n_a) FC_HIP(hipMemsetAsync(out + n_a * C, 0, sizeof(float) * (n_u - n_a) * C, st));
-      return fc_scatter_rows_add(P<const float>(c, op[3]), P<const int>(c, op[4]), n_b, C, out, st);
+      return fc_bn_train_add_fwd(P<const float>(c, op[2]), n, C, eps, P<const float>(c, op[6]), P<const float>(c, op[7]),
+                                 P<const float>(c, op[8]), (int)op[9], mom, P<float>(c, op[11]), P<float>(c, op[12]), P<float>(c, op[13]),
+                                 P<float>(c, op[14]), P<float>(c, op[15]), P<float>(c, op[16]), P<long long>(c, op[17]), part, nbp,
+                                 op[20] > 0 ? (int)op[20] : 1, c.bn_small_elems, add_inv, add_src, c.ws[s], c.ws_bytes[s], st);
     }
     case OP_HEAD_FWD: {  // y, ld, bias, scale, n(dim), n_reg, n_cls, cent, bbox, cls, cmax
       if (c.dry) return 0;
@@ -398,22 +381,6 @@ int run_op_impl(Ctx& c, const int64_t* op) {
                              P<float>(c, op[14]), P<float>(c, op[15]), P<float>(c, op[16]), part, nbp, c.bn_small_elems, c.ws[s],
                              c.ws_bytes[s], st);
     }
-    case OP_NORM_BWD: {  // x, y, gy, seg, n(dim), C, nseg(dim), mean, var, cnt, eps, gamma, beta, act, gx, gres, sums
-      const int64_t n = c.dims[op[6]];
-      const int C = (int)op[7], nseg = (int)c.dims[op[8]];
-      if (!want_ws(c, s, fc_norm_act_bwd_ws_bytes(n, C, nseg))) return 0;
-      return fc_norm_act_bwd(P<const float>(c, op[2]), P<const float>(c, op[3]), P<const float>(c, op[4]), P<const int>(c, op[5]),
-                             op[5] >= 0 ? 4 : 0, n, C, nseg, P<const float>(c, op[9]), P<const float>(c, op[10]), P<const float>(c, op[11]),
-                             (float)as_double(op[12]), P<const float>(c, op[13]), P<const float>(c, op[14]), (int)op[15], P<float>(c, op[16]),
-                             P<float>(c, op[17]), P<float>(c, op[18]), c.ws[s], c.ws_bytes[s], st);
-    }
-    case OP_MAXPOOL_BWD: {  // gout, arg, map, C, gin
-      const int64_t* m = c.maps + op[4] * MAPW;
-      if (c.dry) return 0;
-      const int C = (int)op[5];
-      FC_HIP(hipMemsetAsync(P<float>(c, op[6]), 0, sizeof(float) * m[0] * C, st));
-      return fc_maxpool_bwd(P<const float>(c, op[2]), P<const int>(c, op[3]), m[1], C, P<float>(c, op[6]), st);
-    }
     case OP_STEM_WGRAD: {  // col, gout, map, gW
       const int64_t* m = c.maps + op[4] * MAPW;
       if (!want_ws(c, s, fc_stem_conv_wgrad_ws_bytes(m[1], (int)m[2]))) return 0;
@@ -473,6 +440,30 @@ int run_op_impl(Ctx& c, const int64_t* op) {
       if (c.dry) return 0;
       FC_HIP(hipMemsetAsync(P<void>(c, op[2]), 0, (size_t)op[3], st));
       return 0;
+    }
+    case OP_NORM_POOL_FWD: {  // x, seg, C, mean, var, eps, gamma, beta, act, map, out, arg, y | -1, amax word of out + 1 | 0, parent | -1
+      const int64_t* m = c.maps + op[11] * MAPW;
+      if (c.dry) return 0;
+      if ((int)m[2] != 8) return FC_EINVAL;
+      if (op[15] > 0) fc_amax_out_hint(P<unsigned>(c, op[15] - 1));
+      return fc_norm_act_maxpool8_fwd(P<const float>(c, op[2]), P<const int>(c, op[3]), op[3] >= 0 ? 4 : 0, (int)op[4], P<const float>(c, op[5]),
+                                      P<const float>(c, op[6]), (float)as_double(op[7]), P<const float>(c, op[8]), P<const float>(c, op[9]),
+                                      (int)op[10], reinterpret_cast<const int*>(m[3]), m[1], P<float>(c, op[12]), P<int>(c, op[13]),
+                                      P<float>(c, op[14]), P<int>(c, op[16]), st);
+    }
+    case OP_POOL_NORM_BWD: {  // x, g_pool, arg, parent, seg, n(dim), C, nseg(dim), mean, var, cnt, eps, gamma, beta, act, gx, sums
+      const int64_t n = c.dims[op[7]];
+      const int C = (int)op[8], nseg = (int)c.dims[op[9]];
+      if (!want_ws(c, s, fc_maxpool8_norm_act_bwd_ws_bytes(n, C, nseg))) return 0;
+      return fc_maxpool8_norm_act_bwd(P<const float>(c, op[2]), P<const float>(c, op[3]), P<const int>(c, op[4]), P<const int>(c, op[5]),
+                                      P<const int>(c, op[6]), op[6] >= 0 ? 4 : 0, n, C, nseg, P<const float>(c, op[10]),
+                                      P<const float>(c, op[11]), P<const float>(c, op[12]), (float)as_double(op[13]),
+                                      P<const float>(c, op[14]), P<const float>(c, op[15]), (int)op[16], P<float>(c, op[17]),
+                                      P<float>(c, op[18]), c.ws[s], c.ws_bytes[s], st);
+    }
+    case OP_INV_ROWS: {  // rows, n(dim), n_inv(dim), inv: inv = -1, inv[rows[i]] = i
+      if (c.dry) return 0;
+      return fc_inverse_rows(P<const int>(c, op[2]), c.dims[op[3]], c.dims[op[4]], P<int>(c, op[5]), st);
     }
     case OP_COPY: {  // dst, src, n(dim), C
       if (c.dry) return 0;

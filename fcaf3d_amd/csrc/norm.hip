@@ -249,10 +249,13 @@ __device__ static inline float act_bwd_from_pre(float p, int act) {
 thread_local unsigned* t_fc_amax_out = nullptr;          // fc_amax_out_hint: consumed by the next producer entry point of this thread (fc_common.h)
 
 // y = act( (x-mean[seg])*invstd[seg]*gamma + beta (+ residual) ) ; invstd = 1/sqrt(var+eps)
+// add_inv (nullable, r7): y[r] += add_src[add_inv[r]] where add_inv[r] >= 0, behind the activation — the neck's sparse sum
+// `inputs[i] + x` written by the up block's last normalisation instead of a copy + scatter-add + amax pass over the union
 __global__ void k_norm_act_fwd(const float* __restrict__ x, const int* __restrict__ seg, int seg_stride, int64_t n, int C,
                                const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                               const float* __restrict__ residual, int act, float* __restrict__ y, unsigned* __restrict__ amax_out) {
+                               const float* __restrict__ residual, int act, const int* __restrict__ add_inv,
+                               const float* __restrict__ add_src, float* __restrict__ y, unsigned* __restrict__ amax_out) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4n = C / 4;
   unsigned am = 0u;
@@ -260,6 +263,7 @@ __global__ void k_norm_act_fwd(const float* __restrict__ x, const int* __restric
   int64_t r = t / c4n;
   int c = (int)(t % c4n) * 4;
   int s = seg_of(seg, seg_stride, r);
+  const int q = add_inv ? add_inv[r] : -1;
   float4 v = *reinterpret_cast<const float4*>(x + r * C + c);
   float4 mu = *reinterpret_cast<const float4*>(mean + (int64_t)s * C + c);
   float4 va = *reinterpret_cast<const float4*>(var + (int64_t)s * C + c);
@@ -275,6 +279,10 @@ __global__ void k_norm_act_fwd(const float* __restrict__ x, const int* __restric
     o.x += rs.x; o.y += rs.y; o.z += rs.z; o.w += rs.w;
   }
   o.x = act_fwd(o.x, act); o.y = act_fwd(o.y, act); o.z = act_fwd(o.z, act); o.w = act_fwd(o.w, act);
+  if (q >= 0) {                                  // the sparse sum behind the activation: + add_src[add_inv[r]] (one fp32 add, as fc_scatter_rows_add)
+    const float4 f = *reinterpret_cast<const float4*>(add_src + (int64_t)q * C + c);
+    o.x += f.x; o.y += f.y; o.z += f.z; o.w += f.w;
+  }
   *reinterpret_cast<float4*>(y + r * C + c) = o;
   amax_fold(am, o.x); amax_fold(am, o.y); amax_fold(am, o.z); amax_fold(am, o.w);
   }
@@ -287,8 +295,14 @@ __global__ void k_norm_act_fwd(const float* __restrict__ x, const int* __restric
 // gy2 (nullable, r5): a second contribution to the incoming gradient — g = gy + gy2 is formed on the fly here and, with the same
 // operands in the same order, in the apply kernels: the executor no longer materialises the sum where a normalised tensor has
 // two consumers (k_add_inplace: 22 launches per step in r4)
+// pool_parent / pool_arg (nullable, r7): the layer's output went through a k2s2 max pool and gy is the gradient of the POOLED tensor —
+// row r's incoming gradient is gy[pool_parent[r]][c] where pool_arg[pool_parent[r]][c] == r, else 0: what fc_maxpool_bwd scatters into a
+// zeroed matrix, formed on the fly.  Only the loads differ: the sums run over the same rows in the same order, hence the same bits.
+// (A template parameter, not a run-time test: the plain instantiation is the kernel every other layer runs and keeps its code.)
+template <bool POOL>
 __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gy,
-                                   const float* __restrict__ gy2, const int* __restrict__ seg, int seg_stride, int64_t n, int C, int nseg,
+                                   const float* __restrict__ gy2, const int* __restrict__ pool_parent,
+                                   const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C, int nseg,
                                    const float* __restrict__ mean, const float* __restrict__ var, float eps, int act,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    int64_t rpb, float* __restrict__ part) {
@@ -329,7 +343,15 @@ __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __r
           const int64_t rc = ok[u] ? r : r0;
           if (chk) ok[u] = ok[u] && seg[rc * seg_stride] == s;
           xv[u] = *reinterpret_cast<const float4*>(x + rc * C + cl * 4);
-          gv[u] = *reinterpret_cast<const float4*>(gy + rc * C + cl * 4);
+          if (POOL) {
+            const int64_t o = pool_parent[rc];
+            const int4 a = *reinterpret_cast<const int4*>(pool_arg + o * C + cl * 4);
+            gv[u] = *reinterpret_cast<const float4*>(gy + o * C + cl * 4);
+            gv[u].x = a.x == rc ? gv[u].x : 0.f; gv[u].y = a.y == rc ? gv[u].y : 0.f;
+            gv[u].z = a.z == rc ? gv[u].z : 0.f; gv[u].w = a.w == rc ? gv[u].w : 0.f;
+          } else {
+            gv[u] = *reinterpret_cast<const float4*>(gy + rc * C + cl * 4);
+          }
           if (gy2) g2[u] = *reinterpret_cast<const float4*>(gy2 + rc * C + cl * 4);
           if (from_y) yv[u] = *reinterpret_cast<const float4*>(y + rc * C + cl * 4);
         }
@@ -377,8 +399,11 @@ __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __r
 }
 
 // backward pass 3:  gx = gamma*invstd*( g' - sum_g/cnt - xhat * sum_gx/cnt ) ; gres = g'
+// pool_parent / pool_arg: see k_norm_bwd_partial
+template <bool POOL>
 __global__ void k_norm_bwd_apply(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gy,
-                                 const float* __restrict__ gy2, const int* __restrict__ seg, int seg_stride, int64_t n, int C,
+                                 const float* __restrict__ gy2, const int* __restrict__ pool_parent,
+                                 const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C,
                                  const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                  const float* __restrict__ sums /*[seg][2][C]*/,
@@ -394,7 +419,14 @@ __global__ void k_norm_bwd_apply(const float* __restrict__ x, const float* __res
   float inv_n = 1.f / cnt[s];
   float xv[4], gv[4], muv[4], vav[4], gam[4], bet[4] = {0.f, 0.f, 0.f, 0.f}, s1[4], s2[4], yv[4], o[4], gr[4];
   *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(x + r * C + c);
-  *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(gy + r * C + c);
+  if (POOL) {
+    const int64_t o = pool_parent[r];
+    const int4 a = *reinterpret_cast<const int4*>(pool_arg + o * C + c);
+    *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(gy + o * C + c);
+    gv[0] = a.x == r ? gv[0] : 0.f; gv[1] = a.y == r ? gv[1] : 0.f; gv[2] = a.z == r ? gv[2] : 0.f; gv[3] = a.w == r ? gv[3] : 0.f;
+  } else {
+    *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(gy + r * C + c);
+  }
   if (gy2) {
     const float4 t2 = *reinterpret_cast<const float4*>(gy2 + r * C + c);
     gv[0] += t2.x; gv[1] += t2.y; gv[2] += t2.z; gv[3] += t2.w;
@@ -489,6 +521,79 @@ __global__ void k_maxpool_bwd(const float* __restrict__ gout, const int* __restr
   int i = argrow[t];
   // k2s2 children are disjoint between output cells -> each (row, channel) receives at most one write
   if (i >= 0) gin[(int64_t)i * C + (t % C)] = gout[t];
+}
+
+// ---- r7: the stem's tail without its two n1-row intermediates ------------------------------------------------------------------
+// Forward: instance norm + activation + k2s2 max pool in one pass.  One thread per (pooled row, 4 channels), as k_maxpool8_fwd; the
+// 8 children's x values go through the SAME bn_pre / act_fwd sequence as k_norm_act_fwd before they are compared, so out / argrow
+// (and y, when asked for) are bit for bit those of fc_norm_act_fwd + fc_maxpool_fwd.  The children of a pooled row lie in one
+// scene (seg of the first present child).  y (nullable): the normalised tensor itself — every child has one parent, so every
+// row is written once.  parent (nullable): parent[child row] = pooled row, for the backward pass (k_norm_bwd_* pool_parent).
+__global__ void k_norm_act_maxpool8_fwd(const float* __restrict__ x, const int* __restrict__ seg, int seg_stride, int C,
+                                        const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                        const float* __restrict__ gamma, const float* __restrict__ beta, int act,
+                                        const int* __restrict__ nbr, int64_t n_out, float* __restrict__ out, int* __restrict__ argrow,
+                                        float* __restrict__ y, int* __restrict__ parent, unsigned* __restrict__ amax_out) {
+  const int c4n = C / 4;
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned am = 0u;
+  if (t < n_out * c4n) {
+  const int64_t o = t / c4n;
+  const int c = (int)(t % c4n) * 4;
+  int idx[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) idx[k] = nbr[(int64_t)k * n_out + o];
+  if (parent) {                                  // one store per lane: the lane of channel group k writes child k's entry
+    int mine = -1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mine = (c == 4 * k) ? idx[k] : mine;
+    if (mine >= 0) parent[mine] = (int)o;
+  }
+  float4 v[8];
+  int first = -1;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int i = idx[k] < 0 ? 0 : idx[k];
+    if (first < 0 && idx[k] >= 0) first = idx[k];
+    v[k] = *reinterpret_cast<const float4*>(x + (int64_t)i * C + c);
+  }
+  float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  int arg[4] = {-1, -1, -1, -1};
+  if (first >= 0) {
+    const int s = seg_of(seg, seg_stride, first);
+    float mu[4], va[4], is[4], g[4] = {1.f, 1.f, 1.f, 1.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<float4*>(mu) = *reinterpret_cast<const float4*>(mean + (int64_t)s * C + c);
+    *reinterpret_cast<float4*>(va) = *reinterpret_cast<const float4*>(var + (int64_t)s * C + c);
+    if (gamma) *reinterpret_cast<float4*>(g) = *reinterpret_cast<const float4*>(gamma + c);
+    if (beta) *reinterpret_cast<float4*>(b) = *reinterpret_cast<const float4*>(beta + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) is[j] = 1.f / sqrtf(va[j] + eps);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (idx[k] < 0) continue;
+      float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e[j] = act_fwd(bn_pre(e[j], mu[j], is[j], g[j], b[j]), act);
+        if (arg[j] < 0 || e[j] > best[j]) { best[j] = e[j]; arg[j] = idx[k]; }   // first max in offset order wins ties (A.5)
+      }
+      if (y) *reinterpret_cast<float4*>(y + (int64_t)idx[k] * C + c) = make_float4(e[0], e[1], e[2], e[3]);
+    }
+  }
+  float4 ob = make_float4(arg[0] < 0 ? 0.f : best[0], arg[1] < 0 ? 0.f : best[1], arg[2] < 0 ? 0.f : best[2], arg[3] < 0 ? 0.f : best[3]);
+  *reinterpret_cast<float4*>(out + o * C + c) = ob;
+  *reinterpret_cast<int4*>(argrow + o * C + c) = make_int4(arg[0], arg[1], arg[2], arg[3]);
+  amax_fold(am, ob.x); amax_fold(am, ob.y); amax_fold(am, ob.z); amax_fold(am, ob.w);
+  }
+  if (amax_out) amax_commit(am, amax_out);
+}
+
+// inv[rows[i]] = i (inv pre-filled with -1; rows unique): generated row -> backbone row of a neck level's sparse sum
+__global__ void k_inverse_rows(const int* __restrict__ rows, int64_t n, int64_t n_inv, int* __restrict__ inv) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int r = rows[i];
+  if (r >= 0 && r < n_inv) inv[r] = (int)i;
 }
 
 // ---- row gather / scatter ----------------------------------------------------------------------
@@ -593,7 +698,8 @@ __global__ void k_bn1_apply(const float* __restrict__ x, int64_t n, int C, int64
                             float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
                             const float* __restrict__ residual, int act, float momentum, float* __restrict__ y,
                             float* __restrict__ mean_out, float* __restrict__ var_out, float* __restrict__ cnt_out,
-                            float* __restrict__ rmean, float* __restrict__ rvar, long long* __restrict__ nbt) {
+                            float* __restrict__ rmean, float* __restrict__ rvar, long long* __restrict__ nbt,
+                            const int* __restrict__ add_inv, const float* __restrict__ add_src) {
   extern __shared__ float sm[];
   const int c4n = C / 4;
   const int cl = threadIdx.x % c4n, rl = threadIdx.x / c4n;
@@ -649,6 +755,11 @@ __global__ void k_bn1_apply(const float* __restrict__ x, int64_t n, int C, int64
         o[j] = bn_pre(v[u][j], mu[j], is[j], g[j], bt[j]);
         if (residual) o[j] += rs[u][j];
         o[j] = act_fwd(o[j], act);
+      }
+      const int q = add_inv ? add_inv[r] : -1;
+      if (q >= 0) {
+        const float4 f = *reinterpret_cast<const float4*>(add_src + (int64_t)q * C + cl * 4);
+        o[0] += f.x; o[1] += f.y; o[2] += f.z; o[3] += f.w;
       }
       *reinterpret_cast<float4*>(y + r * C + cl * 4) = *reinterpret_cast<float4*>(o);
     }
@@ -806,11 +917,12 @@ __global__ void k_bn2_apply(const float* __restrict__ x, int64_t n, int C, int64
                             const float* __restrict__ residual, int act, float momentum, float* __restrict__ y,
                             float* __restrict__ mean_out, float* __restrict__ var_out, float* __restrict__ cnt_out,
                             float* __restrict__ rmean, float* __restrict__ rvar, long long* __restrict__ nbt, int CG,
-                            unsigned* __restrict__ amax_out) {
-  // r6: grid.y channel windows of CG channels (see k_bn1_bwd_apply)
+                            const int* __restrict__ add_inv, const float* __restrict__ add_src, unsigned* __restrict__ amax_out) {
+  // r6: grid.y channel windows of CG channels (see k_bn1_bwd_apply); add_inv / add_src: see k_norm_act_fwd
   extern __shared__ double smd[];             // [nrl][2][CG]
   const int c0 = blockIdx.y * CG;
   x += c0; y += c0; part += c0; mean_out += c0; var_out += c0;
+  if (add_src) add_src += c0;
   if (residual) residual += c0;
   if (gamma) gamma += c0;
   if (beta) beta += c0;
@@ -862,12 +974,14 @@ __global__ void k_bn2_apply(const float* __restrict__ x, int64_t n, int C, int64
   unsigned am = 0u;
   for (int64_t rb = r0 + rl; rb < r1; rb += 4 * (int64_t)nrl) {      // four rows in flight per thread
     float v[4][4], rs[4][4];
+    int q[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t r = rb + (int64_t)u * nrl;
       const int64_t rc = r < r1 ? r : r0;
       *reinterpret_cast<float4*>(v[u]) = *reinterpret_cast<const float4*>(x + rc * C + cl * 4);
       if (residual) *reinterpret_cast<float4*>(rs[u]) = *reinterpret_cast<const float4*>(residual + rc * C + cl * 4);
+      q[u] = add_inv ? add_inv[rc] : -1;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -879,6 +993,10 @@ __global__ void k_bn2_apply(const float* __restrict__ x, int64_t n, int C, int64
         o[j] = bn_pre(v[u][j], mu[j], is[j], g[j], bt[j]);
         if (residual) o[j] += rs[u][j];
         o[j] = act_fwd(o[j], act);
+      }
+      if (q[u] >= 0) {
+        const float4 f = *reinterpret_cast<const float4*>(add_src + (int64_t)q[u] * C + cl * 4);
+        o[0] += f.x; o[1] += f.y; o[2] += f.z; o[3] += f.w;
       }
       *reinterpret_cast<float4*>(y + r * C + cl * 4) = *reinterpret_cast<float4*>(o);
 #pragma unroll
@@ -1077,10 +1195,10 @@ int fc_bn_stats_train(const float* x, int64_t n, int C, float momentum, float* m
 
 // training-mode BatchNorm forward for one segment: statistics + running-buffer update + normalise/affine/residual/act.
 // mean/var (C) and cnt (1) are written for the backward pass; running_* / num_batches_tracked may be NULL.
-int fc_bn_act_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta,
-                        const float* residual, int act, float momentum, float* y, float* mean, float* var, float* cnt,
-                        float* running_mean, float* running_var, long long* num_batches_tracked, void* ws,
-                        int64_t ws_bytes, hipStream_t stream) {
+static int bn_act_train_fwd_add(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta,
+                                const float* residual, int act, float momentum, float* y, float* mean, float* var, float* cnt,
+                                float* running_mean, float* running_var, long long* num_batches_tracked, const int* add_inv,
+                                const float* add_src, void* ws, int64_t ws_bytes, hipStream_t stream) {
   if (n < 1 || act < 0 || act > 2) return FC_EINVAL;
   int threads; size_t sf, sb;
   if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
@@ -1091,9 +1209,17 @@ int fc_bn_act_train_fwd(const float* x, int64_t n, int C, float eps, const float
   k_bn1_partial<<<(unsigned)nb, threads, sb, stream>>>(x, n, C, rpb, part);
   FC_CHECK_LAUNCH();
   k_bn1_apply<<<(unsigned)nb, threads, sb, stream>>>(x, n, C, rpb, part, (int)nb, eps, gamma, beta, residual, act, momentum, y,
-                                                    mean, var, cnt, running_mean, running_var, num_batches_tracked);
+                                                    mean, var, cnt, running_mean, running_var, num_batches_tracked, add_inv, add_src);
   FC_CHECK_LAUNCH();
   return FC_OK;
+}
+
+int fc_bn_act_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta,
+                        const float* residual, int act, float momentum, float* y, float* mean, float* var, float* cnt,
+                        float* running_mean, float* running_var, long long* num_batches_tracked, void* ws,
+                        int64_t ws_bytes, hipStream_t stream) {
+  return bn_act_train_fwd_add(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
+                              num_batches_tracked, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 // its backward: sums (2,C) = [d beta, d gamma]
@@ -1107,7 +1233,7 @@ int fc_bn_act_train_bwd(const float* x, const float* y, const float* gy, int64_t
   int64_t nb, rpb;
   bn1_plan(n, &nb, &rpb);
   float* part = (float*)ws;
-  k_norm_bwd_partial<<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb, part);
+  k_norm_bwd_partial<false><<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb, part);
   FC_CHECK_LAUNCH();
   unsigned* ao = take_amax_out();
   k_bn1_bwd_apply<<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, n, C, rpb, part, (int)nb, mean, var, eps, gamma, beta, act, gx,
@@ -1116,16 +1242,23 @@ int fc_bn_act_train_bwd(const float* x, const float* y, const float* gy, int64_t
   return FC_OK;
 }
 
+// add_inv / add_src (both or neither): y[r] += add_src[add_inv[r]] where add_inv[r] >= 0, behind the activation
+int fc_norm_act_add_fwd(const float* x, const int* seg, int seg_stride, int64_t n, int C, const float* mean, const float* var,
+                        float eps, const float* gamma, const float* beta, const float* residual, int act, const int* add_inv,
+                        const float* add_src, float* y, hipStream_t stream) {
+  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
+  if (n < 0 || C < 4 || C % 4 || act < 0 || act > 2 || (add_inv == nullptr) != (add_src == nullptr)) return FC_EINVAL;
+  if (n == 0) return FC_OK;
+  k_norm_act_fwd<<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, seg, seg_stride, n, C, mean, var, eps, gamma,
+                                                                         beta, residual, act, add_inv, add_src, y, ao);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
 int fc_norm_act_fwd(const float* x, const int* seg, int seg_stride, int64_t n, int C, const float* mean, const float* var,
                     float eps, const float* gamma, const float* beta, const float* residual, int act, float* y,
                     hipStream_t stream) {
-  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
-  if (n < 0 || C < 4 || C % 4 || act < 0 || act > 2) return FC_EINVAL;
-  if (n == 0) return FC_OK;
-  k_norm_act_fwd<<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, seg, seg_stride, n, C, mean, var, eps, gamma,
-                                                                         beta, residual, act, y, ao);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
+  return fc_norm_act_add_fwd(x, seg, seg_stride, n, C, mean, var, eps, gamma, beta, residual, act, nullptr, nullptr, y, stream);
 }
 
 int64_t fc_norm_act_bwd_ws_bytes(int64_t n, int C, int nseg) {
@@ -1151,13 +1284,13 @@ int fc_norm_act_bwd(const float* x, const float* y, const float* gy, const int* 
   int64_t nb, rpb;
   red_plan(n, &nb, &rpb);
   float* part = (float*)ws;
-  k_norm_bwd_partial<<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, seg, seg_stride, n, C, nseg, mean, var, eps, act, gamma,
-                                                          beta, rpb, part);
+  k_norm_bwd_partial<false><<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, nseg, mean, var, eps, act,
+                                                          gamma, beta, rpb, part);
   FC_CHECK_LAUNCH();
   k_stats_final<<<(unsigned)(nseg * ((2 * C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, nb, nseg, 2 * C, 2, sums, nullptr);
   FC_CHECK_LAUNCH();
-  k_norm_bwd_apply<<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, nullptr, seg, seg_stride, n, C, mean, var, eps,
-                                                                           gamma, beta, sums, cnt, act, gx, gres, ao);
+  k_norm_bwd_apply<false><<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, mean,
+                                                                           var, eps, gamma, beta, sums, cnt, act, gx, gres, ao);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
@@ -1182,23 +1315,26 @@ int64_t fc_bn_train_ws_bytes(int64_t n, int C) {
 // Forward.  part == NULL: the statistics are computed here from x (n * C <= small_elems: fc_bn_act_train_fwd, else fc_bn_stats_train +
 // fc_norm_act_fwd — the r1-r4 routes).  part != NULL: nb_part row blocks of producer-written column sums [nb_part][2][groups * C]
 // (see k_bn2_apply); x is then (groups * n_rows_of_the_producer, C) = n rows.
-int fc_bn_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
-                    int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
-                    float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
-                    int64_t small_elems, void* ws, int64_t ws_bytes, hipStream_t stream) {
+// add_inv / add_src (both or neither, r7): the sparse sum behind the layer, y[r] += add_src[add_inv[r]] where add_inv[r] >= 0,
+// written (and folded into the amax word) by whichever apply kernel the size routes to
+int fc_bn_train_add_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
+                        int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
+                        float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
+                        int64_t small_elems, const int* add_inv, const float* add_src, void* ws, int64_t ws_bytes,
+                        hipStream_t stream) {
   unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
-  if (n < 1 || act < 0 || act > 2) return FC_EINVAL;
+  if (n < 1 || act < 0 || act > 2 || (add_inv == nullptr) != (add_src == nullptr)) return FC_EINVAL;
   if (!part) {
     if (n * C <= small_elems) {
-      int rc = fc_bn_act_train_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
-                                   num_batches_tracked, ws, ws_bytes, stream);
+      int rc = bn_act_train_fwd_add(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
+                                    num_batches_tracked, add_inv, add_src, ws, ws_bytes, stream);
       if (rc == FC_OK && ao) rc = fc_amax(y, n * (int64_t)C, ao, stream);          // (this route's apply kernel does not fold: a pass of its own)
       return rc;
     }
     int rc = fc_bn_stats_train(x, n, C, momentum, mean, var, cnt, running_mean, running_var, num_batches_tracked, ws, ws_bytes, stream);
     if (rc) return rc;
     t_fc_amax_out = ao;
-    return fc_norm_act_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, y, stream);
+    return fc_norm_act_add_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, stream);
   }
   int threads; size_t sf, sb;
   if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
@@ -1210,7 +1346,8 @@ int fc_bn_train_fwd(const float* x, int64_t n, int C, float eps, const float* ga
     if (CG != C && stats_geometry(CG, &threads, &sf, &sb)) return FC_EINVAL;
     const size_t smem = (size_t)(threads / (CG / 4)) * 2 * CG * sizeof(double);
     k_bn2_apply<<<dim3((unsigned)nb, C / CG), threads, smem, stream>>>(x, n, C, rpb, part, (int)nb_part, groups, eps, gamma, beta, residual, act,
-                                                        momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, CG, ao);
+                                                        momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, CG,
+                                                        add_inv, add_src, ao);
     FC_CHECK_LAUNCH();
     return FC_OK;
   }
@@ -1218,7 +1355,15 @@ int fc_bn_train_fwd(const float* x, int64_t n, int C, float eps, const float* ga
                                                                  running_mean, running_var, num_batches_tracked);
   FC_CHECK_LAUNCH();
   t_fc_amax_out = ao;
-  return fc_norm_act_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, y, stream);
+  return fc_norm_act_add_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, stream);
+}
+
+int fc_bn_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
+                    int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
+                    float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
+                    int64_t small_elems, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  return fc_bn_train_add_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
+                             num_batches_tracked, part, nb_part, groups, small_elems, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 // Backward.  gy2 (nullable): a second contribution to the incoming gradient, added on the fly.  part == NULL: the sums of g' and
@@ -1239,7 +1384,7 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
     if (ws_bytes < (small ? fc_bn_small_ws_bytes(C) : fc_norm_act_bwd_ws_bytes(n, C, 1))) return FC_EWS;
     int64_t rpb;
     if (small) bn1_plan(n, &np, &rpb); else red_plan(n, &np, &rpb);
-    k_norm_bwd_partial<<<(unsigned)np, threads, sb, stream>>>(x, y, gy, gy2, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb,
+    k_norm_bwd_partial<false><<<(unsigned)np, threads, sb, stream>>>(x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb,
                                                             (float*)ws);
     FC_CHECK_LAUNCH();
     p = (const float*)ws;
@@ -1257,8 +1402,8 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
   }
   k_stats_final<<<(unsigned)((2 * C + FIN_CB - 1) / FIN_CB), FIN_CB * FIN_SL, 0, stream>>>(p, nullptr, np, 1, 2 * C, 2, sums, nullptr);
   FC_CHECK_LAUNCH();
-  k_norm_bwd_apply<<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, gy2, nullptr, 0, n, C, mean, var, eps, gamma, beta,
-                                                                           sums, cnt, act, gx, gres, ao);
+  k_norm_bwd_apply<false><<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, mean, var, eps, gamma,
+                                                                           beta, sums, cnt, act, gx, gres, ao);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
@@ -1301,6 +1446,58 @@ int fc_scatter_rows_add(const float* src, const int* idx, int64_t n, int C, floa
   if (n < 0 || C < 1) return FC_EINVAL;
   if (n == 0) return FC_OK;
   k_scatter_rows_add<<<(unsigned)fc_cdiv(n * C, 256), 256, 0, stream>>>(src, idx, n, C, dst);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+// ---- r7: the stem's tail fused (kernels above) ------------------------------------------------------------------------------------
+int fc_norm_act_maxpool8_fwd(const float* x, const int* seg, int seg_stride, int C, const float* mean, const float* var, float eps,
+                             const float* gamma, const float* beta, int act, const int* nbr, int64_t n_out, float* out,
+                             int* argrow, float* y, int* parent, hipStream_t stream) {
+  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |out| into the caller's (zeroed) word
+  if (n_out < 0 || C < 4 || C % 4 || act < 0 || act > 2) return FC_EINVAL;
+  if (n_out == 0) return FC_OK;
+  k_norm_act_maxpool8_fwd<<<(unsigned)fc_cdiv(n_out * (C / 4), 256), 256, 0, stream>>>(x, seg, seg_stride, C, mean, var, eps, gamma, beta,
+                                                                                      act, nbr, n_out, out, argrow, y, parent, ao);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+int64_t fc_maxpool8_norm_act_bwd_ws_bytes(int64_t n_in, int C, int nseg) { return fc_norm_act_bwd_ws_bytes(n_in, C, nseg); }
+
+// fc_norm_act_bwd (y == NULL, no residual) whose incoming gradient is read through the pool: the launches, the geometry and the order of
+// every sum are those of fc_norm_act_bwd over the n_in rows — gx and sums are bit for bit what zero fill + fc_maxpool_bwd + fc_norm_act_bwd give
+int fc_maxpool8_norm_act_bwd(const float* x, const float* gout, const int* argrow, const int* parent, const int* seg, int seg_stride,
+                             int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps,
+                             const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
+                             hipStream_t stream) {
+  if (n_in < 0 || nseg < 1 || nseg > MAXSEG || act < 0 || act > 2 || !parent || !argrow) return FC_EINVAL;
+  int threads; size_t sf, sb;
+  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
+  if (ws_bytes < fc_maxpool8_norm_act_bwd_ws_bytes(n_in, C, nseg)) return FC_EWS;
+  if (n_in == 0) {
+    FC_HIP(hipMemsetAsync(sums, 0, sizeof(float) * nseg * 2 * C, stream));
+    return FC_OK;
+  }
+  int64_t nb, rpb;
+  red_plan(n_in, &nb, &rpb);
+  float* part = (float*)ws;
+  k_norm_bwd_partial<true><<<(unsigned)nb, threads, sb, stream>>>(x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C, nseg, mean, var,
+                                                          eps, act, gamma, beta, rpb, part);
+  FC_CHECK_LAUNCH();
+  k_stats_final<<<(unsigned)(nseg * ((2 * C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, nb, nseg, 2 * C, 2, sums, nullptr);
+  FC_CHECK_LAUNCH();
+  k_norm_bwd_apply<true><<<(unsigned)fc_cdiv(n_in * (C / 4), 256), 256, 0, stream>>>(x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C,
+                                                                              mean, var, eps, gamma, beta, sums, cnt, act, gx, nullptr, nullptr);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+int fc_inverse_rows(const int* rows, int64_t n, int64_t n_inv, int* inv, hipStream_t stream) {
+  if (n < 0 || n_inv < 0) return FC_EINVAL;
+  if (n_inv > 0) FC_HIP(hipMemsetAsync(inv, 0xff, sizeof(int) * n_inv, stream));
+  if (n == 0) return FC_OK;
+  k_inverse_rows<<<(unsigned)fc_cdiv(n, 256), 256, 0, stream>>>(rows, n, n_inv, inv);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }

@@ -42,12 +42,15 @@ PROBE = None
 # else who steps the weights (an optimizer of their own, EMA, surgery) gets fresh images at every call, as on the per-operator path.
 TRUSTED = None
 # tests: keep the bound state of the last forward pass on the detector (`det._last_exec = (program, state)`) so that the recorded
-# activations can be inspected (NetProgram.decisions)
+# activations can be inspected (NetProgram.decisions).  A program built while it is set also stores the stem's normalised output,
+# which a plain step never materialises (r7): part of the program cache key
 KEEP_STATE = False
 
 (OP_STEM_FWD, OP_COL_STATS, OP_NORM_FWD, OP_MAXPOOL_FWD, OP_CONV, OP_BN_FWD, OP_UNION_FWD, OP_HEAD_FWD, OP_RECORD, OP_WAIT,
  OP_HEAD_BWD, OP_WGRAD, OP_BN_BWD, OP_NORM_BWD, OP_MAXPOOL_BWD, OP_STEM_WGRAD, OP_GATHER, OP_ADD, OP_SMALL_GRADS,
- OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR) = range(1, 27)
+ OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD,
+ OP_INV_ROWS) = range(1, 30)
+# (OP_NORM_FWD, OP_MAXPOOL_FWD, OP_UNION_FWD, OP_NORM_BWD, OP_MAXPOOL_BWD: not emitted since r7 and without a case in csrc/exec.hip; the numbers stay)
 OPW, MAPW = 24, 20
 ALIGN = 256
 S_MAIN, S_HEAD, S_WGRAD = 0, 1, 2
@@ -74,12 +77,14 @@ _FORWARD_SINGLE = _NECK_FORWARD = None       # set by fcaf3d_neck_with_head at i
 
 
 class NetProgram:
-    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False):
-        """tail0: the finest neck level is PRUNED this step (`pts_threshold` bites there, fcaf3d_neck_with_head.py:110-126): the
+    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None):
+        """keep_state (default: the module's KEEP_STATE now): the stem's normalised output is stored for `decisions`.
+        tail0: the finest neck level is PRUNED this step (`pts_threshold` bites there, fcaf3d_neck_with_head.py:110-126): the
         program ends at that level's union — `x0`, exported as a fourth differentiable output — and `_prune` + out_block_0 +
         forward_single of level 0 run on the per-operator path, attached by autograd (single_stage_sparse._exec_forward)"""
         self.det = det
         self.tail0 = tail0
+        self.keep_state = bool(KEEP_STATE if keep_state is None else keep_state)
         self.training = training
         self.wgrad_async = wgrad_async and training
         bb, nh = det.backbone, det.neck_with_head
@@ -386,8 +391,11 @@ class NetProgram:
                 tape.append((stream, bwd))
             return y
 
-        def bn(x, mod, act, rows, res=None, stream=S_MAIN):
-            """MinkowskiBatchNorm (+ residual) + activation (functional.bn_train / norm_act)"""
+        def bn(x, mod, act, rows, res=None, stream=S_MAIN, add=None):
+            """MinkowskiBatchNorm (+ residual) + activation (functional.bn_train / norm_act); add = (inverse row map, tensor): the
+            apply kernel also adds tensor[inverse[r]] to row r behind the activation (the neck's sparse sum) — y IS the sum then"""
+            # ... which is legal because the layer's backward never reads y: without a residual act' is recomputed from x (y = -1 below)
+            assert add is None or res is None
             b = mod.bn
             C = b.num_features
             y = self.T(rows, C)
@@ -409,7 +417,7 @@ class NetProgram:
                 ay = amax_of[y] = self.amax_slot()
             self.emit(F, OP_BN_FWD, stream, x, self.D(rows), C, _f(b.eps), self.S(b.weight), self.S(b.bias), -1 if res is None else res, act,
                       _f(b.momentum), y, mean, var, cnt, self.S(b.running_mean), self.S(b.running_var), self.S(b.num_batches_tracked),
-                      1 if tr else 0, prod_word, groups, ay + 1)
+                      1 if tr else 0, prod_word, groups, ay + 1, *((add[0] + 1, add[1] + 1) if add is not None else (0, 0)))
             if tr:
                 sums = torch.zeros((2, C), dtype=torch.float32, device=self.dev)
                 si = self.S(sums)
@@ -452,16 +460,20 @@ class NetProgram:
         self.emit(F, OP_STEM_FWD, S_MAIN, x0, self.S(stem.kernel), self.M('stem'), t_stem, col)
         mean_in, var_in, cnt_in = self.T('B', 64), self.T('B', 64), self.T('B', 1)
         self.emit(F, OP_COL_STATS, S_MAIN, t_stem, seg1, self.D('n1'), 64, self.D('B'), mean_in, var_in, cnt_in)
-        t_in = self.T('n1', 64)
-        self.emit(F, OP_NORM_FWD, S_MAIN, t_stem, seg1, self.D('n1'), 64, mean_in, var_in, _f(inorm.eps), self.S(inorm.weight),
-                  self.S(inorm.bias), -1, relu, t_in)
-        self.relu_outs.append((t_in, 'n1', 64))
+        # instance norm + ReLU + max pool in ONE pass (norm.hip k_norm_act_maxpool8_fwd, bit for bit the two operators): the
+        # normalised tensor's only consumer is the pool, and the backward pass recomputes act' from t_stem — it is stored only for
+        # `decisions` (keep_state)
+        t_in = self.T('n1', 64) if self.keep_state else -1
+        if self.keep_state:
+            self.relu_outs.append((t_in, 'n1', 64))
         t_pool, arg = self.T('n2', 64), self.T('n2', 64)
         self.pool_arg = (arg, 'n2', 64)
         ap = -1
         if AMAX:
             ap = amax_of[t_pool] = self.amax_slot()
-        self.emit(F, OP_MAXPOOL_FWD, S_MAIN, t_in, self.M('pool'), 64, t_pool, arg, ap + 1)
+        pool_parent = self.T('n1', 1) if tr else -1       # child row -> pooled row (4 bytes per row), for the backward pass
+        self.emit(F, OP_NORM_POOL_FWD, S_MAIN, t_stem, seg1, 64, mean_in, var_in, _f(inorm.eps), self.S(inorm.weight), self.S(inorm.bias),
+                  relu, self.M('pool'), t_pool, arg, t_in, ap + 1, pool_parent)
         if tr:
             in_sums = self.T('B', 2 * 64, 'b')
             self.in_sums = in_sums
@@ -469,12 +481,12 @@ class NetProgram:
             def bwd_stem():
                 small_rows.append((None, 'B', 64, inorm.weight, inorm.bias))
                 g_pool = take(t_pool, 'n2', 64)
-                g_in = self.T('n1', 64, 'b')
-                self.emit(Bk, OP_MAXPOOL_BWD, S_MAIN, g_pool, arg, self.M('pool'), 64, g_in)
                 g_stem = self.T('n1', 64, 'b')
-                # instance norm + ReLU without a residual: y is not read (norm.hip bn_pre recomputes act')
-                self.emit(Bk, OP_NORM_BWD, S_MAIN, t_stem, -1, g_in, seg1, self.D('n1'), 64, self.D('B'), mean_in, var_in, cnt_in,
-                          _f(inorm.eps), self.S(inorm.weight), self.S(inorm.bias), relu, g_stem, -1, in_sums)
+                # pool backward + instance-norm backward without the scattered gradient in between: the normalisation backward's
+                # kernels read row r's gradient as g_pool[parent[r]] where arg[parent[r]] == r, else 0 (norm.hip pool_parent) — the sums
+                # in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
+                self.emit(Bk, OP_POOL_NORM_BWD, S_MAIN, t_stem, g_pool, arg, pool_parent, seg1, self.D('n1'), 64, self.D('B'), mean_in,
+                          var_in, cnt_in, _f(inorm.eps), self.S(inorm.weight), self.S(inorm.bias), relu, g_stem, in_sums)
                 if self.wgrad_async:
                     self.emit(Bk, OP_RECORD, S_MAIN, EV_W0)
                     self.emit(Bk, OP_WAIT, S_WGRAD, EV_W0)
@@ -539,18 +551,20 @@ class NetProgram:
                 t = gemm(x, self.gent_w[gi], x_rows, x_C, 8 * Ci, gw_i)
                 t = bn(t, up[1], elu, g_rows)
                 t = conv(t, up[3], f'gsame{i}', g_rows, g_rows)
-                t = bn(t, up[4], elu, g_rows)
                 # x = inputs[i] + t: every backbone voxel lies in the generated set -> the union IS the generated set (sparse.CoordMap.union)
+                # and the up block's last normalisation writes it (r7): its apply kernel adds the backbone row behind the activation
+                # through the inverse of rows{i} and folds the amax word of the SUM, complete when that kernel ends — before the head
+                # branch forks.  (The map is made here, two small launches, not by fc_plan_maps: the plan's outputs and interface stay.)
                 fb, fb_rows, fb_C = levels[i]
-                u = self.T(g_rows, Ci)
                 rows_i = self.DY(f'rows{i}')
-                self.emit(F, OP_UNION_FWD, S_MAIN, t, fb, rows_i, self.D(g_rows), self.D(fb_rows), self.D(g_rows), Ci, u)
-                if AMAX:                 # no producer folds a union: ONE pass here, before the head branch forks, serves both streams' consumers
-                    amax_of[u] = self.amax_op(F, S_MAIN, u, g_rows, Ci)
+                inv_i = self.T(g_rows, 1)
+                self.emit(F, OP_INV_ROWS, S_MAIN, rows_i, self.D(fb_rows), self.D(g_rows), inv_i)
+                u = bn(t, up[4], elu, g_rows, add=(inv_i, fb))
                 if tr:
-                    def bwd_union(u=u, t=t, fb=fb, fb_rows=fb_rows, rows_i=rows_i, g_rows=g_rows, Ci=Ci):
+                    def bwd_union(u=u, fb=fb, fb_rows=fb_rows, rows_i=rows_i, g_rows=g_rows, Ci=Ci):
+                        # d u / d (normalisation output) = identity on all rows (n_a == n_union): the layer's backward, next in the
+                        # reversed walk, takes the gradient of u as its own
                         gu = take(u, g_rows, Ci)
-                        accumulate(t, gu, g_rows, Ci, S_MAIN)          # d out / d fa = identity on all rows (n_a == n_union)
                         gfb = self.T(fb_rows, Ci, 'b')
                         self.emit(Bk, OP_GATHER, S_MAIN, gu, rows_i, self.D(fb_rows), Ci, gfb)
                         accumulate(fb, gfb, fb_rows, Ci, S_MAIN)
@@ -792,6 +806,7 @@ class NetProgram:
     def decisions(self, st):
         """(ReLU sign patterns in forward order, max-pool arg-max rows) of the forward pass bound in `st` — what
         oracle.DecisionTape replays (test infrastructure reads it; needs KEEP_STATE)"""
+        assert self.keep_state, 'this program does not store the stem\'s normalised output: build it under executor.KEEP_STATE'
         fa, addr, dims = st['fa'], st['addr'], st['dims']
 
         def view(idx, rows, C, dtype):
@@ -1004,15 +1019,17 @@ def program_for(det, training, tail0=False):
     if tail0 and min(det.backbone.n_outs, 4) < 2:
         return None
     key = (bool(training), bool(Fn.WGRAD_ASYNC), bool(nh.head_overlap), bool(tail0))
+    keep = bool(KEEP_STATE)                    # the recorder flips it at run time: a program built without the stem's normalised output
+                                               # must never be handed to `decisions`
     fuse = bool(Fn.BN_FUSE)                    # changes the emitted program (statistics tables, producer words): part of the cache key
     # ... and so does the operand split (r6): the three-product route's program carries amax slots, hint words and clear operators,
     # and the weight images are mode-dependent
     mode = Fn.split_mode() if Fn.X6 else -1
     cache = det.__dict__.setdefault('_programs', {})
     sig = NetProgram.signature(det)
-    prog = cache.get(key + (fuse, mode))
+    prog = cache.get(key + (fuse, mode, keep))
     if prog is None or prog._sig != sig:
-        prog = cache[key + (fuse, mode)] = NetProgram(det, *key)
+        prog = cache[key + (fuse, mode, keep)] = NetProgram(det, *key, keep_state=keep)
     if getattr(prog.w, 'split_mode', mode) != mode:      # the shared images were built in the other mode
         prog.w.fresh = False
     prog.w.split_mode = mode

@@ -32,9 +32,10 @@ extern "C" {
  * (flags bit27 went from "input is pre-split planes" to "flat addressing", fc_x6_planes / fc_conv_x6d removed: ADVICE r5),
  * r6 -> 6 (fc_compact_rows takes the output capacity; fc_plan_*, fc_argsort27 added), r6 -> 7 (fc_set_split_mode / fc_get_split_mode / fc_amax /
  * fc_conv_amax_hint / fc_amax_out_hint added; weight images are mode-dependent and fc_x6_weight_images writes their amax word), -> 8
- * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation).  A caller built against another
+ * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation), -> 9 (fc_norm_act_maxpool8_fwd / fc_maxpool8_norm_act_bwd / fc_inverse_rows / fc_norm_act_add_fwd /
+ * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates).  A caller built against another
  * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 8
+#define FC_ABI_VERSION 9
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -389,6 +390,43 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
 int fc_maxpool_fwd(const float* in, const int* nbr, int64_t n_out, int K, int C, float* out, int* argrow,
                    hipStream_t stream);
 int fc_maxpool_bwd(const float* gout, const int* argrow, int64_t n_out, int C, float* gin, hipStream_t stream);
+
+/* r7 — the stem's tail, ME.MinkowskiInstanceNorm + MinkowskiReLU + MinkowskiMaxPooling(k=2,s=2) (me_resnet.py:22-24), without the
+ * normalised tensor in between.  Forward: out / argrow (n_out, C) bit for bit those of fc_norm_act_fwd (no residual) followed by
+ * fc_maxpool_fwd over the (8, n_out) child table nbr — the activation is applied before the comparison, the first maximum in
+ * offset order wins ties, absent children are skipped, a row without children gives 0 / -1; y != NULL: the normalised rows are
+ * stored as well (every child row once).  seg (stride seg_stride ints, NULL = one scene) is the scene of an INPUT row; the children
+ * of a pooled row lie in one scene.  Folds max |out| into the word of fc_amax_out_hint.
+ * parent != NULL: parent[child row] = pooled row is stored as well (n_in ints), for the backward pass.
+ * Backward (the autograd of the pair): fc_norm_act_bwd (y == NULL, no residual) whose incoming gradient is read through the pool —
+ * row r receives gout[parent[r]][c] where argrow[parent[r]][c] == r, else 0 — instead of from the matrix a zero fill + fc_maxpool_bwd
+ * would write: the same launches, rows and summation order, so gx (n_in, C) and sums (nseg, 2, C) = [d beta, d gamma] per scene are bit
+ * for bit those of the three operators.  seg = scene of an INPUT row; every input row must be the child of a pooled row (the rows of
+ * a k2s2 stride map are): parent[] of any other row is not written. */
+int fc_norm_act_maxpool8_fwd(const float* x, const int* seg, int seg_stride, int C, const float* mean, const float* var, float eps,
+                             const float* gamma, const float* beta, int act, const int* nbr, int64_t n_out, float* out,
+                             int* argrow, float* y, int* parent, hipStream_t stream);
+int64_t fc_maxpool8_norm_act_bwd_ws_bytes(int64_t n_in, int C, int nseg);
+int fc_maxpool8_norm_act_bwd(const float* x, const float* gout, const int* argrow, const int* parent, const int* seg, int seg_stride,
+                             int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps,
+                             const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
+                             hipStream_t stream);
+
+/* r7 — the neck's sparse sum `inputs[i] + x` (fcaf3d_neck_with_head.py:101) written by the normalisation that produces x: where
+ * every row of inputs[i] lies in x's coordinate set the sum is x with inputs[i] added at rows[.].  fc_inverse_rows: inv (n_inv
+ * ints) = -1, then inv[rows[i]] = i for i < n (rows unique).  fc_norm_act_add_fwd / fc_bn_train_add_fwd: fc_norm_act_fwd /
+ * fc_bn_train_fwd with y[r] += add_src[add_inv[r]] where add_inv[r] >= 0, behind the activation (one fp32 add per element, the
+ * one fc_scatter_rows_add performs: same bits), and max |y| of the SUM folded into the word of fc_amax_out_hint.  The layer's
+ * backward must not read y (no residual: act' is recomputed from x).  add_inv == add_src == NULL: exactly the plain entry points. */
+int fc_inverse_rows(const int* rows, int64_t n, int64_t n_inv, int* inv, hipStream_t stream);
+int fc_norm_act_add_fwd(const float* x, const int* seg, int seg_stride, int64_t n, int C, const float* mean, const float* var,
+                        float eps, const float* gamma, const float* beta, const float* residual, int act, const int* add_inv,
+                        const float* add_src, float* y, hipStream_t stream);
+int fc_bn_train_add_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
+                        int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
+                        float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
+                        int64_t small_elems, const int* add_inv, const float* add_src, void* ws, int64_t ws_bytes,
+                        hipStream_t stream);
 
 /* feature rows of MinkowskiPruning (fcaf3d_neck_with_head.py:124-125), of the sparse sum `inputs[i] + x` (:101) and of
  * the per-scene decomposition (:266-275); fc_scatter_rows_add is the autograd of the gather. */
