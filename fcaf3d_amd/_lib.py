@@ -41,6 +41,28 @@ def parse_header(path=HEADER):
     return protos
 
 
+EXEC_OPS = os.path.join(_HERE, 'csrc', 'exec_ops.h')
+
+
+def parse_enums(path=EXEC_OPS):
+    """-> [{name: value}] per `enum { ... }` of a header of plain enums, in file order (the executor's operator and map-descriptor
+    layouts, csrc/exec_ops.h: the text csrc/exec.hip compiles).  An enumerator is `NAME`, `NAME = integer` or `NAME = a sum of earlier
+    names and integers`."""
+    txt = re.sub(r'//[^\n]*', '', open(path).read())
+    known, blocks = {}, []
+    for m in re.finditer(r'\benum\s*\{([^}]*)\}', txt):
+        block, nxt = {}, 0
+        for item in filter(None, (s.strip() for s in m.group(1).split(','))):
+            name, _, expr = (s.strip() for s in item.partition('='))
+            if expr:
+                nxt = sum(known[t] if t in known else int(t, 0) for t in (s.strip() for s in expr.split('+')))
+            assert re.fullmatch(r'[A-Z]\w*', name) and name not in known, item
+            block[name] = known[name] = nxt
+            nxt += 1
+        blocks.append(block)
+    return blocks
+
+
 ABI_VERSION = 9          # include/fcaf3d_hip.h FC_ABI_VERSION
 _lib = None
 _protos = None

@@ -16,20 +16,11 @@
 // single_stage_sparse.py:43-50 `extract_feat`, torch.autograd's backward over it).
 #include "fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "exec_ops.h"        // opcodes, the fields of every operator row and of the kernel-map descriptor, OPW / MAPW / NSTREAM
 #include <vector>
 
 namespace {
 
-enum : int64_t {
-  OP_STEM_FWD = 1, OP_COL_STATS, OP_NORM_FWD, OP_MAXPOOL_FWD, OP_CONV, OP_BN_FWD, OP_UNION_FWD, OP_HEAD_FWD, OP_RECORD, OP_WAIT,
-  OP_HEAD_BWD, OP_WGRAD, OP_BN_BWD, OP_NORM_BWD, OP_MAXPOOL_BWD, OP_STEM_WGRAD, OP_GATHER, OP_ADD, OP_SMALL_GRADS,
-  OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD, OP_INV_ROWS
-};
-// (r7: OP_NORM_FWD, OP_MAXPOOL_FWD, OP_UNION_FWD, OP_NORM_BWD, OP_MAXPOOL_BWD are no longer emitted and have no case below — the stem's tail runs as
-// OP_NORM_POOL_FWD / OP_POOL_NORM_BWD, the unions inside OP_BN_FWD; the numbers stay so that the others keep theirs)
-constexpr int OPW = 24;            // int64 words per operator
-constexpr int MAPW = 20;           // int64 words per kernel-map descriptor
-constexpr int NSTREAM = 3;
 constexpr int MAX_EVENTS = 64;
 
 // one event set per DEVICE (an event belongs to the device that was current when it was created; a process that drives
@@ -160,24 +151,24 @@ struct Ctx {
 int run_op_impl(Ctx& c, const int64_t* op);
 
 int run_op(Ctx& c, const int64_t* op) {
-  if (c.dry || !c.probe || (op[0] != OP_CONV && op[0] != OP_AMAX)) return run_op_impl(c, op);
+  if (c.dry || !c.probe || (op[ROW_OP] != OP_CONV && op[ROW_OP] != OP_AMAX)) return run_op_impl(c, op);
   ProbeRec r;
   r.a = probe_event(); r.b = probe_event();
   if (!r.a || !r.b) return run_op_impl(c, op);
-  hipStream_t st = c.streams[op[1]];
-  const int64_t Cin = op[8], Cout = op[9];
-  if (op[0] == OP_AMAX) {          // the amax pass of a convolution operand (h3): meta[0] = -2, n_in = rows, Cin = columns, no FLOPs
-    const int64_t m[8] = {-2, 0, c.dims[op[3]], 0, 0, op[4], 0, 0};
-    __builtin_memcpy(r.meta, m, sizeof m);
-  } else if (op[4] < 0) {
-    const int64_t n = c.dims[op[7]];
-    const int64_t m[8] = {-1, op[5], n, n, 1, Cin, Cout, 0};
-    __builtin_memcpy(r.meta, m, sizeof m);
+  hipStream_t st = c.streams[op[ROW_STREAM]];
+  if (op[ROW_OP] == OP_AMAX) {          // the amax pass of a convolution operand (h3): meta[0] = -2, n_in = rows, Cin = columns, no FLOPs
+    const int64_t meta[8] = {-2, 0, c.dims[op[AMAX_N]], 0, 0, op[AMAX_C], 0, 0};
+    __builtin_memcpy(r.meta, meta, sizeof meta);
+  } else if (op[CONV_MAP] < 0) {
+    const int64_t n = c.dims[op[CONV_N]];
+    const int64_t meta[8] = {-1, op[CONV_DIR], n, n, 1, op[CONV_CIN], op[CONV_COUT], 0};
+    __builtin_memcpy(r.meta, meta, sizeof meta);
   } else {
-    const int64_t* mp = c.maps + op[4] * MAPW;
-    const bool bwd = op[5] != 0;
-    const int64_t m[8] = {op[4], op[5], bwd ? mp[1] : mp[0], bwd ? mp[0] : mp[1], mp[2], Cin, Cout, (mp[19] & (bwd ? 2 : 1)) ? 1 : 0};
-    __builtin_memcpy(r.meta, m, sizeof m);
+    const int64_t* mp = c.maps + op[CONV_MAP] * MAPW;
+    const bool bwd = op[CONV_DIR] != 0;
+    const int64_t meta[8] = {op[CONV_MAP], op[CONV_DIR], bwd ? mp[MAP_N_OUT] : mp[MAP_N_IN], bwd ? mp[MAP_N_IN] : mp[MAP_N_OUT], mp[MAP_K],
+                             op[CONV_CIN], op[CONV_COUT], (mp[MAP_FLAGS] & (bwd ? MAP_ROUTE_BWD_PAIRS : MAP_ROUTE_FWD_PAIRS)) ? 1 : 0};
+    __builtin_memcpy(r.meta, meta, sizeof meta);
   }
   FC_HIP(hipEventRecord(r.a, st));
   const int rc = run_op_impl(c, op);
@@ -186,19 +177,24 @@ int run_op(Ctx& c, const int64_t* op) {
   return rc;
 }
 
+// a field that holds an address index, -1 = none
 template <class T>
 inline T* P(const Ctx& c, int64_t idx) { return idx < 0 ? nullptr : reinterpret_cast<T*>(c.addr[idx]); }
+// a ..._P1 field: address index + 1, 0 = none
+template <class T>
+inline T* P1(const Ctx& c, int64_t idx1) { return P<T>(c, idx1 - 1); }
 
-// Row blocks of the statistics table the convolution operator `pop` leaves (its word 10 = address index + 1 of the table): the
-// route logic of OP_CONV below, as a pure function of the step's tables — the BatchNorm operator behind it may sit in another
-// segment of a segmented run, so nothing is remembered from the launch.
-int64_t stats_blocks_of(const Ctx& c, const int64_t* pop) {
-  const int Cin = (int)pop[8], Cout = (int)pop[9];
+// Row blocks of the statistics table the convolution operator `conv` leaves (CONV_STATS_P1): the route logic of OP_CONV below, as a
+// pure function of the step's tables — the BatchNorm operator behind it may sit in another segment of a segmented run, so
+// nothing is remembered from the launch.
+int64_t stats_blocks_of(const Ctx& c, const int64_t* conv) {
+  const int Cin = (int)conv[CONV_CIN], Cout = (int)conv[CONV_COUT];
   const int fl = c.flags | FC_CONV_SPLIT | FC_CONV_IMAGE;
-  if (pop[4] < 0) return fc_conv_stats_blocks(c.dims[pop[7]], 1, Cin, Cout, fl, 0);
-  const int64_t* m = c.maps + pop[4] * MAPW;
-  const bool bwd = pop[5] != 0;
-  return fc_conv_stats_blocks(bwd ? m[0] : m[1], (int)m[2], Cin, Cout, fl, (m[19] & (bwd ? 2 : 1)) ? 1 : 0);
+  if (conv[CONV_MAP] < 0) return fc_conv_stats_blocks(c.dims[conv[CONV_N]], 1, Cin, Cout, fl, 0);
+  const int64_t* m = c.maps + conv[CONV_MAP] * MAPW;
+  const bool bwd = conv[CONV_DIR] != 0;
+  return fc_conv_stats_blocks(bwd ? m[MAP_N_IN] : m[MAP_N_OUT], (int)m[MAP_K], Cin, Cout, fl,
+                              (m[MAP_FLAGS] & (bwd ? MAP_ROUTE_BWD_PAIRS : MAP_ROUTE_FWD_PAIRS)) ? 1 : 0);
 }
 
 inline bool want_ws(Ctx& c, int s, int64_t bytes) {     // true: the launch may go ahead
@@ -207,267 +203,290 @@ inline bool want_ws(Ctx& c, int s, int64_t bytes) {     // true: the launch may 
 }
 
 int run_op_impl(Ctx& c, const int64_t* op) {
-  const int s = (int)op[1];
+  const int s = (int)op[ROW_STREAM];
   hipStream_t st = c.streams[s];
 #ifdef FC_KO_EXEC
   // knock-out build (tools/knockout.sh FC_KO_EXEC; never the product library): FC_KO_OPS = bit mask of op families NOT launched
   // (1 weight gradients, 2 convolutions, 4 normalisation) — what the step costs without them (results are garbage)
   {
     static const int ko = getenv("FC_KO_OPS") ? atoi(getenv("FC_KO_OPS")) : 0;
-    const int64_t o = op[0];
+    const int64_t o = op[ROW_OP];
     if (!c.dry && (((ko & 1) && (o == OP_WGRAD || o == OP_STEM_WGRAD)) || ((ko & 2) && o == OP_CONV) ||
                    ((ko & 4) && (o == OP_BN_FWD || o == OP_BN_BWD || o == OP_COL_STATS || o == OP_NORM_POOL_FWD || o == OP_POOL_NORM_BWD))))
       return 0;
   }
 #endif
-  switch (op[0]) {
-    case OP_STEM_FWD: {   // in, W, map, out, col
-      const int64_t* m = c.maps + op[4] * MAPW;
+  switch (op[ROW_OP]) {
+    case OP_STEM_FWD: {
+      const int64_t* m = c.maps + op[STEM_FWD_MAP] * MAPW;
       if (c.dry) return 0;
-      return fc_stem_conv_fwd(P<const float>(c, op[2]), P<const float>(c, op[3]), reinterpret_cast<const int*>(m[3]), P<float>(c, op[5]),
-                              P<float>(c, op[6]), m[0], m[1], (int)m[2], st);
+      return fc_stem_conv_fwd(P<const float>(c, op[STEM_FWD_X]), P<const float>(c, op[STEM_FWD_W]), reinterpret_cast<const int*>(m[MAP_NBR]),
+                              P<float>(c, op[STEM_FWD_OUT]), P<float>(c, op[STEM_FWD_COL]), m[MAP_N_IN], m[MAP_N_OUT], (int)m[MAP_K], st);
     }
-    case OP_COL_STATS: {  // x, seg, n(dim), C, nseg(dim), mean, var, cnt
-      const int64_t n = c.dims[op[4]];
-      const int C = (int)op[5], nseg = (int)c.dims[op[6]];
+    case OP_COL_STATS: {
+      const int64_t n = c.dims[op[COL_STATS_N]];
+      const int C = (int)op[COL_STATS_C], nseg = (int)c.dims[op[COL_STATS_NSEG]];
       if (!want_ws(c, s, fc_col_stats_ws_bytes(n, C, nseg))) return 0;
-      return fc_col_stats(P<const float>(c, op[2]), P<const int>(c, op[3]), op[3] >= 0 ? 4 : 0, n, C, nseg, P<float>(c, op[7]),
-                          P<float>(c, op[8]), P<float>(c, op[9]), c.ws[s], c.ws_bytes[s], st);
+      return fc_col_stats(P<const float>(c, op[COL_STATS_X]), P<const int>(c, op[COL_STATS_SEG]), op[COL_STATS_SEG] >= 0 ? 4 : 0, n, C, nseg,
+                          P<float>(c, op[COL_STATS_MEAN]), P<float>(c, op[COL_STATS_VAR]), P<float>(c, op[COL_STATS_CNT]), c.ws[s],
+                          c.ws_bytes[s], st);
     }
-    case OP_CONV: {  // in, img, map (-1: dense GEMM over n rows), dir, out, n(dim, dense only), Cin, Cout, statistics table + 1 | 0,
-                     // [BatchNorm-backward form of the table:] bn_x + 1 | 0, mean, var, gamma, beta, eps, act, add + 1 | 0, bn_y + 1 | 0
-      const int Cin = (int)op[8], Cout = (int)op[9];
+    case OP_CONV: {
+      const int Cin = (int)op[CONV_CIN], Cout = (int)op[CONV_COUT];
       const int fl = c.flags | FC_CONV_SPLIT | FC_CONV_IMAGE;
-      float* stats = (op[10] > 0 && stats_blocks_of(c, op) > 0) ? P<float>(c, op[10] - 1) : nullptr;
-      const float* bnx = (stats && op[11] > 0) ? P<const float>(c, op[11] - 1) : nullptr;
-      const float *bmean = P<const float>(c, op[12]), *bvar = P<const float>(c, op[13]), *bga = P<const float>(c, op[14]),
-                  *bbe = P<const float>(c, op[15]);
-      const float beps = (float)as_double(op[16]);
-      const int bact = (int)op[17];
-      const float* badd = op[18] > 0 ? P<const float>(c, op[18] - 1) : nullptr;     // second gradient contribution / the layer's output
-      const float* bny = op[19] > 0 ? P<const float>(c, op[19] - 1) : nullptr;
-      const float* in = P<const float>(c, op[2]);
-      const float* img = P<const float>(c, op[3]);
-      float* out = P<float>(c, op[6]);
-      // word 20: the amax word of `in` + 1 (h3 split; 0: the entry point makes its own pass) — consumed by the ONE call below
-      if (!c.dry && op[20] > 0) fc_conv_amax_hint(P<const unsigned>(c, op[20] - 1), nullptr);
-      if (op[4] < 0) {
-        const int64_t n = c.dims[op[7]];
+      float* stats = (op[CONV_STATS_P1] > 0 && stats_blocks_of(c, op) > 0) ? P1<float>(c, op[CONV_STATS_P1]) : nullptr;
+      const float* bnx = stats ? P1<const float>(c, op[CONV_BN_X_P1]) : nullptr;
+      const float *bmean = P<const float>(c, op[CONV_BN_MEAN]), *bvar = P<const float>(c, op[CONV_BN_VAR]),
+                  *bga = P<const float>(c, op[CONV_BN_GAMMA]), *bbe = P<const float>(c, op[CONV_BN_BETA]);
+      const float beps = (float)as_double(op[CONV_BN_EPS]);
+      const int bact = (int)op[CONV_BN_ACT];
+      const float* badd = P1<const float>(c, op[CONV_BN_ADD_P1]);
+      const float* bny = P1<const float>(c, op[CONV_BN_Y_P1]);
+      const float* in = P<const float>(c, op[CONV_X]);
+      const float* img = P<const float>(c, op[CONV_IMG]);
+      float* out = P<float>(c, op[CONV_OUT]);
+      // the amax word of `in` is consumed by the ONE call below
+      if (!c.dry && op[CONV_AMAX_X_P1] > 0) fc_conv_amax_hint(P1<const unsigned>(c, op[CONV_AMAX_X_P1]), nullptr);
+      if (op[CONV_MAP] < 0) {
+        const int64_t n = c.dims[op[CONV_N]];
         if (!want_ws(c, s, fc_conv_fwd_ws_bytes(n, 1, Cin, Cout, fl))) return 0;
         if (bnx)
           return fc_conv_fwd_bn_bwd_stats(in, img, nullptr, nullptr, out, n, n, 1, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], stats, bnx, bmean, bvar,
                                           bga, bbe, beps, bact, badd, bny, st);
         return fc_conv_fwd_stats(in, img, nullptr, nullptr, out, n, n, 1, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], stats, st);
       }
-      const int64_t* m = c.maps + op[4] * MAPW;
-      const bool bwd = op[5] != 0;
-      const int64_t n_in = bwd ? m[1] : m[0], n_out = bwd ? m[0] : m[1];
-      const int K = (int)m[2];
-      if (m[19] & (bwd ? 2 : 1)) {                       // per offset over the exact pair lists
-        const int b = bwd ? 14 : 9;
-        const int *pi = reinterpret_cast<const int*>(m[b]), *pc = reinterpret_cast<const int*>(m[b + 3]),
-                  *pp = reinterpret_cast<const int*>(m[b + 2]);
+      const int64_t* m = c.maps + op[CONV_MAP] * MAPW;
+      const bool bwd = op[CONV_DIR] != 0;
+      const int64_t n_in = bwd ? m[MAP_N_OUT] : m[MAP_N_IN], n_out = bwd ? m[MAP_N_IN] : m[MAP_N_OUT];
+      const int K = (int)m[MAP_K];
+      if (m[MAP_FLAGS] & (bwd ? MAP_ROUTE_BWD_PAIRS : MAP_ROUTE_FWD_PAIRS)) {                       // per offset over the exact pair lists
+        const int64_t* pr = m + (bwd ? MAP_PAIRS_T : MAP_PAIRS);
+        const int *pi = reinterpret_cast<const int*>(pr[PAIR_IN]), *pc = reinterpret_cast<const int*>(pr[PAIR_CNT]),
+                  *pp = reinterpret_cast<const int*>(pr[PAIR_POS]);
         if (!want_ws(c, s, fc_conv_fwd_pairs_ws_bytes(n_out, K, Cout))) return 0;
         if (bnx)
-          return fc_conv_fwd_pairs_tiles_bn_bwd_stats(in, img, pi, pc, pp, out, n_in, n_out, K, Cin, Cout, m[b + 4], fl, c.ws[s], c.ws_bytes[s],
-                                                      stats, bnx, bmean, bvar, bga, bbe, beps, bact, badd, bny, st);
-        return fc_conv_fwd_pairs_tiles_stats(in, img, pi, pc, pp, out, n_in, n_out, K, Cin, Cout, m[b + 4], fl, c.ws[s], c.ws_bytes[s], stats,
-                                             st);
+          return fc_conv_fwd_pairs_tiles_bn_bwd_stats(in, img, pi, pc, pp, out, n_in, n_out, K, Cin, Cout, pr[PAIR_TILES], fl, c.ws[s],
+                                                      c.ws_bytes[s], stats, bnx, bmean, bvar, bga, bbe, beps, bact, badd, bny, st);
+        return fc_conv_fwd_pairs_tiles_stats(in, img, pi, pc, pp, out, n_in, n_out, K, Cin, Cout, pr[PAIR_TILES], fl, c.ws[s], c.ws_bytes[s],
+                                             stats, st);
       }
-      const int *tab = reinterpret_cast<const int*>(m[bwd ? 7 : 5]), *oidx = reinterpret_cast<const int*>(m[bwd ? 8 : 6]);
+      const int *tab = reinterpret_cast<const int*>(bwd ? m[MAP_BWD_TAB] : m[MAP_FWD_TAB]),
+                *oidx = reinterpret_cast<const int*>(bwd ? m[MAP_BWD_IDX] : m[MAP_FWD_IDX]);
       if (!want_ws(c, s, fc_conv_fwd_ws_bytes(n_out, K, Cin, Cout, fl))) return 0;
       if (bnx)
         return fc_conv_fwd_bn_bwd_stats(in, img, tab, oidx, out, n_in, n_out, K, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], stats, bnx, bmean, bvar,
                                         bga, bbe, beps, bact, badd, bny, st);
       return fc_conv_fwd_stats(in, img, tab, oidx, out, n_in, n_out, K, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], stats, st);
     }
-    case OP_BN_FWD: {  // x, n(dim), C, eps, gamma, beta, res, act, momentum, y, mean, var, cnt, rmean, rvar, nbt, train, [19-21 below],
-                       // word 22: inverse row map + 1 | 0, word 23: tensor + 1 whose rows are added behind the activation (the neck's sparse sum)
-      const int64_t n = c.dims[op[3]];
-      const int C = (int)op[4];
-      const float eps = (float)as_double(op[5]), mom = (float)as_double(op[10]);
-      const int* add_inv = op[22] > 0 ? P<const int>(c, op[22] - 1) : nullptr;
-      const float* add_src = op[22] > 0 ? P<const float>(c, op[23] - 1) : nullptr;
-      if (!op[18]) {      // eval mode: the running statistics are the statistics
+    case OP_BN_FWD: {
+      const int64_t n = c.dims[op[BN_FWD_N]];
+      const int C = (int)op[BN_FWD_C];
+      const float eps = (float)as_double(op[BN_FWD_EPS]), mom = (float)as_double(op[BN_FWD_MOMENTUM]);
+      const int* add_inv = P1<const int>(c, op[BN_FWD_ADD_INV_P1]);
+      const float* add_src = op[BN_FWD_ADD_INV_P1] > 0 ? P1<const float>(c, op[BN_FWD_ADD_SRC_P1]) : nullptr;
+      if (!op[BN_FWD_TRAIN]) {      // eval mode: the running statistics are the statistics
         if (c.dry) return 0;
-        if (op[21] > 0) fc_amax_out_hint(P<unsigned>(c, op[21] - 1));
-        return fc_norm_act_add_fwd(P<const float>(c, op[2]), nullptr, 0, n, C, P<const float>(c, op[15]), P<const float>(c, op[16]), eps,
-                                   P<const float>(c, op[6]), P<const float>(c, op[7]), P<const float>(c, op[8]), (int)op[9], add_inv, add_src,
-                                   P<float>(c, op[11]), st);
+        if (op[BN_FWD_AMAX_Y_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[BN_FWD_AMAX_Y_P1]));
+        return fc_norm_act_add_fwd(P<const float>(c, op[BN_FWD_X]), nullptr, 0, n, C, P<const float>(c, op[BN_FWD_RMEAN]),
+                                   P<const float>(c, op[BN_FWD_RVAR]), eps, P<const float>(c, op[BN_FWD_GAMMA]),
+                                   P<const float>(c, op[BN_FWD_BETA]), P<const float>(c, op[BN_FWD_RES]), (int)op[BN_FWD_ACT], add_inv, add_src,
+                                   P<float>(c, op[BN_FWD_Y]), st);
       }
-      // training: statistics from the producer's epilogue when the operator names one (word 19 = producer index + 1, word 20 =
-      // column groups per channel) and that launch has a statistics epilogue; else computed from x (fc_bn_train_fwd)
+      // training: statistics from the producer's epilogue when the operator names one and that launch has a statistics epilogue;
+      // else computed from x (fc_bn_train_fwd)
       const float* part = nullptr;
       int64_t nbp = 0;
-      if (op[19] > 0) {
-        const int64_t* pop = c.ops + (op[19] - 1) * OPW;
-        nbp = pop[10] > 0 ? stats_blocks_of(c, pop) : 0;
-        if (nbp > 0) part = P<const float>(c, pop[10] - 1);
+      if (op[BN_FWD_PRODUCER_P1] > 0) {
+        const int64_t* conv = c.ops + (op[BN_FWD_PRODUCER_P1] - 1) * OPW;
+        nbp = conv[CONV_STATS_P1] > 0 ? stats_blocks_of(c, conv) : 0;
+        if (nbp > 0) part = P1<const float>(c, conv[CONV_STATS_P1]);
       }
       if (!want_ws(c, s, fc_bn_train_ws_bytes(n, C))) return 0;
-      if (op[21] > 0) fc_amax_out_hint(P<unsigned>(c, op[21] - 1));         // word 21: amax word of y + 1 | 0 (h3: y feeds a convolution)
-      return fc_bn_train_add_fwd(P<const float>(c, op[2]), n, C, eps, P<const float>(c, op[6]), P<const float>(c, op[7]),
-                                 P<const float>(c, op[8]), (int)op[9], mom, P<float>(c, op[11]), P<float>(c, op[12]), P<float>(c, op[13]),
-                                 P<float>(c, op[14]), P<float>(c, op[15]), P<float>(c, op[16]), P<long long>(c, op[17]), part, nbp,
-                                 op[20] > 0 ? (int)op[20] : 1, c.bn_small_elems, add_inv, add_src, c.ws[s], c.ws_bytes[s], st);
+      if (op[BN_FWD_AMAX_Y_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[BN_FWD_AMAX_Y_P1]));         // (h3: y feeds a convolution)
+      return fc_bn_train_add_fwd(P<const float>(c, op[BN_FWD_X]), n, C, eps, P<const float>(c, op[BN_FWD_GAMMA]),
+                                 P<const float>(c, op[BN_FWD_BETA]), P<const float>(c, op[BN_FWD_RES]), (int)op[BN_FWD_ACT], mom,
+                                 P<float>(c, op[BN_FWD_Y]), P<float>(c, op[BN_FWD_MEAN]), P<float>(c, op[BN_FWD_VAR]),
+                                 P<float>(c, op[BN_FWD_CNT]), P<float>(c, op[BN_FWD_RMEAN]), P<float>(c, op[BN_FWD_RVAR]),
+                                 P<long long>(c, op[BN_FWD_NBT]), part, nbp, op[BN_FWD_GROUPS] > 0 ? (int)op[BN_FWD_GROUPS] : 1,
+                                 c.bn_small_elems, add_inv, add_src, c.ws[s], c.ws_bytes[s], st);
     }
-    case OP_HEAD_FWD: {  // y, ld, bias, scale, n(dim), n_reg, n_cls, cent, bbox, cls, cmax
+    case OP_HEAD_FWD: {
       if (c.dry) return 0;
-      return fc_head_split_fwd(P<const float>(c, op[2]), (int)op[3], P<const float>(c, op[4]), P<const float>(c, op[5]), c.dims[op[6]],
-                               (int)op[7], (int)op[8], P<float>(c, op[9]), P<float>(c, op[10]), P<float>(c, op[11]), P<float>(c, op[12]), st);
+      return fc_head_split_fwd(P<const float>(c, op[HEAD_FWD_Y]), (int)op[HEAD_FWD_LD], P<const float>(c, op[HEAD_FWD_BIAS]),
+                               P<const float>(c, op[HEAD_FWD_SCALE]), c.dims[op[HEAD_FWD_N]], (int)op[HEAD_FWD_N_REG], (int)op[HEAD_FWD_N_CLS],
+                               P<float>(c, op[HEAD_FWD_CENT]), P<float>(c, op[HEAD_FWD_BBOX]), P<float>(c, op[HEAD_FWD_CLS]),
+                               P<float>(c, op[HEAD_FWD_CMAX]), st);
     }
     case OP_RECORD:
       if (c.dry) return 0;
-      FC_HIP(hipEventRecord(g_events[op[2]], st));
+      FC_HIP(hipEventRecord(g_events[op[RECORD_EVENT]], st));
       return 0;
     case OP_WAIT:
       if (c.dry) return 0;
-      FC_HIP(hipStreamWaitEvent(st, g_events[op[2]], 0));
+      FC_HIP(hipStreamWaitEvent(st, g_events[op[WAIT_EVENT]], 0));
       return 0;
-    case OP_HEAD_BWD: {  // y, ld, scale, bbox, g_cent, g_bbox, g_cls, n(dim), n_reg, n_cls, gy, gs_row | -1, g_scale, bias_part
-      if (op[13] < 0) {    // with the scale / class-bias reductions of this level (fc_head_split_bwd_sums)
-        const int64_t n = c.dims[op[9]];
+    case OP_HEAD_BWD: {
+      const float *y = P<const float>(c, op[HEAD_BWD_Y]), *scale = P<const float>(c, op[HEAD_BWD_SCALE]),
+                  *bbox = P<const float>(c, op[HEAD_BWD_BBOX]), *g_cent = P<const float>(c, op[HEAD_BWD_G_CENT]),
+                  *g_bbox = P<const float>(c, op[HEAD_BWD_G_BBOX]), *g_cls = P<const float>(c, op[HEAD_BWD_G_CLS]);
+      const int64_t n = c.dims[op[HEAD_BWD_N]];
+      const int ld = (int)op[HEAD_BWD_LD], n_reg = (int)op[HEAD_BWD_N_REG], n_cls = (int)op[HEAD_BWD_N_CLS];
+      if (op[HEAD_BWD_GS_ROW] < 0) {    // with the scale / class-bias reductions of this level (fc_head_split_bwd_sums)
         if (!want_ws(c, s, fc_head_split_bwd_sums_ws_bytes(n))) return 0;
-        if (op[16] > 0) fc_amax_out_hint(P<unsigned>(c, op[16] - 1));         // word 16: amax slot of gy + 1 | 0
-        return fc_head_split_bwd_sums(P<const float>(c, op[2]), (int)op[3], P<const float>(c, op[4]), P<const float>(c, op[5]),
-                                      P<const float>(c, op[6]), P<const float>(c, op[7]), P<const float>(c, op[8]), n, (int)op[10],
-                                      (int)op[11], P<float>(c, op[12]), P<float>(c, op[15]), P<float>(c, op[14]), c.ws[s],
-                                      c.ws_bytes[s], st);
+        if (op[HEAD_BWD_AMAX_GY_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[HEAD_BWD_AMAX_GY_P1]));
+        return fc_head_split_bwd_sums(y, ld, scale, bbox, g_cent, g_bbox, g_cls, n, n_reg, n_cls, P<float>(c, op[HEAD_BWD_GY]),
+                                      P<float>(c, op[HEAD_BWD_BIAS_PART]), P<float>(c, op[HEAD_BWD_G_SCALE]), c.ws[s], c.ws_bytes[s], st);
       }
       if (c.dry) return 0;
-      return fc_head_split_bwd(P<const float>(c, op[2]), (int)op[3], P<const float>(c, op[4]), P<const float>(c, op[5]),
-                               P<const float>(c, op[6]), P<const float>(c, op[7]), P<const float>(c, op[8]), c.dims[op[9]], (int)op[10],
-                               (int)op[11], P<float>(c, op[12]), P<float>(c, op[13]), st);
+      return fc_head_split_bwd(y, ld, scale, bbox, g_cent, g_bbox, g_cls, n, n_reg, n_cls, P<float>(c, op[HEAD_BWD_GY]),
+                               P<float>(c, op[HEAD_BWD_GS_ROW]), st);
     }
-    case OP_WGRAD: {  // in, gout, map (-1: dense), gW, n(dim, dense only), Cin, Cout, amax word of in + 1 | 0, of gout + 1 | 0
-      const int Cin = (int)op[7], Cout = (int)op[8];
+    case OP_WGRAD: {
+      const int Cin = (int)op[WGRAD_CIN], Cout = (int)op[WGRAD_COUT];
       const int fl = c.flags | FC_CONV_SPLIT;
-      if (!c.dry && (op[9] > 0 || op[10] > 0))
-        fc_conv_amax_hint(op[9] > 0 ? P<const unsigned>(c, op[9] - 1) : nullptr, op[10] > 0 ? P<const unsigned>(c, op[10] - 1) : nullptr);
-      if (op[4] < 0) {
-        const int64_t n = c.dims[op[6]];
+      const float *in = P<const float>(c, op[WGRAD_X]), *gout = P<const float>(c, op[WGRAD_GOUT]);
+      float* gw = P<float>(c, op[WGRAD_GW]);
+      if (!c.dry && (op[WGRAD_AMAX_X_P1] > 0 || op[WGRAD_AMAX_GOUT_P1] > 0))
+        fc_conv_amax_hint(P1<const unsigned>(c, op[WGRAD_AMAX_X_P1]), P1<const unsigned>(c, op[WGRAD_AMAX_GOUT_P1]));
+      if (op[WGRAD_MAP] < 0) {
+        const int64_t n = c.dims[op[WGRAD_N]];
         if (!want_ws(c, s, fc_conv_wgrad_ws_bytes(n, 1, Cin, Cout, fl))) return 0;
-        return fc_conv_wgrad(P<const float>(c, op[2]), P<const float>(c, op[3]), nullptr, nullptr, P<float>(c, op[5]), n, n, 1, Cin, Cout, fl,
-                             c.ws[s], c.ws_bytes[s], st);
+        return fc_conv_wgrad(in, gout, nullptr, nullptr, gw, n, n, 1, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], st);
       }
-      const int64_t* m = c.maps + op[4] * MAPW;
-      const int K = (int)m[2];
-      if (!want_ws(c, s, fc_conv_wgrad_ws_bytes(m[1], K, Cin, Cout, fl))) return 0;
-      if ((m[19] & 4) && Cin % 64 == 0 && Cout % 64 == 0)
-        return fc_conv_wgrad_pairs(P<const float>(c, op[2]), P<const float>(c, op[3]), reinterpret_cast<const int*>(m[9]),
-                                   reinterpret_cast<const int*>(m[10]), reinterpret_cast<const int*>(m[12]), P<float>(c, op[5]), m[0], m[1],
-                                   K, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], st);
-      return fc_conv_wgrad(P<const float>(c, op[2]), P<const float>(c, op[3]), reinterpret_cast<const int*>(m[3]), nullptr,
-                           P<float>(c, op[5]), m[0], m[1], K, Cin, Cout, fl, c.ws[s], c.ws_bytes[s], st);
+      const int64_t* m = c.maps + op[WGRAD_MAP] * MAPW;
+      const int K = (int)m[MAP_K];
+      if (!want_ws(c, s, fc_conv_wgrad_ws_bytes(m[MAP_N_OUT], K, Cin, Cout, fl))) return 0;
+      if ((m[MAP_FLAGS] & MAP_ROUTE_WGRAD_PAIRS) && Cin % 64 == 0 && Cout % 64 == 0) {
+        const int64_t* pr = m + MAP_PAIRS;
+        return fc_conv_wgrad_pairs(in, gout, reinterpret_cast<const int*>(pr[PAIR_IN]), reinterpret_cast<const int*>(pr[PAIR_OUT]),
+                                   reinterpret_cast<const int*>(pr[PAIR_CNT]), gw, m[MAP_N_IN], m[MAP_N_OUT], K, Cin, Cout, fl, c.ws[s],
+                                   c.ws_bytes[s], st);
+      }
+      return fc_conv_wgrad(in, gout, reinterpret_cast<const int*>(m[MAP_NBR]), nullptr, gw, m[MAP_N_IN], m[MAP_N_OUT], K, Cin, Cout, fl,
+                           c.ws[s], c.ws_bytes[s], st);
     }
-    case OP_BN_BWD: {  // x, y, gy, n(dim), C, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums, gy2 + 1 | 0, producer of gy + 1 | 0
-      const int64_t n = c.dims[op[5]];
-      const int C = (int)op[6];
-      const float eps = (float)as_double(op[10]);
-      // the backward-data convolution that wrote gy may have left this layer's two reductions in its epilogue (word 18: its index
-      // + 1 in this list; fc_conv_fwd_bn_bwd_stats)
+    case OP_BN_BWD: {
+      const int64_t n = c.dims[op[BN_BWD_N]];
+      const int C = (int)op[BN_BWD_C];
+      const float eps = (float)as_double(op[BN_BWD_EPS]);
+      // the backward-data convolution that wrote gy may have left this layer's two reductions in its epilogue (fc_conv_fwd_bn_bwd_stats)
       const float* part = nullptr;
       int64_t nbp = 0;
-      if (op[18] > 0) {
-        const int64_t* pop = c.ops + (op[18] - 1) * OPW;
-        nbp = (pop[10] > 0 && pop[11] > 0) ? stats_blocks_of(c, pop) : 0;
-        if (nbp > 0) part = P<const float>(c, pop[10] - 1);
+      if (op[BN_BWD_PRODUCER_P1] > 0) {
+        const int64_t* conv = c.ops + (op[BN_BWD_PRODUCER_P1] - 1) * OPW;
+        nbp = (conv[CONV_STATS_P1] > 0 && conv[CONV_BN_X_P1] > 0) ? stats_blocks_of(c, conv) : 0;
+        if (nbp > 0) part = P1<const float>(c, conv[CONV_STATS_P1]);
       }
       if (!want_ws(c, s, fc_bn_train_ws_bytes(n, C))) return 0;
-      if (op[19] > 0) fc_amax_out_hint(P<unsigned>(c, op[19] - 1));         // word 19: amax word of gx + 1 | 0
-      return fc_bn_train_bwd(P<const float>(c, op[2]), P<const float>(c, op[3]), P<const float>(c, op[4]),
-                             op[17] > 0 ? P<const float>(c, op[17] - 1) : nullptr, n, C, P<const float>(c, op[7]), P<const float>(c, op[8]),
-                             P<const float>(c, op[9]), eps, P<const float>(c, op[11]), P<const float>(c, op[12]), (int)op[13],
-                             P<float>(c, op[14]), P<float>(c, op[15]), P<float>(c, op[16]), part, nbp, c.bn_small_elems, c.ws[s],
+      if (op[BN_BWD_AMAX_GX_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[BN_BWD_AMAX_GX_P1]));
+      return fc_bn_train_bwd(P<const float>(c, op[BN_BWD_X]), P<const float>(c, op[BN_BWD_Y]), P<const float>(c, op[BN_BWD_GY]),
+                             P1<const float>(c, op[BN_BWD_GY2_P1]), n, C, P<const float>(c, op[BN_BWD_MEAN]),
+                             P<const float>(c, op[BN_BWD_VAR]), P<const float>(c, op[BN_BWD_CNT]), eps, P<const float>(c, op[BN_BWD_GAMMA]),
+                             P<const float>(c, op[BN_BWD_BETA]), (int)op[BN_BWD_ACT], P<float>(c, op[BN_BWD_GX]),
+                             P<float>(c, op[BN_BWD_GRES]), P<float>(c, op[BN_BWD_SUMS]), part, nbp, c.bn_small_elems, c.ws[s],
                              c.ws_bytes[s], st);
     }
-    case OP_STEM_WGRAD: {  // col, gout, map, gW
-      const int64_t* m = c.maps + op[4] * MAPW;
-      if (!want_ws(c, s, fc_stem_conv_wgrad_ws_bytes(m[1], (int)m[2]))) return 0;
-      return fc_stem_conv_wgrad(P<const float>(c, op[2]), P<const float>(c, op[3]), P<float>(c, op[5]), m[1], (int)m[2], c.ws[s],
-                                c.ws_bytes[s], st);
+    case OP_STEM_WGRAD: {
+      const int64_t* m = c.maps + op[STEM_WGRAD_MAP] * MAPW;
+      if (!want_ws(c, s, fc_stem_conv_wgrad_ws_bytes(m[MAP_N_OUT], (int)m[MAP_K]))) return 0;
+      return fc_stem_conv_wgrad(P<const float>(c, op[STEM_WGRAD_COL]), P<const float>(c, op[STEM_WGRAD_GOUT]), P<float>(c, op[STEM_WGRAD_GW]),
+                                m[MAP_N_OUT], (int)m[MAP_K], c.ws[s], c.ws_bytes[s], st);
     }
-    case OP_GATHER: {  // src, idx, n(dim), C, dst
+    case OP_GATHER: {
       if (c.dry) return 0;
-      return fc_gather_rows(P<const float>(c, op[2]), P<const int>(c, op[3]), c.dims[op[4]], (int)op[5], P<float>(c, op[6]), st);
+      return fc_gather_rows(P<const float>(c, op[GATHER_SRC]), P<const int>(c, op[GATHER_IDX]), c.dims[op[GATHER_N]], (int)op[GATHER_C],
+                            P<float>(c, op[GATHER_DST]), st);
     }
-    case OP_ADD: {  // dst += src over n(dim) * C floats (C % 4 == 0)
+    case OP_ADD: {
       if (c.dry) return 0;
-      const int64_t n4 = c.dims[op[4]] * op[5] / 4;
-      if (n4 > 0) k_add_inplace<<<(unsigned)fc_cdiv(n4, 256), 256, 0, st>>>(P<float>(c, op[2]), P<const float>(c, op[3]), n4);
+      const int64_t n4 = c.dims[op[ADD_N]] * op[ADD_C] / 4;
+      if (n4 > 0) k_add_inplace<<<(unsigned)fc_cdiv(n4, 256), 256, 0, st>>>(P<float>(c, op[ADD_DST]), P<const float>(c, op[ADD_SRC]), n4);
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_SMALL_GRADS: {  // desc (device), first entry, n entries
+    case OP_SMALL_GRADS: {
       if (c.dry) return 0;
-      if (op[4] > 0) k_small_grads<<<(unsigned)op[4], 128, 0, st>>>(P<const long long>(c, op[2]) + 8 * op[3], (int)op[4]);
+      const int64_t cnt = op[SMALL_GRADS_COUNT];
+      if (cnt > 0) k_small_grads<<<(unsigned)cnt, 128, 0, st>>>(P<const long long>(c, op[SMALL_GRADS_DESC]) + 8 * op[SMALL_GRADS_FIRST], (int)cnt);
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_COL_SUM: {  // x (n, C), n(dim), C, dst (C)
+    case OP_COL_SUM: {
       if (c.dry) return 0;
-      k_col_sum<<<(unsigned)op[4], 1024, 0, st>>>(P<const float>(c, op[2]), c.dims[op[3]], (int)op[4], P<float>(c, op[5]));
+      k_col_sum<<<(unsigned)op[COL_SUM_C], 1024, 0, st>>>(P<const float>(c, op[COL_SUM_X]), c.dims[op[COL_SUM_N]], (int)op[COL_SUM_C],
+                                                         P<float>(c, op[COL_SUM_DST]));
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_ROW_SUM: {  // x (n), n(dim), dst (1)
+    case OP_ROW_SUM: {
       if (c.dry) return 0;
-      k_col_sum<<<1, 1024, 0, st>>>(P<const float>(c, op[2]), c.dims[op[3]], 1, P<float>(c, op[4]));
+      k_col_sum<<<1, 1024, 0, st>>>(P<const float>(c, op[ROW_SUM_X]), c.dims[op[ROW_SUM_N]], 1, P<float>(c, op[ROW_SUM_DST]));
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_PERMUTE_GENT: {  // src (Cin, 8 Cout), dst (8, Cin, Cout), Cin, Cout
+    case OP_PERMUTE_GENT: {
       if (c.dry) return 0;
-      const int64_t total = 8 * op[4] * op[5];
-      k_permute_gent<<<(unsigned)fc_cdiv(total, 256), 256, 0, st>>>(P<const float>(c, op[2]), P<float>(c, op[3]), (int)op[4], (int)op[5]);
+      const int Cin = (int)op[PERMUTE_GENT_CIN], Cout = (int)op[PERMUTE_GENT_COUT];
+      const int64_t total = (int64_t)8 * Cin * Cout;
+      k_permute_gent<<<(unsigned)fc_cdiv(total, 256), 256, 0, st>>>(P<const float>(c, op[PERMUTE_GENT_SRC]), P<float>(c, op[PERMUTE_GENT_DST]),
+                                                                    Cin, Cout);
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_HEAD_WFIN: {  // part, nl, R, ld, n_reg, n_cls, g_cent, g_reg, g_cls, bias_part | -1, g_bias | -1
+    case OP_HEAD_WFIN: {
       if (c.dry) return 0;
-      const int total = (int)(op[4] * (1 + op[6] + op[7]));
-      k_head_wfin<<<(unsigned)fc_cdiv(total, 256), 256, 0, st>>>(P<const float>(c, op[2]), (int)op[3], (int)op[4], (int)op[5], (int)op[6],
-                                                                 (int)op[7], P<float>(c, op[8]), P<float>(c, op[9]), P<float>(c, op[10]),
-                                                                 P<const float>(c, op[11]), P<float>(c, op[12]));
+      const int R = (int)op[HEAD_WFIN_R], n_reg = (int)op[HEAD_WFIN_N_REG], n_cls = (int)op[HEAD_WFIN_N_CLS];
+      const int total = R * (1 + n_reg + n_cls);
+      k_head_wfin<<<(unsigned)fc_cdiv(total, 256), 256, 0, st>>>(P<const float>(c, op[HEAD_WFIN_PART]), (int)op[HEAD_WFIN_NL], R,
+                                                                 (int)op[HEAD_WFIN_LD], n_reg, n_cls, P<float>(c, op[HEAD_WFIN_G_CENT]),
+                                                                 P<float>(c, op[HEAD_WFIN_G_REG]), P<float>(c, op[HEAD_WFIN_G_CLS]),
+                                                                 P<const float>(c, op[HEAD_WFIN_BIAS_PART]), P<float>(c, op[HEAD_WFIN_G_BIAS]));
       FC_CHECK_LAUNCH();
       return 0;
     }
-    case OP_AMAX: {  // x, n(dim), C, slot: max |x| over n * C floats -> slot word 0 (fc_amax)
+    case OP_AMAX: {
       if (c.dry) return 0;
-      return fc_amax(P<const float>(c, op[2]), c.dims[op[3]] * op[4], P<unsigned>(c, op[5]), st);
+      return fc_amax(P<const float>(c, op[AMAX_X]), c.dims[op[AMAX_N]] * op[AMAX_C], P<unsigned>(c, op[AMAX_SLOT]), st);
     }
-    case OP_CLEAR: {  // dst, bytes: zero-fill (the amax words a pass's producers fold into)
+    case OP_CLEAR: {
       if (c.dry) return 0;
-      FC_HIP(hipMemsetAsync(P<void>(c, op[2]), 0, (size_t)op[3], st));
+      FC_HIP(hipMemsetAsync(P<void>(c, op[CLEAR_DST]), 0, (size_t)op[CLEAR_BYTES], st));
       return 0;
     }
-    case OP_NORM_POOL_FWD: {  // x, seg, C, mean, var, eps, gamma, beta, act, map, out, arg, y | -1, amax word of out + 1 | 0, parent | -1
-      const int64_t* m = c.maps + op[11] * MAPW;
+    case OP_NORM_POOL_FWD: {
+      const int64_t* m = c.maps + op[NORM_POOL_FWD_MAP] * MAPW;
       if (c.dry) return 0;
-      if ((int)m[2] != 8) return FC_EINVAL;
-      if (op[15] > 0) fc_amax_out_hint(P<unsigned>(c, op[15] - 1));
-      return fc_norm_act_maxpool8_fwd(P<const float>(c, op[2]), P<const int>(c, op[3]), op[3] >= 0 ? 4 : 0, (int)op[4], P<const float>(c, op[5]),
-                                      P<const float>(c, op[6]), (float)as_double(op[7]), P<const float>(c, op[8]), P<const float>(c, op[9]),
-                                      (int)op[10], reinterpret_cast<const int*>(m[3]), m[1], P<float>(c, op[12]), P<int>(c, op[13]),
-                                      P<float>(c, op[14]), P<int>(c, op[16]), st);
+      if ((int)m[MAP_K] != 8) return FC_EINVAL;
+      if (op[NORM_POOL_FWD_AMAX_OUT_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[NORM_POOL_FWD_AMAX_OUT_P1]));
+      return fc_norm_act_maxpool8_fwd(P<const float>(c, op[NORM_POOL_FWD_X]), P<const int>(c, op[NORM_POOL_FWD_SEG]),
+                                      op[NORM_POOL_FWD_SEG] >= 0 ? 4 : 0, (int)op[NORM_POOL_FWD_C], P<const float>(c, op[NORM_POOL_FWD_MEAN]),
+                                      P<const float>(c, op[NORM_POOL_FWD_VAR]), (float)as_double(op[NORM_POOL_FWD_EPS]),
+                                      P<const float>(c, op[NORM_POOL_FWD_GAMMA]), P<const float>(c, op[NORM_POOL_FWD_BETA]),
+                                      (int)op[NORM_POOL_FWD_ACT], reinterpret_cast<const int*>(m[MAP_NBR]), m[MAP_N_OUT],
+                                      P<float>(c, op[NORM_POOL_FWD_OUT]), P<int>(c, op[NORM_POOL_FWD_ARG]), P<float>(c, op[NORM_POOL_FWD_Y]),
+                                      P<int>(c, op[NORM_POOL_FWD_PARENT]), st);
     }
-    case OP_POOL_NORM_BWD: {  // x, g_pool, arg, parent, seg, n(dim), C, nseg(dim), mean, var, cnt, eps, gamma, beta, act, gx, sums
-      const int64_t n = c.dims[op[7]];
-      const int C = (int)op[8], nseg = (int)c.dims[op[9]];
+    case OP_POOL_NORM_BWD: {
+      const int64_t n = c.dims[op[POOL_NORM_BWD_N]];
+      const int C = (int)op[POOL_NORM_BWD_C], nseg = (int)c.dims[op[POOL_NORM_BWD_NSEG]];
       if (!want_ws(c, s, fc_maxpool8_norm_act_bwd_ws_bytes(n, C, nseg))) return 0;
-      return fc_maxpool8_norm_act_bwd(P<const float>(c, op[2]), P<const float>(c, op[3]), P<const int>(c, op[4]), P<const int>(c, op[5]),
-                                      P<const int>(c, op[6]), op[6] >= 0 ? 4 : 0, n, C, nseg, P<const float>(c, op[10]),
-                                      P<const float>(c, op[11]), P<const float>(c, op[12]), (float)as_double(op[13]),
-                                      P<const float>(c, op[14]), P<const float>(c, op[15]), (int)op[16], P<float>(c, op[17]),
-                                      P<float>(c, op[18]), c.ws[s], c.ws_bytes[s], st);
+      return fc_maxpool8_norm_act_bwd(P<const float>(c, op[POOL_NORM_BWD_X]), P<const float>(c, op[POOL_NORM_BWD_G_POOL]),
+                                      P<const int>(c, op[POOL_NORM_BWD_ARG]), P<const int>(c, op[POOL_NORM_BWD_PARENT]),
+                                      P<const int>(c, op[POOL_NORM_BWD_SEG]), op[POOL_NORM_BWD_SEG] >= 0 ? 4 : 0, n, C, nseg,
+                                      P<const float>(c, op[POOL_NORM_BWD_MEAN]), P<const float>(c, op[POOL_NORM_BWD_VAR]),
+                                      P<const float>(c, op[POOL_NORM_BWD_CNT]), (float)as_double(op[POOL_NORM_BWD_EPS]),
+                                      P<const float>(c, op[POOL_NORM_BWD_GAMMA]), P<const float>(c, op[POOL_NORM_BWD_BETA]),
+                                      (int)op[POOL_NORM_BWD_ACT], P<float>(c, op[POOL_NORM_BWD_GX]), P<float>(c, op[POOL_NORM_BWD_SUMS]),
+                                      c.ws[s], c.ws_bytes[s], st);
     }
-    case OP_INV_ROWS: {  // rows, n(dim), n_inv(dim), inv: inv = -1, inv[rows[i]] = i
+    case OP_INV_ROWS: {
       if (c.dry) return 0;
-      return fc_inverse_rows(P<const int>(c, op[2]), c.dims[op[3]], c.dims[op[4]], P<int>(c, op[5]), st);
+      return fc_inverse_rows(P<const int>(c, op[INV_ROWS_ROWS]), c.dims[op[INV_ROWS_N]], c.dims[op[INV_ROWS_N_INV]], P<int>(c, op[INV_ROWS_INV]), st);
     }
-    case OP_COPY: {  // dst, src, n(dim), C
+    case OP_COPY: {
       if (c.dry) return 0;
-      FC_HIP(hipMemcpyAsync(P<float>(c, op[2]), P<const float>(c, op[3]), sizeof(float) * c.dims[op[4]] * op[5], hipMemcpyDeviceToDevice, st));
+      FC_HIP(hipMemcpyAsync(P<float>(c, op[COPY_DST]), P<const float>(c, op[COPY_SRC]), sizeof(float) * c.dims[op[COPY_N]] * op[COPY_C],
+                            hipMemcpyDeviceToDevice, st));
       return 0;
     }
     default:
@@ -482,7 +501,7 @@ extern "C" {
 int fc_exec_op_words(void) { return OPW; }
 int fc_exec_map_words(void) { return MAPW; }
 
-// Runs operators [op_begin, op_end) of `ops` (HOST array, fc_exec_op_words() int64 per operator; layouts: fcaf3d_amd/executor.py).
+// Runs operators [op_begin, op_end) of `ops` (HOST array, fc_exec_op_words() int64 per operator; layouts: csrc/exec_ops.h).
 // addr / dims / maps: HOST arrays of device addresses, row counts and kernel-map descriptors the operators index.
 // streams / ws / ws_bytes: 3 entries each (0 main, 1 head branch, 2 weight gradients).  A first pass sizes the scratch space of
 // every operator; if a stream's workspace is too small NOTHING is launched, ws_need[3] holds the required sizes and the call

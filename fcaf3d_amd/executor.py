@@ -11,7 +11,7 @@ from step to step.  `NetProgram` walks the module graph ONCE and emits
     normalisation backward, gradient accumulation where a tensor has two consumers), gradients written straight into the flat
     gradient buffer (flat.FlatParams) or a buffer of the same layout;
 
-as rows of int64 (operand layouts: csrc/exec.hip `run_op`).  Operands are indices into three host tables refreshed per step with
+as rows of int64 (the fields of every operator, by name: csrc/exec_ops.h).  Operands are indices into three host tables refreshed per step with
 a few vectorised numpy operations: `addr` (device addresses: arena tensors = base + aligned prefix sum of rows x bytes per row;
 parameters, buffers, weight images: static), `dims` (row counts) and `maps` (KernelMap.desc()).
 
@@ -46,12 +46,29 @@ TRUSTED = None
 # which a plain step never materialises (r7): part of the program cache key
 KEEP_STATE = False
 
-(OP_STEM_FWD, OP_COL_STATS, OP_NORM_FWD, OP_MAXPOOL_FWD, OP_CONV, OP_BN_FWD, OP_UNION_FWD, OP_HEAD_FWD, OP_RECORD, OP_WAIT,
- OP_HEAD_BWD, OP_WGRAD, OP_BN_BWD, OP_NORM_BWD, OP_MAXPOOL_BWD, OP_STEM_WGRAD, OP_GATHER, OP_ADD, OP_SMALL_GRADS,
- OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD,
- OP_INV_ROWS) = range(1, 30)
-# (OP_NORM_FWD, OP_MAXPOOL_FWD, OP_UNION_FWD, OP_NORM_BWD, OP_MAXPOOL_BWD: not emitted since r7 and without a case in csrc/exec.hip; the numbers stay)
-OPW, MAPW = 24, 20
+
+def _layouts():
+    """csrc/exec_ops.h -> ({OP_*, OPW, MAPW, ROW_OP, ROW_STREAM: value}, {opcode: {field: (word, stored as index + 1)}}): operator OP_X's fields are the
+    enum X_<FIELD> ... X_END, a field's name here is <field> in lower case without the _P1 that marks the index + 1 coding"""
+    names, fields = {}, {}
+    for block in L.parse_enums():
+        names.update(block)
+        *members, end = block
+        op = names.get('OP_' + end[:-len('_END')]) if end.endswith('_END') else None
+        if op is not None:
+            fields[op] = {n[len(end) - 3:].lower().removesuffix('_p1'): (block[n], n.endswith('_P1')) for n in members}
+    return {k: v for k, v in names.items() if k.startswith('OP_') or k in ('OPW', 'MAPW', 'ROW_OP', 'ROW_STREAM')}, fields
+
+
+_NAMES, FIELDS = _layouts()
+globals().update(_NAMES)         # OP_STEM_FWD ... OP_INV_ROWS, OPW, MAPW, ROW_OP, ROW_STREAM
+
+
+def word(op, field):
+    """the column of `field` in the rows of operator `op` (program build, tests; nothing per step looks a name up)"""
+    return FIELDS[op][field][0]
+
+
 ALIGN = 256
 S_MAIN, S_HEAD, S_WGRAD = 0, 1, 2
 EV_FORK, EV_HEAD_DONE, EV_W0, EV_W1, EV_WEND, EV_BWD0, EV_HB = 0, 8, 9, 10, 11, 12, 16       # EV_FORK + level, EV_HB + level
@@ -172,10 +189,22 @@ class NetProgram:
         self.grad_refs.append((i, self._goff[id(p)]))
         return i
 
-    def emit(self, lst, *words):
-        w = list(words) + [0] * (OPW - len(words))
-        assert len(w) == OPW, len(w)
-        lst.append(w)
+    def emit(self, lst, op, stream, **fields):
+        """append a row of operator `op`: its fields by name (csrc/exec_ops.h), the others 0"""
+        row = [0] * OPW
+        row[ROW_OP], row[ROW_STREAM] = op, stream
+        self.patch(row, **fields)
+        lst.append(row)
+
+    @staticmethod
+    def patch(row, **fields):
+        """set fields of an emitted row.  A field the header declares ..._P1 takes the plain index (-1: none) and is stored + 1"""
+        layout = FIELDS[row[ROW_OP]]
+        for k, v in fields.items():
+            if k not in layout:
+                raise KeyError(f'operator {row[ROW_OP]} has no field {k!r}')
+            w, p1 = layout[k]
+            row[w] = v + 1 if p1 else v
 
     # ---- r6: amax words of the convolutions' operands (csrc/conv_x6.h "h3": the scale of the two-piece fp16 split) ------------
     # One fc_amax pass per operand TENSOR and stream instead of one per consuming launch: a forward activation's word serves its
@@ -197,7 +226,7 @@ class NetProgram:
     def amax_op(self, lst, stream, x, rows, cols):
         """emit the amax pass of tensor x ((rows, cols) floats) on `stream` -> address index of its word"""
         slot = self.amax_slot()
-        self.emit(lst, OP_AMAX, stream, x, self.D(rows), cols, slot)
+        self.emit(lst, OP_AMAX, stream, x=x, n=self.D(rows), c=cols, slot=slot)
         return slot
 
     # ---- weights: pre-split images of every kernel, incl. the packed head kernel and the generative convolutions' GEMM form; ONE
@@ -258,7 +287,7 @@ class NetProgram:
             gradient slices (one launch); called where a group of layers ends, so that a data-parallel bucket is complete early"""
             n = len(small_rows) - flushed[0]
             if n:
-                self.emit(Bk, OP_SMALL_GRADS, stream, self.DY('small_desc'), 2 * flushed[0], 2 * n)
+                self.emit(Bk, OP_SMALL_GRADS, stream, desc=self.DY('small_desc'), first=2 * flushed[0], count=2 * n)
                 for _, _, _, w_, b_ in small_rows[flushed[0]:]:
                     wrote(w_, b_)
                 flushed[0] = len(small_rows)
@@ -266,9 +295,9 @@ class NetProgram:
 
         def head_wfin(stream):
             lo = 1 if self.tail0 else 0
-            self.emit(Bk, OP_HEAD_WFIN, stream, self.SA(head_part[lo].data_ptr()), self.nl - lo, Cn, 64, n_reg, n_cls,
-                      self.G(nh.centerness_conv.kernel), self.G(nh.reg_conv.kernel), self.G(nh.cls_conv.kernel),
-                      self.SA(bias_part[lo].data_ptr()), self.G(nh.cls_conv.bias))
+            self.emit(Bk, OP_HEAD_WFIN, stream, part=self.SA(head_part[lo].data_ptr()), nl=self.nl - lo, r=Cn, ld=64, n_reg=n_reg, n_cls=n_cls,
+                      g_cent=self.G(nh.centerness_conv.kernel), g_reg=self.G(nh.reg_conv.kernel), g_cls=self.G(nh.cls_conv.kernel),
+                      bias_part=self.SA(bias_part[lo].data_ptr()), g_bias=self.G(nh.cls_conv.bias))
             wrote(nh.centerness_conv.kernel, nh.reg_conv.kernel, nh.cls_conv.kernel, nh.cls_conv.bias)
 
         def wstream(cur):
@@ -278,7 +307,7 @@ class NetProgram:
 
         def flush2(t):
             g2, rows, cols, stream = grad2.pop(t)
-            self.emit(Bk, OP_ADD, stream, grad[t], g2, self.D(rows), cols)
+            self.emit(Bk, OP_ADD, stream, dst=grad[t], src=g2, n=self.D(rows), c=cols)
             grad_src.pop(grad[t], None)          # added to in place: no longer the plain result of the convolution that wrote it
             amax_of.pop(grad[t], None)           # ... nor bounded by its producer's amax word
 
@@ -293,7 +322,7 @@ class NetProgram:
             else:
                 if t in grad2:
                     flush2(t)
-                self.emit(Bk, OP_ADD, stream, grad[t], g, self.D(rows), cols)
+                self.emit(Bk, OP_ADD, stream, dst=grad[t], src=g, n=self.D(rows), c=cols)
                 grad_src.pop(grad[t], None)
                 amax_of.pop(grad[t], None)
 
@@ -302,7 +331,7 @@ class NetProgram:
             the caller adds a second contribution itself -> (gradient, second contribution | None)"""
             if t in head_grads:
                 g, lvl = head_grads.pop(t)
-                self.emit(Bk, OP_WAIT, S_MAIN, EV_HB + lvl)          # the head branch of this level has delivered
+                self.emit(Bk, OP_WAIT, S_MAIN, event=EV_HB + lvl)          # the head branch of this level has delivered
                 for prm in head_written.pop(lvl, ()):
                     self._pready[id(prm)] = max(self._pready[id(prm)], len(Bk))
                 accumulate(t, g, rows, cols, S_MAIN)
@@ -318,12 +347,12 @@ class NetProgram:
                 flush2(t)
             return grad[t]
 
-        def emit_wgrad(cur, *words):
+        def emit_wgrad(cur, **fields):
             if self.wgrad_async:
                 ev = EV_W0 if cur == S_MAIN else EV_W1
-                self.emit(Bk, OP_RECORD, cur, ev)
-                self.emit(Bk, OP_WAIT, S_WGRAD, ev)
-            self.emit(Bk, OP_WGRAD, wstream(cur), *words)
+                self.emit(Bk, OP_RECORD, cur, event=ev)
+                self.emit(Bk, OP_WAIT, S_WGRAD, event=ev)
+            self.emit(Bk, OP_WGRAD, wstream(cur), **fields)
 
         AMAX = Fn.X6 and Fn.split_mode() == 2          # the convolutions scale their operands by their amax words (csrc/conv_x6.h h3)
         amax_f = {}                      # (forward tensor, stream) -> address index of its amax word
@@ -331,7 +360,7 @@ class NetProgram:
         if AMAX:
             # the words the producers fold into start every pass at zero: one fill per direction, its size patched in below
             self.amax_slot()             # (slot 0 doubles as the buffer's base address)
-            self.emit(F, OP_CLEAR, S_MAIN, self.SA(self._amax_buf.data_ptr()), 0)
+            self.emit(F, OP_CLEAR, S_MAIN, dst=self.SA(self._amax_buf.data_ptr()), bytes=0)
 
         def fwd_amax(x, rows, cols, stream):
             if not AMAX:
@@ -351,16 +380,16 @@ class NetProgram:
             y = self.T(rows_out, Cout)
             m = self.M(mname)
             ax = fwd_amax(x, rows_in, Cin, stream)
-            self.emit(F, OP_CONV, stream, x, self.IMG(mod.kernel, False), m, 0, y, -1, Cin, Cout, *([0] * 10), ax + 1)
+            self.emit(F, OP_CONV, stream, x=x, img=self.IMG(mod.kernel, False), map=m, dir=0, out=y, n=-1, cin=Cin, cout=Cout, amax_x=ax)
             producer[y] = (len(F) - 1, rows_out, Cout)
             if tr:
                 def bwd():
                     gy = take(y, rows_out, Cout) if stream == S_MAIN else got(y)
                     gx = self.T(rows_in, Cin, 'b')
                     ag = (amax_of[gy] if gy in amax_of else self.amax_op(Bk, stream, gy, rows_out, Cout)) if AMAX else -1
-                    self.emit(Bk, OP_CONV, stream, gy, self.IMG(mod.kernel, True), m, 1, gx, -1, Cout, Cin, *([0] * 10), ag + 1)
+                    self.emit(Bk, OP_CONV, stream, x=gy, img=self.IMG(mod.kernel, True), map=m, dir=1, out=gx, n=-1, cin=Cout, cout=Cin, amax_x=ag)
                     grad_src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
-                    emit_wgrad(stream, x, gy, m, self.G(mod.kernel), -1, Cin, Cout, ax + 1, ag + 1)
+                    emit_wgrad(stream, x=x, gout=gy, map=m, gw=self.G(mod.kernel), n=-1, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
                     wrote(mod.kernel)
                     accumulate(x, gx, rows_in, Cin, stream)
                 tape.append((stream, bwd))
@@ -371,16 +400,16 @@ class NetProgram:
             index the (Cin, Cout) weight gradient goes to"""
             y = self.T(rows, Cout)
             ax = fwd_amax(x, rows, Cin, stream)
-            self.emit(F, OP_CONV, stream, x, self.IMG(w_tensor, False), -1, 0, y, self.D(rows), Cin, Cout, *([0] * 10), ax + 1)
+            self.emit(F, OP_CONV, stream, x=x, img=self.IMG(w_tensor, False), map=-1, dir=0, out=y, n=self.D(rows), cin=Cin, cout=Cout, amax_x=ax)
             producer[y] = (len(F) - 1, rows, Cout)
             if tr:
                 def bwd():
                     gy = take(y, rows, Cout) if stream == S_MAIN else got(y)
                     gx = self.T(rows, Cin, 'b')
                     ag = (amax_of[gy] if gy in amax_of else self.amax_op(Bk, stream, gy, rows, Cout)) if AMAX else -1
-                    self.emit(Bk, OP_CONV, stream, gy, self.IMG(w_tensor, True), -1, 1, gx, self.D(rows), Cout, Cin, *([0] * 10), ag + 1)
+                    self.emit(Bk, OP_CONV, stream, x=gy, img=self.IMG(w_tensor, True), map=-1, dir=1, out=gx, n=self.D(rows), cin=Cout, cout=Cin, amax_x=ag)
                     grad_src[gx] = (len(Bk) - 1, rows, Cin, stream)
-                    emit_wgrad(stream, x, gy, -1, gw_dst, self.D(rows), Cin, Cout, ax + 1, ag + 1)
+                    emit_wgrad(stream, x=x, gout=gy, map=-1, gw=gw_dst, n=self.D(rows), cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
                     if w_tensor is self.packed:
                         head_wgrads[0] += 1
                         if head_wgrads[0] == self.nl - (1 if self.tail0 else 0) and self.wgrad_async:
@@ -402,7 +431,7 @@ class NetProgram:
             mean, var, cnt = (self.T('one', C), self.T('one', C), self.T('one', 1)) if tr else (-1, -1, -1)
             if act == relu:
                 self.relu_outs.append((y, rows, C))
-            prod_word, groups = 0, 1
+            prod, groups = -1, 1
             if tr and Fn.BN_FUSE and x in producer:
                 # the convolution that wrote x leaves the column sums of x and x^2 per row block in its epilogue (conv_x6.h /
                 # k_sum_*_stats) and this BatchNorm takes its batch statistics from them: no statistics pass over x
@@ -410,14 +439,16 @@ class NetProgram:
                 groups = pcols // C
                 assert pcols == groups * C and groups in (1, 8)
                 # table: [blocks][2][pcols] floats, blocks <= rows / 16 + 1 (conv.hip fc_stat_rb)
-                F[pi][10] = self.T(prows, pcols // 8, extra=8 * pcols + 256) + 1
-                prod_word = pi + 1
+                self.patch(F[pi], stats=self.T(prows, pcols // 8, extra=8 * pcols + 256))
+                prod = pi
             ay = -1
             if AMAX:                     # the apply kernel folds max |y| into this word: a convolution gathering y needs no amax pass
                 ay = amax_of[y] = self.amax_slot()
-            self.emit(F, OP_BN_FWD, stream, x, self.D(rows), C, _f(b.eps), self.S(b.weight), self.S(b.bias), -1 if res is None else res, act,
-                      _f(b.momentum), y, mean, var, cnt, self.S(b.running_mean), self.S(b.running_var), self.S(b.num_batches_tracked),
-                      1 if tr else 0, prod_word, groups, ay + 1, *((add[0] + 1, add[1] + 1) if add is not None else (0, 0)))
+            add_inv, add_src = add if add is not None else (-1, -1)
+            self.emit(F, OP_BN_FWD, stream, x=x, n=self.D(rows), c=C, eps=_f(b.eps), gamma=self.S(b.weight), beta=self.S(b.bias),
+                      res=-1 if res is None else res, act=act, momentum=_f(b.momentum), y=y, mean=mean, var=var, cnt=cnt,
+                      rmean=self.S(b.running_mean), rvar=self.S(b.running_var), nbt=self.S(b.num_batches_tracked), train=1 if tr else 0,
+                      producer=prod, groups=groups, amax_y=ay, add_inv=add_inv, add_src=add_src)
             if tr:
                 sums = torch.zeros((2, C), dtype=torch.float32, device=self.dev)
                 si = self.S(sums)
@@ -427,7 +458,7 @@ class NetProgram:
                     gy, gy2 = take(y, rows, C, pair=True) if stream == S_MAIN else (got(y), None)
                     gx = self.T(rows, C, 'b')
                     gres = self.T(rows, C, 'b') if res is not None else -1
-                    prod = 0
+                    prod = -1
                     # the LAST contribution to gy is the result of a backward-data convolution (and at most one other contribution
                     # arrived before it): that launch leaves this layer's two reductions (sum g', sum g' xhat) in its epilogue
                     # (fc_conv_fwd_bn_bwd_stats; `add` = the earlier contribution, bn_y = this layer's output where act' needs it)
@@ -436,15 +467,16 @@ class NetProgram:
                     src = grad_src.get(last)
                     if Fn.BN_FUSE and src is not None and src[3] == stream and src[1:3] == (rows, C):
                         pi = src[0]
-                        Bk[pi][10] = self.T(rows, C // 8, 'b', extra=8 * C + 256) + 1
-                        Bk[pi][11:20] = [x + 1, mean, var, self.S(b.weight), self.S(b.bias), _f(b.eps), act,
-                                         0 if first is None else first + 1, 0 if res is None else y + 1]
-                        prod = pi + 1
+                        self.patch(Bk[pi], stats=self.T(rows, C // 8, 'b', extra=8 * C + 256), bn_x=x, bn_mean=mean, bn_var=var,
+                                   bn_gamma=self.S(b.weight), bn_beta=self.S(b.bias), bn_eps=_f(b.eps), bn_act=act,
+                                   bn_add=-1 if first is None else first, bn_y=-1 if res is None else y)
+                        prod = pi
                     agx = -1
                     if AMAX:
                         agx = amax_of[gx] = self.amax_slot()
-                    self.emit(Bk, OP_BN_BWD, stream, x, y if res is not None else -1, gy, self.D(rows), C, mean, var, cnt, _f(b.eps),
-                              self.S(b.weight), self.S(b.bias), act, gx, gres, si, 0 if gy2 is None else gy2 + 1, prod, agx + 1)
+                    self.emit(Bk, OP_BN_BWD, stream, x=x, y=y if res is not None else -1, gy=gy, n=self.D(rows), c=C, mean=mean, var=var,
+                              cnt=cnt, eps=_f(b.eps), gamma=self.S(b.weight), beta=self.S(b.bias), act=act, gx=gx, gres=gres, sums=si,
+                              gy2=-1 if gy2 is None else gy2, producer=prod, amax_gx=agx)
                     accumulate(x, gx, rows, C, stream)
                     if res is not None:
                         accumulate(res, gres, rows, C, stream)
@@ -457,9 +489,9 @@ class NetProgram:
         stem, inorm = bb.conv1[0], bb.conv1[1]
         t_stem = self.T('n1', 64)
         col = self.T('n1', 84) if tr else -1
-        self.emit(F, OP_STEM_FWD, S_MAIN, x0, self.S(stem.kernel), self.M('stem'), t_stem, col)
+        self.emit(F, OP_STEM_FWD, S_MAIN, x=x0, w=self.S(stem.kernel), map=self.M('stem'), out=t_stem, col=col)
         mean_in, var_in, cnt_in = self.T('B', 64), self.T('B', 64), self.T('B', 1)
-        self.emit(F, OP_COL_STATS, S_MAIN, t_stem, seg1, self.D('n1'), 64, self.D('B'), mean_in, var_in, cnt_in)
+        self.emit(F, OP_COL_STATS, S_MAIN, x=t_stem, seg=seg1, n=self.D('n1'), c=64, nseg=self.D('B'), mean=mean_in, var=var_in, cnt=cnt_in)
         # instance norm + ReLU + max pool in ONE pass (norm.hip k_norm_act_maxpool8_fwd, bit for bit the two operators): the
         # normalised tensor's only consumer is the pool, and the backward pass recomputes act' from t_stem — it is stored only for
         # `decisions` (keep_state)
@@ -472,8 +504,8 @@ class NetProgram:
         if AMAX:
             ap = amax_of[t_pool] = self.amax_slot()
         pool_parent = self.T('n1', 1) if tr else -1       # child row -> pooled row (4 bytes per row), for the backward pass
-        self.emit(F, OP_NORM_POOL_FWD, S_MAIN, t_stem, seg1, 64, mean_in, var_in, _f(inorm.eps), self.S(inorm.weight), self.S(inorm.bias),
-                  relu, self.M('pool'), t_pool, arg, t_in, ap + 1, pool_parent)
+        self.emit(F, OP_NORM_POOL_FWD, S_MAIN, x=t_stem, seg=seg1, c=64, mean=mean_in, var=var_in, eps=_f(inorm.eps), gamma=self.S(inorm.weight),
+                  beta=self.S(inorm.bias), act=relu, map=self.M('pool'), out=t_pool, arg=arg, y=t_in, amax_out=ap, parent=pool_parent)
         if tr:
             in_sums = self.T('B', 2 * 64, 'b')
             self.in_sums = in_sums
@@ -485,12 +517,13 @@ class NetProgram:
                 # pool backward + instance-norm backward without the scattered gradient in between: the normalisation backward's
                 # kernels read row r's gradient as g_pool[parent[r]] where arg[parent[r]] == r, else 0 (norm.hip pool_parent) — the sums
                 # in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
-                self.emit(Bk, OP_POOL_NORM_BWD, S_MAIN, t_stem, g_pool, arg, pool_parent, seg1, self.D('n1'), 64, self.D('B'), mean_in,
-                          var_in, cnt_in, _f(inorm.eps), self.S(inorm.weight), self.S(inorm.bias), relu, g_stem, in_sums)
+                self.emit(Bk, OP_POOL_NORM_BWD, S_MAIN, x=t_stem, g_pool=g_pool, arg=arg, parent=pool_parent, seg=seg1, n=self.D('n1'), c=64,
+                          nseg=self.D('B'), mean=mean_in, var=var_in, cnt=cnt_in, eps=_f(inorm.eps), gamma=self.S(inorm.weight),
+                          beta=self.S(inorm.bias), act=relu, gx=g_stem, sums=in_sums)
                 if self.wgrad_async:
-                    self.emit(Bk, OP_RECORD, S_MAIN, EV_W0)
-                    self.emit(Bk, OP_WAIT, S_WGRAD, EV_W0)
-                self.emit(Bk, OP_STEM_WGRAD, wstream(S_MAIN), col, g_stem, self.M('stem'), self.G(stem.kernel))
+                    self.emit(Bk, OP_RECORD, S_MAIN, event=EV_W0)
+                    self.emit(Bk, OP_WAIT, S_WGRAD, event=EV_W0)
+                self.emit(Bk, OP_STEM_WGRAD, wstream(S_MAIN), col=col, gout=g_stem, map=self.M('stem'), gw=self.G(stem.kernel))
                 wrote(stem.kernel)
             tape.append((S_MAIN, bwd_stem))
         cur, cur_rows, cur_C = t_pool, 'n2', 64
@@ -544,7 +577,7 @@ class NetProgram:
                 gw_i = self.S(gw_tmp)
                 if tr:
                     def bwd_perm(gw_i=gw_i, mod=up[0], Cin=x_C, Ci=Ci):
-                        self.emit(Bk, OP_PERMUTE_GENT, wstream(S_MAIN), gw_i, self.G(mod.kernel), Cin, Ci)
+                        self.emit(Bk, OP_PERMUTE_GENT, wstream(S_MAIN), src=gw_i, dst=self.G(mod.kernel), cin=Cin, cout=Ci)
                         wrote(mod.kernel)
                         flush_small(S_MAIN)                     # ... and after every neck level's up-block
                     tape.append((S_MAIN, bwd_perm))          # forward order: BEFORE the GEMM, so the reversed walk reaches it after
@@ -558,7 +591,7 @@ class NetProgram:
                 fb, fb_rows, fb_C = levels[i]
                 rows_i = self.DY(f'rows{i}')
                 inv_i = self.T(g_rows, 1)
-                self.emit(F, OP_INV_ROWS, S_MAIN, rows_i, self.D(fb_rows), self.D(g_rows), inv_i)
+                self.emit(F, OP_INV_ROWS, S_MAIN, rows=rows_i, n=self.D(fb_rows), n_inv=self.D(g_rows), inv=inv_i)
                 u = bn(t, up[4], elu, g_rows, add=(inv_i, fb))
                 if tr:
                     def bwd_union(u=u, fb=fb, fb_rows=fb_rows, rows_i=rows_i, g_rows=g_rows, Ci=Ci):
@@ -566,7 +599,7 @@ class NetProgram:
                         # reversed walk, takes the gradient of u as its own
                         gu = take(u, g_rows, Ci)
                         gfb = self.T(fb_rows, Ci, 'b')
-                        self.emit(Bk, OP_GATHER, S_MAIN, gu, rows_i, self.D(fb_rows), Ci, gfb)
+                        self.emit(Bk, OP_GATHER, S_MAIN, src=gu, idx=rows_i, n=self.D(fb_rows), c=Ci, dst=gfb)
                         accumulate(fb, gfb, fb_rows, Ci, S_MAIN)
                     tape.append((S_MAIN, bwd_union))
                 x, x_rows, x_C = u, g_rows, Ci
@@ -581,8 +614,8 @@ class NetProgram:
             # out_block_i + forward_single: on the head stream for i > 0
             hs = S_HEAD if (self.head_overlap and i > 0) else S_MAIN
             if hs == S_HEAD:
-                self.emit(F, OP_RECORD, S_MAIN, EV_FORK + i)
-                self.emit(F, OP_WAIT, S_HEAD, EV_FORK + i)
+                self.emit(F, OP_RECORD, S_MAIN, event=EV_FORK + i)
+                self.emit(F, OP_WAIT, S_HEAD, event=EV_FORK + i)
             ob = getattr(nh, f'out_block_{i}')
             o = conv(x, ob[0], kname, x_rows, x_rows, stream=hs)
             o = bn(o, ob[1], elu, x_rows, stream=hs)
@@ -590,7 +623,8 @@ class NetProgram:
             y = gemm(o, self.packed, x_rows, Cn, 64, gw_head, stream=hs)
             off = f'off{i}'
             outs = [self.AL(cent_all, off, 1), self.AL(bbox_all, off, n_reg), self.AL(cls_all, off, n_cls), self.AL(cmax_all, off, 1)]
-            self.emit(F, OP_HEAD_FWD, hs, y, 64, self.S(nh.cls_conv.bias), self.S(nh.scales[i].scale), self.D(x_rows), n_reg, n_cls, *outs)
+            self.emit(F, OP_HEAD_FWD, hs, y=y, ld=64, bias=self.S(nh.cls_conv.bias), scale=self.S(nh.scales[i].scale), n=self.D(x_rows), n_reg=n_reg,
+                      n_cls=n_cls, cent=outs[0], bbox=outs[1], cls=outs[2], cmax=outs[3])
             if tr:
                 def bwd_head(y=y, outs=outs, off=off, hs=hs, rows=x_rows, lvl=i):
                     gy = self.T(rows, 64, 'b')
@@ -601,29 +635,30 @@ class NetProgram:
                     agy = -1
                     if AMAX:                 # the kernel folds max |gy| for the backward-data GEMM behind it
                         agy = amax_of[gy] = self.amax_slot()
-                    self.emit(Bk, OP_HEAD_BWD, hs, y, 64, self.S(nh.scales[lvl].scale), outs[1], gin[0], gin[1], gin[2], self.D(rows), n_reg,
-                              n_cls, gy, -1, self.G(nh.scales[lvl].scale), self.SA(bias_part[lvl].data_ptr()), agy + 1)
+                    self.emit(Bk, OP_HEAD_BWD, hs, y=y, ld=64, scale=self.S(nh.scales[lvl].scale), bbox=outs[1], g_cent=gin[0], g_bbox=gin[1],
+                              g_cls=gin[2], n=self.D(rows), n_reg=n_reg, n_cls=n_cls, gy=gy, gs_row=-1, g_scale=self.G(nh.scales[lvl].scale),
+                              bias_part=self.SA(bias_part[lvl].data_ptr()), amax_gy=agy)
                     wrote(nh.scales[lvl].scale)
                     grad[y] = gy
                 tape.append((hs, bwd_head))
                 if hs == S_HEAD:
                     tape.append((S_HEAD, ('join', x, x_rows, x_C, i)))      # marker: where this level's head branch begins in reverse
         if self.head_overlap:
-            self.emit(F, OP_RECORD, S_HEAD, EV_HEAD_DONE)
-            self.emit(F, OP_WAIT, S_MAIN, EV_HEAD_DONE)
+            self.emit(F, OP_RECORD, S_HEAD, event=EV_HEAD_DONE)
+            self.emit(F, OP_WAIT, S_MAIN, event=EV_HEAD_DONE)
         # ---- backward program -------------------------------------------------------------------------------------------
         if AMAX:
             n_fwd_slots = self._amax_used
-            F[0][3] = self.AMAX_SLOT_BYTES * n_fwd_slots                     # the forward pass clears its own words; they stay valid through the backward pass
+            self.patch(F[0], bytes=self.AMAX_SLOT_BYTES * n_fwd_slots)       # the forward pass clears its own words; they stay valid through the backward pass
             if tr:
-                self.emit(Bk, OP_CLEAR, S_MAIN, self.SA(self._amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * n_fwd_slots), 0)
+                self.emit(Bk, OP_CLEAR, S_MAIN, dst=self.SA(self._amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * n_fwd_slots), bytes=0)
                 clear_b = len(Bk) - 1
         if tr:
             if self.head_overlap:
                 # the head branches depend on the loss gradients only: their backward is enqueued first, on the head stream, finest
                 # forked level first (the main chain needs that one first); each leaves the gradient of its neck tensor behind an event
-                self.emit(Bk, OP_RECORD, S_MAIN, EV_BWD0)          # the loss gradients are ready on the caller's stream
-                self.emit(Bk, OP_WAIT, S_HEAD, EV_BWD0)
+                self.emit(Bk, OP_RECORD, S_MAIN, event=EV_BWD0)          # the loss gradients are ready on the caller's stream
+                self.emit(Bk, OP_WAIT, S_HEAD, event=EV_BWD0)
                 branches, cur_b = [], None
                 for s, e in reversed(tape):
                     if s != S_HEAD:
@@ -641,7 +676,7 @@ class NetProgram:
                         e()
                     flush_small(S_HEAD)                    # this branch's normalisation layer
                     head_lvl[0] = None
-                    self.emit(Bk, OP_RECORD, S_HEAD, EV_HB + lvl)
+                    self.emit(Bk, OP_RECORD, S_HEAD, event=EV_HB + lvl)
                     head_grads[xt] = (got(xt), lvl)
                     grad.pop(xt)
             for s, e in reversed(tape):
@@ -660,10 +695,10 @@ class NetProgram:
                 missing = [n for n in missing if not (n.startswith('neck_with_head.out_block_0.') or n == 'neck_with_head.scales.0.scale')]
             assert not missing, missing
             if self.wgrad_async:
-                self.emit(Bk, OP_RECORD, S_WGRAD, EV_WEND)
-                self.emit(Bk, OP_WAIT, S_MAIN, EV_WEND)
+                self.emit(Bk, OP_RECORD, S_WGRAD, event=EV_WEND)
+                self.emit(Bk, OP_WAIT, S_MAIN, event=EV_WEND)
             if AMAX:
-                Bk[clear_b][3] = self.AMAX_SLOT_BYTES * (self._amax_used - n_fwd_slots)
+                self.patch(Bk[clear_b], bytes=self.AMAX_SLOT_BYTES * (self._amax_used - n_fwd_slots))
 
     # ---- per-step tables ---------------------------------------------------------------------------------------------------
     def _finalise(self):
@@ -684,9 +719,9 @@ class NetProgram:
         self._ws = [None, None, None]
         self._need = np.zeros(3, dtype=np.int64)
         self._cfg = np.array([Fn.BN_SMALL_ELEMS, Fn.FLAGS, 0, 0], dtype=np.int64)
-        self.n_conv_f = int((self.ops_f[:, 0] == OP_CONV).sum())
-        self.n_conv_b = int((self.ops_b[:, 0] == OP_CONV).sum()) if len(self.ops_b) else 0
-        self.n_amax = int((self.ops_f[:, 0] == OP_AMAX).sum()) + (int((self.ops_b[:, 0] == OP_AMAX).sum()) if len(self.ops_b) else 0)
+        self.n_conv_f = int((self.ops_f[:, ROW_OP] == OP_CONV).sum())
+        self.n_conv_b = int((self.ops_b[:, ROW_OP] == OP_CONV).sum()) if len(self.ops_b) else 0
+        self.n_amax = int((self.ops_f[:, ROW_OP] == OP_AMAX).sum()) + (int((self.ops_b[:, ROW_OP] == OP_AMAX).sum()) if len(self.ops_b) else 0)
         self._anchor = torch.zeros(1, device=self.dev, requires_grad=True)
         if self.training:
             # small-gradient descriptor template: (src, dst, C, nseg, stride, 0, 0, 0) per (bias, weight) of every normalisation layer

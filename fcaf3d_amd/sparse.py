@@ -112,6 +112,8 @@ SORT_MIN_ROWS = 8192
 # (r6, three-product kernels: 8 192 — the 14.7k-row level on its mask-sorted table — 462.9 scenes/s against 456.1 at 16 384 and 452.5 at
 # 2 048, same box; the six-product kernels of r3-r5 were level at 16 384 / 8 192: profiles/r5_notes.md section 7)
 PAIR_CONV_ROWS = 8192
+# the words of a kernel-map descriptor (KernelMap.desc): MAPW, MAP_*, PAIR_* of csrc/exec_ops.h, the text csrc/exec.hip compiles
+globals().update({k: v for block in L.parse_enums() for k, v in block.items() if k.startswith(('MAPW', 'MAP_', 'PAIR_'))})
 _offs_cache = {}
 
 
@@ -245,7 +247,7 @@ class KernelMap(_Lazy):
                 self.sorted_bwd()
 
     def desc(self, conv=True, backward=True):
-        """int64 descriptor of this map for the native executor (csrc/exec.hip, MAPW words): sizes, the tables the
+        """int64 descriptor of this map for the native executor (MAP_* of csrc/exec_ops.h): sizes, the tables the
         convolution routes of functional._SparseConv would pick (built now if they are not yet: the same lazy tables, so a
         planned step finds them prefetched) and the route bits.  conv=False: the plain table only (stem, pooling)."""
         key = (conv, backward)
@@ -254,31 +256,35 @@ class KernelMap(_Lazy):
             return d
         if not hasattr(self, '_desc'):
             self._desc = {}
-        d = np.zeros(20, dtype=np.int64)
-        d[0], d[1], d[2], d[3] = self.n_in, self.n_out, self.K, self.nbr.data_ptr()
+        d = np.zeros(MAPW, dtype=np.int64)
+
+        def put_pairs(group, lists, tiles=None):
+            for k, t in zip((PAIR_IN, PAIR_OUT, PAIR_POS, PAIR_CNT), lists):
+                d[group + k] = t.data_ptr()
+            if tiles is not None:
+                d[group + PAIR_TILES] = tiles
+
+        def put_table(tab_word, idx_word, tab, idx):
+            d[tab_word], d[idx_word] = tab.data_ptr(), (idx.data_ptr() if idx is not None else 0)
+        d[MAP_N_IN], d[MAP_N_OUT], d[MAP_K], d[MAP_NBR] = self.n_in, self.n_out, self.K, self.nbr.data_ptr()
         if conv:
             flags = 0
             if self.use_pairs and self.n_out <= PAIR_CONV_ROWS:
-                pi, po, pos, cnt = self.pairs()
-                d[9:14] = (pi.data_ptr(), po.data_ptr(), pos.data_ptr(), cnt.data_ptr(), self.pair_tiles())
-                flags |= 1
+                put_pairs(MAP_PAIRS, self.pairs(), self.pair_tiles())
+                flags |= MAP_ROUTE_FWD_PAIRS
             else:
-                tab, idx = self.sorted_fwd()
-                d[5], d[6] = tab.data_ptr(), (idx.data_ptr() if idx is not None else 0)
+                put_table(MAP_FWD_TAB, MAP_FWD_IDX, *self.sorted_fwd())
             if backward:
-                d[4] = self.nbr_t.data_ptr()
+                d[MAP_NBR_T] = self.nbr_t.data_ptr()
                 if self.use_pairs:
-                    pi, po, pos, cnt = self.pairs()
-                    d[9:13] = (pi.data_ptr(), po.data_ptr(), pos.data_ptr(), cnt.data_ptr())
-                    flags |= 4
+                    put_pairs(MAP_PAIRS, self.pairs())
+                    flags |= MAP_ROUTE_WGRAD_PAIRS
                 if self.use_pairs and self.n_in <= PAIR_CONV_ROWS:
-                    pi, po, pos, cnt = self.pairs_t()
-                    d[14:19] = (pi.data_ptr(), po.data_ptr(), pos.data_ptr(), cnt.data_ptr(), self.pair_tiles(transposed=True))
-                    flags |= 2
+                    put_pairs(MAP_PAIRS_T, self.pairs_t(), self.pair_tiles(transposed=True))
+                    flags |= MAP_ROUTE_BWD_PAIRS
                 else:
-                    tab, idx = self.sorted_bwd()
-                    d[7], d[8] = tab.data_ptr(), (idx.data_ptr() if idx is not None else 0)
-            d[19] = flags
+                    put_table(MAP_BWD_TAB, MAP_BWD_IDX, *self.sorted_bwd())
+            d[MAP_FLAGS] = flags
         self._desc[key] = d
         return d
 

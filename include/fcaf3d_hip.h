@@ -609,7 +609,7 @@ int fc_debug_set_h3r(int mode);
  * Fcaf3DNeckWithHead.forward, fcaf3d_neck_with_head.py:94-108) and torch.autograd's backward over it, as a STATIC list of
  * operators walked natively: every operator is one of the entry points above with operands taken from host tables of device
  * addresses (`addr`), row counts (`dims`) and kernel-map descriptors (`maps`, fc_exec_map_words() int64 each) that the caller
- * refreshes per step; `ops` holds fc_exec_op_words() int64 per operator (layouts: fcaf3d_amd/executor.py, csrc/exec.hip).
+ * refreshes per step; `ops` holds fc_exec_op_words() int64 per operator (layouts: fcaf3d_amd/csrc/exec_ops.h).
  * Operators [op_begin, op_end) run on streams[0] (caller's), streams[1] (head branch of the neck), streams[2] (weight
  * gradients), ordered by library-owned events.  ws / ws_bytes: one scratch buffer per stream; a sizing pass runs first: if a
  * buffer is too small NOTHING is launched, ws_need[3] receives the sizes and the call returns -2.

@@ -2,6 +2,8 @@
 structure checks of what fc_exec (csrc/exec.hip) will walk: operand indices in range, every trainable tensor has a place its
 gradient is written to, forward / backward operator counts follow the model (the numerics are the GPU tests' business:
 tests/test_gpu_exec.py compares the executor with the per-operator path bit for bit)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -9,6 +11,8 @@ import torch
 import fcaf3d_amd as fa
 from fcaf3d_amd import executor as E
 from fcaf3d_amd import nn as MEnn
+
+OP, STREAM = E.ROW_OP, E.ROW_STREAM        # columns of an operator row: these two, then E.word(operator, field) (csrc/exec_ops.h)
 
 
 def _model(levels=4, name='fcaf3d_scannet-3d-18class'):
@@ -33,9 +37,9 @@ def test_training_program_structure(levels, wgrad_async, head_overlap):
     assert p.n_conv_f == n_conv + n_gemm
     assert p.n_conv_b == n_conv + n_gemm              # one backward-data launch per forward launch (the stem's input needs none)
     f, b = p.ops_f, p.ops_b
-    assert int((b[:, 0] == E.OP_WGRAD).sum()) == n_conv + n_gemm and int((b[:, 0] == E.OP_STEM_WGRAD).sum()) == 1
+    assert int((b[:, OP] == E.OP_WGRAD).sum()) == n_conv + n_gemm and int((b[:, OP] == E.OP_STEM_WGRAD).sum()) == 1
     n_bn = len([m for m in det.modules() if isinstance(m, MEnn.MinkowskiBatchNorm)])
-    assert int((f[:, 0] == E.OP_BN_FWD).sum()) == n_bn == int((b[:, 0] == E.OP_BN_BWD).sum())
+    assert int((f[:, OP] == E.OP_BN_FWD).sum()) == n_bn == int((b[:, OP] == E.OP_BN_BWD).sum())
     # every parameter that requires a gradient is written by some operator (or by the head's bias / scale reductions)
     nh = det.neck_with_head
     direct = {id(nh.cls_conv.bias)} | {id(s.scale) for s in nh.scales}
@@ -44,19 +48,19 @@ def test_training_program_structure(levels, wgrad_async, head_overlap):
         assert id(prm) in direct or p._goff[id(prm)] in reached, 'a parameter has no gradient destination'
     # streams and events: cross-stream operators only in the overlapped program, every wait has its record
     for ops in (f, b):
-        assert set(np.unique(ops[:, 1])) <= ({0, 1, 2} if (wgrad_async or head_overlap) and levels > 1 or wgrad_async else {0})
-        rec = set(ops[ops[:, 0] == E.OP_RECORD][:, 2])
-        assert set(ops[ops[:, 0] == E.OP_WAIT][:, 2]) <= rec
+        assert set(np.unique(ops[:, STREAM])) <= ({0, 1, 2} if (wgrad_async or head_overlap) and levels > 1 or wgrad_async else {0})
+        rec = set(ops[ops[:, OP] == E.OP_RECORD][:, E.word(E.OP_RECORD, 'event')])
+        assert set(ops[ops[:, OP] == E.OP_WAIT][:, E.word(E.OP_WAIT, 'event')]) <= rec
     if not (wgrad_async or head_overlap):
-        assert not (f[:, 0] == E.OP_RECORD).any() and not (b[:, 0] == E.OP_RECORD).any()
+        assert not (f[:, OP] == E.OP_RECORD).any() and not (b[:, OP] == E.OP_RECORD).any()
 
 
 def test_inference_program_has_no_backward_and_no_saved_statistics():
     det = _model(4).eval()
     p = E.NetProgram(det, False, False, True)
     assert len(p.ops_b) == 0 and not p.arena['b']
-    bn = p.ops_f[p.ops_f[:, 0] == E.OP_BN_FWD]
-    assert (bn[:, 18] == 0).all() and (bn[:, 12] == -1).all()          # eval mode: running statistics, nothing saved
+    bn = p.ops_f[p.ops_f[:, OP] == E.OP_BN_FWD]
+    assert (bn[:, E.word(E.OP_BN_FWD, 'train')] == 0).all() and (bn[:, E.word(E.OP_BN_FWD, 'mean')] == -1).all()          # eval mode: running statistics, nothing saved
 
 
 def test_bottleneck_and_wide_heads_fall_back():
@@ -80,38 +84,43 @@ def test_batchnorm_fusions_are_wired_consistently():
     BatchNorm (gy2) or added by OP_ADD, never both; nothing is linked when FC_BN_FUSE is off."""
     import fcaf3d_amd.functional as Fn
     det = _model(4)
+    CV, BF, BB = (functools.partial(E.word, op) for op in (E.OP_CONV, E.OP_BN_FWD, E.OP_BN_BWD))
     for wgrad_async, head_overlap in ((True, True), (False, False)):
         p = E.NetProgram(det, True, wgrad_async, head_overlap)
         f, b = p.ops_f, p.ops_b
-        bn_f = f[f[:, 0] == E.OP_BN_FWD]
-        assert (bn_f[:, 19] > 0).all(), 'every training-mode BatchNorm takes its statistics from a producer'
+        bn_f = f[f[:, OP] == E.OP_BN_FWD]
+        assert (bn_f[:, BF('producer')] > 0).all(), 'every training-mode BatchNorm takes its statistics from a producer'
         for row in bn_f:
-            prod = f[row[19] - 1]
-            assert prod[0] == E.OP_CONV and prod[5] == 0 and prod[10] > 0 and prod[6] == row[2], 'the producer wrote the BatchNorm input'
-            assert prod[9] == row[4] * row[20] and row[20] in (1, 8)       # columns = groups x channels
-        assert int(((f[:, 0] == E.OP_CONV) & (f[:, 10] > 0)).sum()) == len(bn_f)
-        bn_b = b[b[:, 0] == E.OP_BN_BWD]
-        linked = bn_b[bn_b[:, 18] > 0]
+            prod = f[row[BF('producer')] - 1]
+            assert prod[OP] == E.OP_CONV and prod[CV('dir')] == 0 and prod[CV('stats')] > 0 and prod[CV('out')] == row[BF('x')], \
+                'the producer wrote the BatchNorm input'
+            assert prod[CV('cout')] == row[BF('c')] * row[BF('groups')] and row[BF('groups')] in (1, 8)       # columns = groups x channels
+        assert int(((f[:, OP] == E.OP_CONV) & (f[:, CV('stats')] > 0)).sum()) == len(bn_f)
+        bn_b = b[b[:, OP] == E.OP_BN_BWD]
+        linked = bn_b[bn_b[:, BB('producer')] > 0]
         assert len(linked) >= 36 and len(bn_b) == len(bn_f)
         for row in linked:
-            prod = b[row[18] - 1]
-            assert prod[0] == E.OP_CONV and prod[5] == 1 and prod[10] > 0
-            assert prod[11] - 1 == row[2] and prod[12] == row[7] and prod[13] == row[8] and prod[9] == row[6]     # layer input, mean, var, channels
-            last = row[17] - 1 if row[17] > 0 else row[4]                # the contribution that arrived last = the producer's result
-            assert prod[6] == last
-            if row[17] > 0:
-                assert prod[18] - 1 == row[4], 'the earlier contribution rides along as `add`'
-            assert (prod[19] > 0) == (row[3] >= 0), "act' from the output exactly where the layer had a residual"
+            prod = b[row[BB('producer')] - 1]
+            assert prod[OP] == E.OP_CONV and prod[CV('dir')] == 1 and prod[CV('stats')] > 0
+            assert prod[CV('bn_x')] - 1 == row[BB('x')] and prod[CV('bn_mean')] == row[BB('mean')] and prod[CV('bn_var')] == row[BB('var')] \
+                and prod[CV('cout')] == row[BB('c')]                         # layer input, mean, var, channels
+            # the contribution that arrived last = the producer's result
+            last = row[BB('gy2')] - 1 if row[BB('gy2')] > 0 else row[BB('gy')]
+            assert prod[CV('out')] == last
+            if row[BB('gy2')] > 0:
+                assert prod[CV('bn_add')] - 1 == row[BB('gy')], 'the earlier contribution rides along as `add`'
+            assert (prod[CV('bn_y')] > 0) == (row[BB('y')] >= 0), "act' from the output exactly where the layer had a residual"
         # stream order: a linked producer precedes its BatchNorm and sits on the same stream
         idx = {tuple(r): i for i, r in enumerate(map(tuple, b))}
         for row in linked:
-            assert row[18] - 1 < idx[tuple(row)] and b[row[18] - 1][1] == row[1]
+            assert row[BB('producer')] - 1 < idx[tuple(row)] and b[row[BB('producer')] - 1][STREAM] == row[STREAM]
     Fn.BN_FUSE = False
     try:
         p0 = E.NetProgram(det, True, True, True)
-        assert not (p0.ops_f[:, 10][p0.ops_f[:, 0] == E.OP_CONV] > 0).any() and not (p0.ops_f[:, 19][p0.ops_f[:, 0] == E.OP_BN_FWD] > 0).any()
-        bb = p0.ops_b[p0.ops_b[:, 0] == E.OP_BN_BWD]
-        assert not (bb[:, 17] > 0).any() and not (bb[:, 18] > 0).any()
-        assert int((p0.ops_b[:, 0] == E.OP_ADD).sum()) > int((p.ops_b[:, 0] == E.OP_ADD).sum())
+        assert not (p0.ops_f[:, CV('stats')][p0.ops_f[:, OP] == E.OP_CONV] > 0).any()
+        assert not (p0.ops_f[:, BF('producer')][p0.ops_f[:, OP] == E.OP_BN_FWD] > 0).any()
+        bb = p0.ops_b[p0.ops_b[:, OP] == E.OP_BN_BWD]
+        assert not (bb[:, BB('gy2')] > 0).any() and not (bb[:, BB('producer')] > 0).any()
+        assert int((p0.ops_b[:, OP] == E.OP_ADD).sum()) > int((p.ops_b[:, OP] == E.OP_ADD).sum())
     finally:
         Fn.BN_FUSE = True

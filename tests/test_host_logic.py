@@ -266,6 +266,7 @@ def test_committed_profile_tables_follow_from_the_committed_traces():
 # equal to that of a profiled source: a change of host code, names and comments only, which leaves the profiles valid
 DEVICE_IDENTICAL_SOURCES = {
     '66ec67355c91a62d': '5b97211d4d40026d',      # retired A/B switches, named FC_CONV_* flag bits
+    'f17a9bc9f17e6a93': '7094ae11604f2248',      # csrc/exec_ops.h: the executor's row and descriptor layouts by name (host code only)
 }
 
 
