@@ -63,7 +63,7 @@ def parse_enums(path=EXEC_OPS):
     return blocks
 
 
-ABI_VERSION = 9          # include/fcaf3d_hip.h FC_ABI_VERSION
+ABI_VERSION = 10         # include/fcaf3d_hip.h FC_ABI_VERSION
 _lib = None
 _protos = None
 
@@ -117,6 +117,25 @@ def call(name, *args):
     if rc != 0:
         kind = 'invalid argument' if rc == -1 else 'workspace too small' if rc == -2 else f'hipError {rc}'
         raise RuntimeError(f'{name} failed: {kind}')
+
+
+_header_enums = {}
+
+
+def header_enums():
+    """{name: value} of every enum of include/fcaf3d_hip.h (FC_TABLE_*, FC_FAM_*, FC_ROUTE_* ...)"""
+    if not _header_enums:
+        _header_enums.update({k: v for block in parse_enums(HEADER) for k, v in block.items()})
+    return _header_enums
+
+
+def route(name, *args):
+    """fc_conv_fwd_route / fc_conv_wgrad_route(*args) -> (status, {field: value}), the fields under the header's FC_ROUTE_* /
+    FC_WROUTE_* names in lower case: the launch the matching entry point would make of that call (pure host functions)"""
+    out = (ctypes.c_int * 16)()
+    rc = getattr(lib(), name)(*args, out)
+    prefix = 'FC_WROUTE_' if name == 'fc_conv_wgrad_route' else 'FC_ROUTE_'
+    return rc, {k[len(prefix):].lower(): out[v] for k, v in header_enums().items() if k.startswith(prefix)}
 
 
 _query_cache = {}

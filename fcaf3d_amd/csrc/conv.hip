@@ -67,7 +67,7 @@ extern "C" int fc_set_split_mode(int mode) {
   return FC_OK;
 }
 extern "C" int fc_get_split_mode(void) { return split_mode(); }
-static int g_h3r = 1;                            // which h3 launches run the register-operand kernel (launch_conv_mfma)
+static int g_h3r = 1;                            // which h3 launches run the register-operand kernel (conv_route.h)
 extern "C" int fc_debug_set_h3r(int mode) {
   if (mode < 0 || mode > 2) return FC_EINVAL;
   g_h3r = mode;
@@ -78,6 +78,9 @@ extern "C" int fc_debug_set_h3r(int mode) {
 #include "conv_x6.h"
 #include "wgrad_x6.h"
 #include "conv_h3r.h"
+#include "conv_route.h"
+// the three switches above as every entry point reads them: once, before it computes its route
+static inline RouteEnv route_env() { return {split_mode(), g_bf16_fast, g_h3r}; }
 
 // ---- r6: max |x| of an operand tensor (the scale of the h3 split, conv_x6.h) -----------------------------------------------------
 // slot = FC_AMAX_SLOT_BYTES (fc_common.h: 32 sub-words, one per 64-byte line; the kernels read their maximum); this pass uses the
@@ -1326,238 +1329,163 @@ __global__ void k_conv_fma(const float* __restrict__ in, const float* __restrict
   out[t] = acc;
 }
 
-extern "C" {
+static_assert(STEM_CIN == 3 && STEM_COUT == 64 && BK == 32, "conv_route.h spells these shapes out");
 
-// The deeper-pipelined LDS kernel (k_conv_mfma_p) holds 3 workgroups per CU (768 slots) where k_conv_mfma holds 4 (1024): it
-// wins on launches of many rounds and on launches that fit 768 slots anyway, and loses a round in between (r2: +5.5 / +7 %
-// on the 441k / 55k-row levels, +5 % on the 862-row pair mode, -12 % on the 3.5k-row pair mode with its 972 workgroups).
-// FC_CONV_PIPE_ON forces it on, FC_CONV_PIPE_OFF off.
-// FC_CONV_GLDS: the LDS-DMA kernel (k_conv_glds, 2 workgroups per CU) instead.  Returns 0 / 1 / 2 = k_conv_mfma / _p / k_conv_glds.
-static inline int conv_pipe(int flags, dim3 grid) {
-  if (flags & FC_CONV_SPLIT) return (flags & FC_CONV_IMAGE) ? 4 : 3;     // split-bf16 kernel (conv_x6.h); W is a pre-split image
-  if (flags & FC_CONV_GLDS) return 2;
-  if (flags & FC_CONV_PIPE_ON) return 1;
-  if (flags & FC_CONV_PIPE_OFF) return 0;
-  const int64_t wgs = (int64_t)grid.x * grid.y * grid.z;
-  if (wgs >= 1536 || wgs <= 768) return 1;
-  // in between: offset-split launches of a dense table go to the LDS-DMA kernel (r2 nbench, same box: 6.9k rows 256->256
-  // 251 -> 232 us, 256->128 139 -> 128 us, 14.9k rows 128->128 163 -> 146 us; unsplit and pair-list launches: neutral)
-  return (grid.z > 1 && !(flags & FC_CONV_GLDS_OFF)) ? 2 : 0;
-}
+// what every tiled convolution kernel takes (k_conv_x6 / k_conv_h3r: and the epilogue)
+struct ConvArgs {
+  const float *in, *W; const int *nbr, *out_index, *cnt; float* dst;
+  int64_t n_rows; int K, Cin, Cout; X6Epi epi; hipStream_t stream;
+};
+#define FC_LAUNCH(...) __VA_ARGS__<<<grid, 256, 0, a.stream>>>(a.in, a.W, a.nbr, a.out_index, a.cnt, a.dst, a.n_rows, a.K, a.Cin, a.Cout)
+#define FC_LAUNCH_EPI(...) __VA_ARGS__<<<grid, 256, 0, a.stream>>>(a.in, a.W, a.nbr, a.out_index, a.cnt, a.dst, a.n_rows, a.K, a.Cin, a.Cout, a.epi)
 
-static void conv_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool* mfma, int* bm, int* bn, int* S) {
-  *mfma = !(flags & FC_CONV_FMA) && (Cin % BK == 0) && (Cout % 64 == 0) && K <= 32;
-  *bn = (Cout % 128 == 0) ? 128 : 64;
-  const int64_t wg128 = fc_cdiv(n_out, 128) * (Cout / *bn);
-  // measured on the benchmark's layers (tools/convbench.py): 128-row tiles win at every size once the grid
-  // is topped up to ~1024 workgroups by splitting over kernel offsets
-  *bm = (n_out > 64 && wg128 >= 4) ? 128 : 64;
-  // 64-wide outputs on big maps: 256 x 64 tiles, 4 waves along the rows (r2: +6 % on the 441k-row level, 88 / 95 TF)
-  if (*bn == 64 && Cout == 64 && fc_cdiv(n_out, 256) >= 1024 && !(flags & FC_CONV_SPLIT)) *bm = 256;      // (split-bf16: 128 x 64 at 4 waves / SIMD is ahead, 613 vs 628 us)
-  const int64_t tiles = fc_cdiv(n_out, *bm) * (Cout / *bn);
-  int s = 1;
-  // split over kernel offsets: the LARGEST split that still fits one resident round (1024 workgroup slots) — one workgroup
-  // over (r1 rounded up) starts a second, nearly empty round (r2 sweep: 256->256 on 6.9k rows 275 us at S = 10 -> 238 at
-  // S = 9); from ~400 tiles on the unsplit launch wins (64->64 on 64k rows: 159 us at S = 2 -> 144 at S = 1, and no
-  // partial tiles to write and sum)
-  if (*mfma && K > 1 && tiles < 384) {          // (r5 sweep with the split-bf16 kernels: 256 / 512 / 768 change nothing, 368.1-368.5 scenes/s)
-    s = (int)(1024 / tiles);
-    if (s > K) s = K;
-    if (s < 1) s = 1;
-  }
-  // tuning overrides: BM (1=64, 2=128, 3=256), BN (1=64, 2=128), S
-  int fbm = (flags >> FC_CONV_BM_SHIFT) & FC_CONV_TILE_MASK, fbn = (flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK,
-      fs = (flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK;
-  if (fbm) *bm = fbm == 1 ? 64 : (fbm == 2 ? 128 : 256);
-  if (fbn && (Cout % (fbn == 1 ? 64 : 128) == 0)) *bn = fbn == 1 ? 64 : 128;
-  if (*bm == 256) *bn = 64;                      // the 4 x 1 wave arrangement: 256 x 64 tiles
-  if (fbm || fbn) {
-    const int64_t t2 = fc_cdiv(n_out, *bm) * (Cout / *bn);
-    s = 1;
-    if (*mfma && K > 1 && t2 < 384) { s = (int)(1024 / t2); if (s > K) s = K; if (s < 1) s = 1; }
-  }
-  if (fs) s = fs > K ? K : fs;
-  if ((flags & FC_CONV_SPLIT) && *mfma && *bm == 64) {     // the split-bf16 kernel has 128- and 256-row tiles only
-    *bm = 128;
-    const int64_t t3 = fc_cdiv(n_out, 128) * (Cout / *bn);
-    if (!fs) { s = 1; if (K > 1 && t3 < 384) { s = (int)(1024 / t3); if (s > K) s = K; } }
-  }
-  *S = s;
-}
-
-// one launch of the LDS-tiled MFMA kernel (32-deep slabs; measured r1: 64-deep slabs, 256-row tiles, an LDS index table
+// the LDS-tiled fp32 MFMA kernels (32-deep slabs; measured r1: 64-deep slabs, 256-row tiles, an LDS index table
 // and LDS-padding occupancy caps all lose or are neutral — profiles/r1_conv_pmc.md — and were removed in r2)
-static int launch_conv_mfma(int pipe, int bm, int bn, dim3 grid, const float* in, const float* W, const int* nbr,
-                            const int* out_index, const int* cnt, float* dst, int64_t n_rows, int K, int Cin, int Cout,
-                            hipStream_t stream, bool wt = false, const X6Epi* epi = nullptr, int64_t n_in = -1,
-                            int64_t n_in_rows = -1) {
-  if (epi && (pipe < 3 || bm < 128 || cnt || grid.z != 1)) return FC_EINVAL;      // the statistics epilogue lives in k_conv_x6
-  // buffer addressing (k_conv_x6 BUF; gathering launches on a weight image): the gathered operand must end below the 2 GB its
-  // descriptor spans; n_in < 0: the caller asks for (FC_CONV_FLAT) or only knows flat addresses
-  const bool bufok = nbr && n_in >= 0 && (uint64_t)n_in * (uint64_t)Cin * 4u < (1ull << 31) - 4096u &&
-                     (uint64_t)K * (uint64_t)n_rows * 4u < (1ull << 31) - 4096u;      // (r6: the neighbour table goes through a descriptor too)
-  X6Epi e6 = {};
-  if (epi) e6 = *epi;
-  const bool h3 = pipe == 4 && bm >= 128 && split_mode() == 2;
-  if (h3) {                                      // the gathered operand's amax word: the caller's hint or a pass of our own
-    if (n_in_rows < 0) return FC_EINVAL;
-    int rc = operand_amax(in, n_in_rows * (int64_t)Cin, 0, stream, &e6.amax_in);
-    if (rc != FC_OK) return rc;
+template <int BM, int BN, int WM>
+static void launch_conv_fp32(const ConvRoute& r, const ConvArgs& a, dim3 grid) {
+#define FC_LAUNCH_MFMA(KERNEL)                                                                                              \
+  do { if (r.wsrc == FC_WSRC_FP32_T) FC_LAUNCH(KERNEL<BM, BN, 32, true, WM, true>); else if (a.nbr) FC_LAUNCH(KERNEL<BM, BN, 32, true, WM>); \
+       else FC_LAUNCH(KERNEL<BM, BN, 32, false, WM>); } while (0)
+  if (r.family == FC_FAM_MFMA) FC_LAUNCH_MFMA(k_conv_mfma);
+  if constexpr (BM >= 128) {                     // the deeper pipeline and the LDS-DMA kernel have no 64-row tile
+    if (r.family == FC_FAM_MFMA_P) FC_LAUNCH_MFMA(k_conv_mfma_p);
+    if (r.family == FC_FAM_GLDS) { if (a.nbr) FC_LAUNCH(k_conv_glds<BM, BN, true, WM>); else FC_LAUNCH(k_conv_glds<BM, BN, false, WM>); }
   }
-#define FC_ARGS <<<grid, 256, 0, stream>>>(in, W, nbr, out_index, cnt, dst, n_rows, K, Cin, Cout)
-#define FC_LAUNCH_MFMA(KERNEL, BM_, BN_, WM_)                                    \
-  do {                                                                           \
-    if (wt) KERNEL<BM_, BN_, 32, true, WM_, true> FC_ARGS;                        \
-    else if (nbr) KERNEL<BM_, BN_, 32, true, WM_> FC_ARGS;                        \
-    else KERNEL<BM_, BN_, 32, false, WM_> FC_ARGS;                                \
-  } while (0)
-#define FC_LAUNCH_GLDS(BM_, BN_, WM_)                                            \
-  do {                                                                           \
-    if (nbr) k_conv_glds<BM_, BN_, true, WM_> FC_ARGS;                            \
-    else k_conv_glds<BM_, BN_, false, WM_> FC_ARGS;                               \
-  } while (0)
-  if (pipe == 4) wt = false;                     // a weight image already is the operator of its direction
-  if (wt && !nbr) return FC_EINVAL;              // transposed weights: neighbour-table / pair-list launches only
-  if (wt && pipe == 2) pipe = 0;                 // the LDS-DMA image cannot be transposed in flight
-  // r6: h3 launches on 128 x 128 tiles take the register-operand kernel (conv_h3r.h): +1...11 % per launch there (tools/nbench, same
-  // box), while the 64-column tiles LOSE 7-14 % on the 441k-row maps — a lane-per-row load touches 32 cache lines per instruction
-  // where the LDS staging touches 8, and those launches are bound by the gather.  fc_debug_set_h3r: 0 never, 1 (default)
-  // 128-column tiles, 2 every 128-row tile.
-  if (h3 && bm == 128 && !g_bf16_fast && (g_h3r == 2 || (g_h3r == 1 && bn == 128))) {
-#define FC_LAUNCH_H3R(BN_)                                                                                               \
-  do {                                                                                                                  \
-    if (nbr && bufok) k_conv_h3r<BN_, true, true><<<grid, 256, 0, stream>>>(in, W, nbr, out_index, cnt, dst, n_rows, K, Cin, Cout, e6);       \
-    else if (nbr) k_conv_h3r<BN_, true, false><<<grid, 256, 0, stream>>>(in, W, nbr, out_index, cnt, dst, n_rows, K, Cin, Cout, e6);          \
-    else k_conv_h3r<BN_, false, false><<<grid, 256, 0, stream>>>(in, W, nbr, out_index, cnt, dst, n_rows, K, Cin, Cout, e6);                  \
-  } while (0)
-    if (bn == 128) FC_LAUNCH_H3R(128); else FC_LAUNCH_H3R(64);
-#undef FC_LAUNCH_H3R
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  if (pipe >= 3 && bm >= 128) {                  // split-bf16 kernel; pipe 4: the weights are a pre-split image
-#define FC_ARGS6 <<<grid, 256, 0, stream>>>(in, W, nbr, out_index, cnt, dst, n_rows, K, Cin, Cout, e6)
-#define FC_LAUNCH_X6(BM_, BN_, WM_)                                              \
-  do {                                                                           \
-    if (pipe == 4 && g_bf16_fast && BM_ == 128 && nbr) k_conv_x6<128, BN_, true, 2, 2, 1> FC_ARGS6;   \
-    else if (pipe == 4 && g_bf16_fast && BM_ == 128) k_conv_x6<128, BN_, false, 2, 2, 1> FC_ARGS6;  \
-    else if (pipe == 4 && h3 && bufok && BM_ == 128) k_conv_x6<128, BN_, true, 2, 2, 2, true> FC_ARGS6;  \
-    else if (pipe == 4 && h3 && nbr) k_conv_x6<BM_, BN_, true, WM_, 2, 2> FC_ARGS6;  \
-    else if (pipe == 4 && h3) k_conv_x6<BM_, BN_, false, WM_, 2, 2> FC_ARGS6;  \
-    else if (pipe == 4 && bufok && BM_ == 128) k_conv_x6<128, BN_, true, 2, 2, 0, true> FC_ARGS6;  \
-    else if (pipe == 4 && nbr) k_conv_x6<BM_, BN_, true, WM_, 2> FC_ARGS6;       \
-    else if (pipe == 4) k_conv_x6<BM_, BN_, false, WM_, 2> FC_ARGS6;        \
-    else if (wt) k_conv_x6<BM_, BN_, true, WM_, 1> FC_ARGS6;                \
-    else if (nbr) k_conv_x6<BM_, BN_, true, WM_, 0> FC_ARGS6;               \
-    else k_conv_x6<BM_, BN_, false, WM_, 0> FC_ARGS6;                       \
-  } while (0)
-    if (bm == 256) FC_LAUNCH_X6(256, 64, 4);
-    else if (bn == 128) FC_LAUNCH_X6(128, 128, 2);
-    else FC_LAUNCH_X6(128, 64, 2);
-#undef FC_LAUNCH_X6
-#undef FC_ARGS6
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  if (pipe >= 3) pipe = 1;                       // 64-row tiles: fp32 pipe
-  if (pipe == 2 && bm >= 128) {
-    if (bm == 256) FC_LAUNCH_GLDS(256, 64, 4);
-    else if (bn == 128) FC_LAUNCH_GLDS(128, 128, 2);
-    else FC_LAUNCH_GLDS(128, 64, 2);
-  } else if (pipe && bm == 256) FC_LAUNCH_MFMA(k_conv_mfma_p, 256, 64, 4);
-  else if (pipe && bm == 128 && bn == 128) FC_LAUNCH_MFMA(k_conv_mfma_p, 128, 128, 2);
-  else if (pipe && bm == 128 && bn == 64) FC_LAUNCH_MFMA(k_conv_mfma_p, 128, 64, 2);
-  else if (bm == 256) FC_LAUNCH_MFMA(k_conv_mfma, 256, 64, 4);
-  else if (bm == 128 && bn == 128) FC_LAUNCH_MFMA(k_conv_mfma, 128, 128, 2);
-  else if (bm == 128) FC_LAUNCH_MFMA(k_conv_mfma, 128, 64, 2);
-  else if (bn == 128) FC_LAUNCH_MFMA(k_conv_mfma, 64, 128, 2);
-  else FC_LAUNCH_MFMA(k_conv_mfma, 64, 64, 2);
-#undef FC_LAUNCH_GLDS
 #undef FC_LAUNCH_MFMA
-#undef FC_ARGS
+}
+
+// the split-bf16 kernel (conv_x6.h): template arguments <tile, HAS_NBR, WM, BSRC = r.wsrc, MODE, BUF>; bf16-fast and buffer addressing
+// exist for 128-row tiles reading an image; k_conv_h3r (conv_h3r.h): h3 on 128-row tiles
+template <int BM, int BN, int WM>
+static void launch_conv_x6(const ConvRoute& r, const ConvArgs& a, dim3 grid) {
+  if (r.family == FC_FAM_H3R) {
+    if constexpr (BM == 128) {
+      if (r.buf) FC_LAUNCH_EPI(k_conv_h3r<BN, true, true>);
+      else if (a.nbr) FC_LAUNCH_EPI(k_conv_h3r<BN, true, false>);
+      else FC_LAUNCH_EPI(k_conv_h3r<BN, false, false>);
+    }
+  } else if (r.wsrc == FC_WSRC_FP32_T) FC_LAUNCH_EPI(k_conv_x6<BM, BN, true, WM, 1>);
+  else if (r.wsrc == FC_WSRC_FP32) { if (a.nbr) FC_LAUNCH_EPI(k_conv_x6<BM, BN, true, WM, 0>); else FC_LAUNCH_EPI(k_conv_x6<BM, BN, false, WM, 0>); }
+  else if (r.mode == FC_MODE_BF16 || r.buf) {
+    if constexpr (BM == 128) {
+      if (r.mode == FC_MODE_BF16) { if (a.nbr) FC_LAUNCH_EPI(k_conv_x6<128, BN, true, 2, 2, 1>); else FC_LAUNCH_EPI(k_conv_x6<128, BN, false, 2, 2, 1>); }
+      else if (r.mode == FC_MODE_H3) FC_LAUNCH_EPI(k_conv_x6<128, BN, true, 2, 2, 2, true>);
+      else FC_LAUNCH_EPI(k_conv_x6<128, BN, true, 2, 2, 0, true>);
+    }
+  } else if (r.mode == FC_MODE_H3) { if (a.nbr) FC_LAUNCH_EPI(k_conv_x6<BM, BN, true, WM, 2, 2>); else FC_LAUNCH_EPI(k_conv_x6<BM, BN, false, WM, 2, 2>); }
+  else { if (a.nbr) FC_LAUNCH_EPI(k_conv_x6<BM, BN, true, WM, 2>); else FC_LAUNCH_EPI(k_conv_x6<BM, BN, false, WM, 2>); }
+}
+
+// one convolution launch: nothing but the route's template instantiation (STEM / FMA: a.dst is the output itself)
+static int launch_conv(const ConvRoute& r, const ConvArgs& a) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+  if (r.family == FC_FAM_STEM) {
+    const size_t smem = (size_t)(STEM_ROWS * STEM_FWD_LDA + 96 * 64) * sizeof(float);
+    k_stem_fwd<<<(unsigned)fc_cdiv(a.n_rows, STEM_ROWS), 256, smem, a.stream>>>(a.in, a.W, a.nbr, a.dst, nullptr, a.n_rows, a.K);
+  } else if (r.family == FC_FAM_FMA) {
+    k_conv_fma<<<(unsigned)fc_cdiv(a.n_rows * a.Cout, 256), 256, 0, a.stream>>>(a.in, a.W, a.nbr, a.dst, a.n_rows, a.K, a.Cin, a.Cout, r.wsrc == FC_WSRC_FP32_T ? 1 : 0);
+  } else {
+#define FC_TILE(BM, BN, WM) do { if (r.family >= FC_FAM_X6) launch_conv_x6<BM, BN, WM>(r, a, grid); else launch_conv_fp32<BM, BN, WM>(r, a, grid); } while (0)
+    if (r.bm == 256) FC_TILE(256, 64, 4);
+    else if (r.bm == 128 && r.bn == 128) FC_TILE(128, 128, 2);
+    else if (r.bm == 128) FC_TILE(128, 64, 2);
+    else if (r.bn == 128) launch_conv_fp32<64, 128, 2>(r, a, grid);
+    else launch_conv_fp32<64, 64, 2>(r, a, grid);
+#undef FC_TILE
+  }
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
+#undef FC_LAUNCH
+#undef FC_LAUNCH_EPI
 
-static inline bool is_stem(const int* nbr, int K, int Cin, int Cout, int flags) {
-  return !(flags & FC_CONV_FMA) && !(flags & FC_CONV_WT) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27;
+extern "C" {
+
+int fc_conv_fwd_route(int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, int table_kind, int64_t live_tiles, int* out) {
+  if (!out || n_in < 0 || n_out < 0 || K < 1 || Cin < 1 || Cout < 1) return FC_EINVAL;
+  const ConvRoute r = conv_route({n_in, n_out, K, Cin, Cout}, flags, table_kind, live_tiles, route_env());
+  const int f[16] = {r.family, r.bm, r.bn, r.wm, r.S, r.wsrc, r.mode, r.buf, r.epi, (int)r.grid[0], (int)r.grid[1], (int)r.grid[2]};
+  for (int i = 0; i < 16; ++i) out[i] = f[i];
+  return r.family == FC_FAM_INVALID ? FC_EINVAL : FC_OK;
 }
 
 int64_t fc_conv_fwd_ws_bytes(int64_t n_out, int K, int Cin, int Cout, int flags) {
-  bool mfma; int bm, bn, S;
-  conv_plan(n_out > 0 ? n_out : 1, K, Cin, Cout, flags, &mfma, &bm, &bn, &S);
-  return S > 1 ? (int64_t)S * n_out * Cout * (int64_t)sizeof(float) : 0;
+  const ConvRoute r = conv_route({n_out, n_out, K, Cin, Cout}, flags, FC_TABLE_DENSE, 0, route_env());
+  return r.S > 1 ? (int64_t)r.S * n_out * Cout * (int64_t)sizeof(float) : 0;
 }
 
-static int sum_parts(const float* part, float* out, int64_t n_out, int Cout, int S, hipStream_t stream) {
-  int64_t e4 = n_out * Cout / 4;
-  k_sum_parts<<<(unsigned)fc_cdiv(e4, 256), 256, 0, stream>>>(part, out, e4, S);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
-static int sum_parts_stats(const float* part, float* out, int64_t n_out, int Cout, int S, const X6Epi& epi, hipStream_t stream) {
-  const int rb = fc_stat_rb(n_out);
-  k_sum_parts_stats<<<dim3((unsigned)fc_cdiv(n_out, rb), Cout / 64), 256, 0, stream>>>(part, out, n_out, Cout, S, rb, epi);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
-static int conv_fwd_impl(const float* in, const float* W, const int* nbr, const int* out_index,
-                         float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, void* ws,
-                         int64_t ws_bytes, hipStream_t stream, const X6Epi* epi = nullptr) {
-  AmaxHintScope hint_scope;
-  const bool stats = epi != nullptr;
-  if (n_in < 0 || n_out < 0 || K < 1 || Cin < 1 || Cout < 1) return FC_EINVAL;
-  if (n_out == 0) return FC_OK;                 // nothing to write (an empty table may well be a NULL pointer)
-  if (!nbr && (K != 1 || n_in != n_out)) return FC_EINVAL;
-  if (out_index && !nbr) return FC_EINVAL;
-  if (is_stem(nbr, K, Cin, Cout, flags) && !out_index) {
-    size_t smem = (size_t)(STEM_ROWS * STEM_FWD_LDA + 96 * 64) * sizeof(float);
-    k_stem_fwd<<<(unsigned)fc_cdiv(n_out, STEM_ROWS), 256, smem, stream>>>(in, W, nbr, out, nullptr, n_out, K);
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  const bool wt = (flags & FC_CONV_WT) != 0;    // W[k] given as (Cout, Cin): the backward-data pass on the layer's own kernel
-  if (wt && !nbr) return FC_EINVAL;
-  bool mfma_ok; int bm, bn, S;
-  conv_plan(n_out, K, Cin, Cout, flags, &mfma_ok, &bm, &bn, &S);
-  if (stats && (!mfma_ok || !(flags & FC_CONV_SPLIT))) return FC_EINVAL;      // see fc_conv_stats_blocks
-  if (!mfma_ok) {
-    if (out_index || (flags & FC_CONV_IMAGE)) return FC_EINVAL;      // sorted-row tables and weight images are MFMA-path features
-    k_conv_fma<<<(unsigned)fc_cdiv(n_out * Cout, 256), 256, 0, stream>>>(in, W, nbr, out, n_out, K, Cin, Cout, wt ? 1 : 0);
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  if (S > 1 && ws_bytes < (int64_t)S * n_out * Cout * (int64_t)sizeof(float)) return FC_EWS;
-  float* dst = S > 1 ? (float*)ws : out;
-  dim3 grid((unsigned)fc_cdiv(n_out, bm), Cout / bn, S);
-  int rc = launch_conv_mfma(conv_pipe(flags, grid), bm, bn, grid, in, W, nbr, out_index, nullptr, dst, n_out, K, Cin, Cout, stream, wt,
-                            S > 1 ? nullptr : epi, (flags & FC_CONV_FLAT) ? -1 : n_in, n_in);
-  if (rc != FC_OK) return rc;
-  if (S > 1) return stats ? sum_parts_stats(dst, out, n_out, Cout, S, *epi, stream) : sum_parts(dst, out, n_out, Cout, S, stream);
-  return FC_OK;
+int64_t fc_conv_fwd_pairs_ws_bytes(int64_t n_out, int K, int Cout) {      // the pair-list route's S is K, whatever the rest of the shape
+  return (int64_t)K * n_out * Cout * (int64_t)sizeof(float);
 }
 
 // Row blocks of the statistics table a convolution launch leaves for the BatchNorm behind it (fc_conv_fwd_stats /
 // fc_conv_fwd_pairs_tiles_stats: stats[blocks][2][Cout], column sums of the result and of its square per row block); 0: this launch
 // has no statistics epilogue (not the split-bf16 MFMA route).  pairs != 0: the per-offset pair-list route.
 int64_t fc_conv_stats_blocks(int64_t n_out, int K, int Cin, int Cout, int flags, int pairs) {
-  if (n_out < 1 || !(flags & FC_CONV_SPLIT)) return 0;
-  if (pairs) return (Cin % 32 == 0 && Cout % 64 == 0) ? fc_cdiv(n_out, fc_stat_rb(n_out)) : 0;
-  bool mfma_ok; int bm, bn, S;
-  conv_plan(n_out, K, Cin, Cout, flags, &mfma_ok, &bm, &bn, &S);
-  if (!mfma_ok || bm < 128) return 0;
-  return S > 1 ? fc_cdiv(n_out, fc_stat_rb(n_out)) : fc_cdiv(n_out, bm);
+  if (n_out < 1) return 0;
+  const ConvRoute r = conv_route({n_out, n_out, K, Cin, Cout}, flags, pairs ? FC_TABLE_PAIRS : FC_TABLE_DENSE, 0, route_env());
+  if (r.epi == FC_EPI_NONE) return 0;
+  return r.epi == FC_EPI_SUM ? fc_cdiv(n_out, fc_stat_rb(n_out)) : fc_cdiv(n_out, r.bm);
+}
+
+// Every convolution entry point: the route, the workspace, the amax word, the launch, the fixed-order sum of the partial results.
+// cnt / pos != NULL: the exact pair lists (nbr = pair_in) — per offset a compacted gather-GEMM into the workspace, then a gather-sum.
+static int conv_impl(const float* in, const float* W, const int* nbr, const int* out_index, const int* cnt, const int* pos, float* out,
+                     int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags, void* ws, int64_t ws_bytes,
+                     hipStream_t stream, const X6Epi* epi) {
+  AmaxHintScope hint_scope;
+  if (n_in < 0 || n_out < 0 || K < 1 || Cin < 1 || Cout < 1) return FC_EINVAL;
+  // nothing to write (an empty table may well be a NULL pointer) and no row block to leave statistics for
+  if (n_out == 0 && !cnt) return epi ? FC_EINVAL : FC_OK;
+  if (out_index && !nbr) return FC_EINVAL;
+  const int table = cnt ? FC_TABLE_PAIRS : out_index ? FC_TABLE_SORTED : nbr ? FC_TABLE_DENSE : FC_TABLE_NONE;
+  const ConvRoute r = conv_route({n_in, n_out, K, Cin, Cout}, flags, table | (epi ? FC_TABLE_STATS : 0), live_tiles, route_env());
+  if (r.family == FC_FAM_INVALID) return FC_EINVAL;
+  if (n_out == 0) return FC_OK;
+  ConvArgs a = {in, W, nbr, out_index, cnt, out, n_out, K, Cin, Cout, {}, stream};
+  if (r.family == FC_FAM_STEM || r.family == FC_FAM_FMA) return launch_conv(r, a);      // untiled: no partial sums
+  const bool parts = cnt || r.S > 1;
+  if (parts && ws_bytes < (int64_t)r.S * n_out * Cout * (int64_t)sizeof(float)) return FC_EWS;
+  if (parts) a.dst = (float*)ws;
+  if (epi && r.epi == FC_EPI_KERNEL) a.epi = *epi;
+  int rc = FC_OK;
+  if (r.mode == FC_MODE_H3) rc = operand_amax(in, n_in * (int64_t)Cin, 0, stream, &a.epi.amax_in);      // the gathered operand's amax word: the caller's hint or a pass of our own
+  if (rc == FC_OK) rc = launch_conv(r, a);
+  if (rc != FC_OK || !parts) return rc;
+  const int rb = fc_stat_rb(n_out);
+  const dim3 sgrid((unsigned)fc_cdiv(n_out, rb), Cout / 64);
+  if (cnt && epi) k_sum_pairs_stats<<<sgrid, 256, 0, stream>>>(a.dst, pos, out, n_out, K, Cout, rb, *epi);
+  else if (cnt) k_sum_pairs<<<(unsigned)fc_cdiv(n_out * (Cout / 4), 256), 256, 0, stream>>>(a.dst, pos, out, n_out, K, Cout);
+  else if (epi) k_sum_parts_stats<<<sgrid, 256, 0, stream>>>(a.dst, out, n_out, Cout, r.S, rb, *epi);
+  else k_sum_parts<<<(unsigned)fc_cdiv(n_out * Cout / 4, 256), 256, 0, stream>>>(a.dst, out, n_out * Cout / 4, r.S);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+static int conv_pairs_impl(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos, float* out,
+                           int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags, void* ws,
+                           int64_t ws_bytes, hipStream_t stream, const X6Epi* epi) {
+  if (!pair_in || !pair_cnt || !pair_pos || K > 65535) return FC_EINVAL;
+  return conv_impl(in, W, pair_in, nullptr, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream, epi);
+}
+
+// the epilogue of the *_stats entry points (conv_x6.h X6Epi); bn_x != NULL: the two backward reductions of the BatchNorm in front
+static X6Epi stats_epi(float* stats, const float* bn_x = nullptr, const float* mean = nullptr, const float* var = nullptr, const float* gamma = nullptr,
+                       const float* beta = nullptr, float eps = 0.f, int act = 0, const float* add = nullptr, const float* bn_y = nullptr) {
+  return {stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y, nullptr};
+}
+
+// flags: FC_CONV_* (include/fcaf3d_hip.h).
+int fc_conv_fwd(const float* in, const float* W, const int* nbr, const int* out_index, float* out, int64_t n_in,
+                int64_t n_out, int K, int Cin, int Cout, int flags, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  return conv_impl(in, W, nbr, out_index, nullptr, nullptr, out, n_in, n_out, K, Cin, Cout, 0, flags, ws, ws_bytes, stream, nullptr);
 }
 
 int fc_conv_fwd_stats(const float* in, const float* W, const int* nbr, const int* out_index, float* out, int64_t n_in,
                       int64_t n_out, int K, int Cin, int Cout, int flags, void* ws, int64_t ws_bytes, float* stats,
                       hipStream_t stream) {
-  if (stats && fc_conv_stats_blocks(n_out, K, Cin, Cout, flags, 0) == 0) return FC_EINVAL;
-  X6Epi e = {};
-  e.stats = stats;
-  return conv_fwd_impl(in, W, nbr, out_index, out, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream, stats ? &e : nullptr);
+  const X6Epi e = stats_epi(stats);
+  return conv_impl(in, W, nbr, out_index, nullptr, nullptr, out, n_in, n_out, K, Cin, Cout, 0, flags, ws, ws_bytes, stream, stats ? &e : nullptr);
 }
 
 // The backward-data pass of a convolution whose INPUT came out of a BatchNorm (+ ReLU / ELU) layer: besides the gradient g it
@@ -1570,15 +1498,38 @@ int fc_conv_fwd_bn_bwd_stats(const float* in, const float* W, const int* nbr, co
                              const float* bn_x, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
                              int act, const float* add, const float* bn_y, hipStream_t stream) {
   if (!stats || !bn_x || !mean || !var || act < 0 || act > 2) return FC_EINVAL;
-  if (fc_conv_stats_blocks(n_out, K, Cin, Cout, flags, 0) == 0) return FC_EINVAL;
-  X6Epi e = {stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y};
-  return conv_fwd_impl(in, W, nbr, out_index, out, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream, &e);
+  const X6Epi e = stats_epi(stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y);
+  return conv_impl(in, W, nbr, out_index, nullptr, nullptr, out, n_in, n_out, K, Cin, Cout, 0, flags, ws, ws_bytes, stream, &e);
 }
 
-// flags: FC_CONV_* (include/fcaf3d_hip.h).
-int fc_conv_fwd(const float* in, const float* W, const int* nbr, const int* out_index, float* out, int64_t n_in,
-                int64_t n_out, int K, int Cin, int Cout, int flags, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  return conv_fwd_impl(in, W, nbr, out_index, out, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream);
+int fc_conv_fwd_pairs_tiles(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
+                            float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
+                            void* ws, int64_t ws_bytes, hipStream_t stream) {
+  return conv_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream, nullptr);
+}
+
+int fc_conv_fwd_pairs_tiles_stats(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
+                                  float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
+                                  void* ws, int64_t ws_bytes, float* stats, hipStream_t stream) {
+  const X6Epi e = stats_epi(stats);
+  return conv_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
+                         stats ? &e : nullptr);
+}
+
+int fc_conv_fwd_pairs_tiles_bn_bwd_stats(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
+                                         float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
+                                         void* ws, int64_t ws_bytes, float* stats, const float* bn_x, const float* mean,
+                                         const float* var, const float* gamma, const float* beta, float eps, int act,
+                                         const float* add, const float* bn_y, hipStream_t stream) {
+  if (!stats || !bn_x || !mean || !var || act < 0 || act > 2) return FC_EINVAL;
+  const X6Epi e = stats_epi(stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y);
+  return conv_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream, &e);
+}
+
+int fc_conv_fwd_pairs(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
+                      float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, void* ws,
+                      int64_t ws_bytes, hipStream_t stream) {
+  return fc_conv_fwd_pairs_tiles(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, 0, flags, ws, ws_bytes, stream);
 }
 
 // Pre-split weight image for the split-bf16 kernel (FC_CONV_SPLIT | FC_CONV_IMAGE of fc_conv_fwd / fc_conv_fwd_pairs*): R = reduction
@@ -1612,76 +1563,6 @@ int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, hipStr
   }
   FC_CHECK_LAUNCH();
   return FC_OK;
-}
-
-int64_t fc_conv_fwd_pairs_ws_bytes(int64_t n_out, int K, int Cout) {
-  return (int64_t)K * n_out * Cout * (int64_t)sizeof(float);
-}
-
-// Convolution over the exact pair lists: per offset a compacted gather-GEMM into the workspace, then a gather-sum.
-static int conv_fwd_pairs_impl(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
-                            float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
-                            void* ws, int64_t ws_bytes, hipStream_t stream, const X6Epi* epi) {
-  AmaxHintScope hint_scope;
-  if (n_in < 0 || n_out < 0 || K < 1 || K > 65535 || Cin < 1 || Cout < 1) return FC_EINVAL;
-  if (!pair_in || !pair_cnt || !pair_pos) return FC_EINVAL;
-  if (Cin % 32 != 0 || Cout % 64 != 0) return FC_EINVAL;       // MFMA shapes only; callers use fc_conv_fwd otherwise
-  if (n_out == 0) return FC_OK;
-  if (ws_bytes < fc_conv_fwd_pairs_ws_bytes(n_out, K, Cout)) return FC_EWS;
-  float* part = (float*)ws;
-  const bool wt = (flags & FC_CONV_WT) != 0;
-  // (r5, measured null: 64-column tiles for the few-thousand-row pair-list launches — 4 workgroups per CU, finer rounds — 373.6 /
-  // 372.5 / 372.2 scenes/s at <= 1k / 4k / 16k rows against 375.4: profiles/r5_notes.md)
-  const bool wide = (Cout % 128 == 0) && !(((flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK) == 1);
-  const int bn = wide ? 128 : 64;
-  dim3 grid((unsigned)fc_cdiv(n_out, 128), Cout / bn, K);
-  if (live_tiles > 0) grid = dim3((unsigned)live_tiles, Cout / bn, 1);       // linear list of the live (offset, tile) pairs
-  {
-    int rc = launch_conv_mfma((live_tiles > 0 || (flags & FC_CONV_SPLIT)) ? conv_pipe(flags, grid) : ((flags & FC_CONV_GLDS) ? 2 : ((flags & FC_CONV_PIPE_ON) ? 1 : 0)), 128, bn, grid, in, W, pair_in, nullptr, pair_cnt, part, n_out, K, Cin, Cout, stream, wt, nullptr, (flags & FC_CONV_FLAT) ? -1 : n_in, n_in);
-    if (rc != FC_OK) return rc;
-  }
-  if (epi) {
-    const int rb = fc_stat_rb(n_out);
-    k_sum_pairs_stats<<<dim3((unsigned)fc_cdiv(n_out, rb), Cout / 64), 256, 0, stream>>>(part, pair_pos, out, n_out, K, Cout, rb, *epi);
-  } else {
-    k_sum_pairs<<<(unsigned)fc_cdiv(n_out * (Cout / 4), 256), 256, 0, stream>>>(part, pair_pos, out, n_out, K, Cout);
-  }
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
-int fc_conv_fwd_pairs_tiles(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
-                            float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
-                            void* ws, int64_t ws_bytes, hipStream_t stream) {
-  return conv_fwd_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
-                             nullptr);
-}
-
-int fc_conv_fwd_pairs_tiles_stats(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
-                                  float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
-                                  void* ws, int64_t ws_bytes, float* stats, hipStream_t stream) {
-  if (stats && !(flags & FC_CONV_SPLIT)) return FC_EINVAL;
-  X6Epi e = {};
-  e.stats = stats;
-  return conv_fwd_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
-                             stats ? &e : nullptr);
-}
-
-int fc_conv_fwd_pairs_tiles_bn_bwd_stats(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
-                                         float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int64_t live_tiles, int flags,
-                                         void* ws, int64_t ws_bytes, float* stats, const float* bn_x, const float* mean,
-                                         const float* var, const float* gamma, const float* beta, float eps, int act,
-                                         const float* add, const float* bn_y, hipStream_t stream) {
-  if (!stats || !bn_x || !mean || !var || act < 0 || act > 2 || !(flags & FC_CONV_SPLIT)) return FC_EINVAL;
-  X6Epi e = {stats, bn_x, mean, var, gamma, beta, eps, act, add, bn_y};
-  return conv_fwd_pairs_impl(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, live_tiles, flags, ws, ws_bytes, stream,
-                             &e);
-}
-
-int fc_conv_fwd_pairs(const float* in, const float* W, const int* pair_in, const int* pair_cnt, const int* pair_pos,
-                      float* out, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, void* ws,
-                      int64_t ws_bytes, hipStream_t stream) {
-  return fc_conv_fwd_pairs_tiles(in, W, pair_in, pair_cnt, pair_pos, out, n_in, n_out, K, Cin, Cout, 0, flags, ws, ws_bytes, stream);
 }
 
 }  // extern "C"
@@ -2142,65 +2023,55 @@ __global__ void k_transpose_w(const float* __restrict__ W, float* __restrict__ W
   }
 }
 
+// what every weight-gradient kernel takes (k_wgrad_x6t: and the amax words; the kernels without pair lists: no row_index / cnt)
+struct WgradArgs {
+  const float *in, *gout; const int *nbr, *row_index, *cnt; float* part;
+  int64_t n_out; int K, Cin, Cout; const unsigned *amax_in, *amax_gout; hipStream_t stream;
+};
+#define FC_LAUNCH(...) __VA_ARGS__<<<grid, 256, 0, a.stream>>>(a.in, a.gout, a.nbr, a.row_index, a.cnt, a.part, a.n_out, a.K, a.Cin, a.Cout, r.rps)
+#define FC_LAUNCH_X6T(...) __VA_ARGS__<<<grid, 256, 0, a.stream>>>(a.in, a.gout, a.nbr, a.row_index, a.cnt, a.part, a.n_out, a.K, a.Cin, a.Cout, r.rps, a.amax_in, a.amax_gout, r.wbuf)
+#define FC_LAUNCH_TABLE(...) __VA_ARGS__<<<grid, 256, 0, a.stream>>>(a.in, a.gout, a.nbr, a.part, a.n_out, a.K, a.Cin, a.Cout, r.rps)
+
+template <int BM, int BN, int KO, bool PAIRS>          // split-bf16 (wgrad_x6.h): the arithmetic is the last template argument
+static void launch_wgrad_x6t(const WgradRoute& r, const WgradArgs& a, dim3 grid) {
+  if (r.mode == FC_MODE_BF16) FC_LAUNCH_X6T(k_wgrad_x6t<BM, BN, KO, PAIRS, 1>);
+  else if (r.mode == FC_MODE_H3) FC_LAUNCH_X6T(k_wgrad_x6t<BM, BN, KO, PAIRS, 2>);
+  else FC_LAUNCH_X6T(k_wgrad_x6t<BM, BN, KO, PAIRS>);
+}
+
+template <int BM, int BN>                               // one offset per workgroup: k_wgrad_x6t, k_wgrad_mfma, k_wgrad_mfma_p (64-channel Cin tiles)
+static void launch_wgrad_tile(const WgradRoute& r, const WgradArgs& a, dim3 grid) {
+  const bool pairs = r.table == FC_TABLE_PAIRS;
+  if (r.family == FC_WFAM_X6T) { if (pairs) launch_wgrad_x6t<BM, BN, 1, true>(r, a, grid); else launch_wgrad_x6t<BM, BN, 1, false>(r, a, grid); }
+  else if (r.family == FC_WFAM_MFMA && !pairs && r.bkr == 32) { if (a.nbr) FC_LAUNCH(k_wgrad_mfma<BM, BN, true, 32, false>); else FC_LAUNCH(k_wgrad_mfma<BM, BN, false, 32, false>); }
+  else if constexpr (BM == 64) {
+    if (r.family == FC_WFAM_MFMA) { if (pairs) FC_LAUNCH(k_wgrad_mfma<64, BN, true, 32, true>); else FC_LAUNCH(k_wgrad_mfma<64, BN, true, 64, false>); }
+    else if (pairs) FC_LAUNCH(k_wgrad_mfma_p<BN, true, true>);
+    else if (a.nbr) FC_LAUNCH(k_wgrad_mfma_p<BN, true, false>);
+    else FC_LAUNCH(k_wgrad_mfma_p<BN, false, false>);
+  }
+}
+
+// one weight-gradient launch: nothing but the route's template instantiation
+static int launch_wgrad(const WgradRoute& r, const WgradArgs& a) {
+  const dim3 grid((unsigned)r.S, r.grid_y);
+  const bool wide = r.bn == 128;
+  if (r.family == FC_WFAM_STEM) {
+    const size_t smem = (size_t)(STEM_ROWS * STEM_JP + STEM_ROWS * 64) * sizeof(float);
+    k_stem_wgrad<<<(unsigned)r.S, 256, smem, a.stream>>>(a.in, a.gout, a.nbr, a.part, a.n_out, a.K, r.rps);
+  } else if (r.family == FC_WFAM_FMA) FC_LAUNCH_TABLE(k_wgrad_fma);
+  else if (r.family == FC_WFAM_MULTI) { if (wide) FC_LAUNCH_TABLE(k_wgrad_multi<128, WGRAD_KO>); else FC_LAUNCH_TABLE(k_wgrad_multi<64, WGRAD_KO>); }
+  else if (r.ko == WGRAD_KO) { if (wide) launch_wgrad_x6t<64, 128, WGRAD_KO, false>(r, a, grid); else launch_wgrad_x6t<64, 64, WGRAD_KO, false>(r, a, grid); }
+  else if (r.bm == 128) { if (wide) launch_wgrad_tile<128, 128>(r, a, grid); else launch_wgrad_tile<128, 64>(r, a, grid); }
+  else { if (wide) launch_wgrad_tile<64, 128>(r, a, grid); else launch_wgrad_tile<64, 64>(r, a, grid); }
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+#undef FC_LAUNCH
+#undef FC_LAUNCH_X6T
+#undef FC_LAUNCH_TABLE
+
 extern "C" {
-
-static void wgrad_tiles(int Cin, int Cout, int flags, int* bm, int* bn) {
-  *bm = 64;                                  // measured: 64-channel Cin tiles beat 128 on every benchmark layer
-  *bn = (Cout % 128 == 0) ? 128 : 64;
-  int fbm = (flags >> FC_CONV_BM_SHIFT) & FC_CONV_TILE_MASK, fbn = (flags >> FC_CONV_BN_SHIFT) & FC_CONV_TILE_MASK;      // tuning overrides
-  if (fbm == 1) *bm = 64;
-  if (fbm == 2 && Cin % 128 == 0) *bm = 128;
-  if (fbn == 1) *bn = 64;
-  if (fbn == 2 && Cout % 128 == 0) *bn = 128;
-}
-
-// several offsets per workgroup (k_wgrad_multi): every dense table with >= 4096 rows (r2 nbench, one-offset kernel -> multi:
-// 55k rows 128->128 504 -> 446 us, 6.9k rows 256->256 278 -> 247, 256->128 148 -> 135, 441k rows 128->64 2121 -> 2003, 64->64
-// 1086 -> 1051); FC_CONV_WGRAD_MULTI_OFF disables it, FC_CONV_WGRAD_MULTI_FIRST restricts it to its first rule (Cin = 64, >= 32768 rows)
-#define WGRAD_KO 3
-// split-bf16 weight gradients: rows loaded 16 B per lane and transposed by ds_read_b64_tr_b16 (k_wgrad_x6t, r4; the register
-// transposition of r3, k_wgrad_x6, is gone since r5), every pair-list and table-free dense shape included
-static inline bool wgrad_multi_ok(int64_t n_out, int K, int Cin, int Cout, int flags, bool dense_table) {
-  return dense_table && !(flags & FC_CONV_FMA) && !(flags & FC_CONV_WGRAD_MULTI_OFF) && K % WGRAD_KO == 0 &&
-         Cin % 64 == 0 && Cout % 64 == 0 && n_out >= 4096 && (!(flags & FC_CONV_WGRAD_MULTI_FIRST) || (Cin == 64 && n_out >= 32768));
-}
-
-static void wgrad_plan(int64_t n_out, int K, int Cin, int Cout, int flags, bool dense_table, int* S, int64_t* rows_per_split) {
-  if (!(flags & FC_CONV_FMA) && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {     // stem: 4096 rows per block
-    int64_t m = n_out > 0 ? n_out : 1;
-    *rows_per_split = 1024;                      // (r2: 512 rows per block is slower — more partial tiles to write and reduce)
-    *S = (int)fc_cdiv(m, 1024);
-    return;
-  }
-  bool mfma_ok = !(flags & FC_CONV_FMA) && (Cin % 64 == 0) && (Cout % 64 == 0);
-  int tbm, tbn;
-  wgrad_tiles(Cin, Cout, flags, &tbm, &tbn);
-  if ((flags & FC_CONV_SPLIT) && !dense_table && Cin % 128 == 0) tbm = 128;      // split-bf16 pair-list kernel: 128-channel tiles
-  int64_t tiles = mfma_ok ? (int64_t)K * (Cin / tbm) * (Cout / tbn) : (int64_t)K;
-  // aim for ~1728 workgroups (r2 sweep: 2048 rounded UP left a nearly empty last round on most layers — 128->128 on 55k
-  // rows 559 us at 38 splits, 448 at 32), at least 512 rows per split, at most 256 splits
-  int64_t s = 1728 / tiles;                  // (same-box A/B in the full step: neutral, 230.3 vs 230.9 scenes/s; kept: fewer partial tiles)
-  if (wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table)) {
-    // uniform long workgroups: exactly one resident round (3 per CU), fewer partial gradients to write and re-read
-    const bool wide = Cout % 128 == 0;
-    tiles = (int64_t)(K / WGRAD_KO) * (Cin / 64) * (Cout / (wide ? 128 : 64));
-    // r4 A/B in the full step (weight gradients beside the dependent chain): 3/4 of a resident round 22.91 ms, a full round
-    // (r3) 23.34, half 23.70, a quarter 28.63, two rounds 23.25 — the main stream's kernels find a slot sooner.  With the
-    // transposing-read kernel (k_wgrad_x6t, 1.4x faster per launch) half a round of the wide variant is ahead: 256 / 512
-    // 22.26-22.35 ms, 192 / 512 22.41, 384 / 512 22.65, 128 / 512 23.36 (same box)
-    constexpr int round_wide = 256, round_narrow = 512;
-    s = (wide ? round_wide : round_narrow) / tiles;     // the 128-column variant holds 2 workgroups per CU (registers)
-  }
-  int64_t max_by_rows = fc_cdiv(n_out > 0 ? n_out : 1, mfma_ok ? 512 : 2048);
-  if (s > max_by_rows) s = max_by_rows;
-  if (s > 256) s = 256;
-  if (s < 1) s = 1;
-  if ((flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK) s = (flags >> FC_CONV_S_SHIFT) & FC_CONV_S_MASK;         // tuning override
-  int64_t rps = fc_align(fc_cdiv(n_out > 0 ? n_out : 1, s), 64);
-  s = fc_cdiv(n_out > 0 ? n_out : 1, rps);
-  *S = (int)s;
-  *rows_per_split = rps;
-}
 
 // gW = sum of the S partial slabs, fixed order
 static int wgrad_reduce(const float* part, float* gW, int64_t elems, int S, hipStream_t stream) {
@@ -2261,11 +2132,20 @@ int fc_stem_conv_wgrad(const float* col, const float* gout, float* gW, int64_t n
   return FC_OK;
 }
 
+int fc_conv_wgrad_route(int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, int table_kind, int* out) {
+  if (!out || n_in < 0 || n_out < 0 || K < 1 || Cin < 1 || Cout < 1) return FC_EINVAL;
+  const WgradRoute r = wgrad_route({n_in, n_out, K, Cin, Cout}, flags, table_kind, route_env());
+  const int f[16] = {r.family, r.bm, r.bn, r.ko, r.bkr, r.table, r.mode, r.S, (int)(r.rps < 0x7fffffff ? r.rps : 0x7fffffff), r.wbuf, (int)r.grid_y};
+  for (int i = 0; i < 16; ++i) out[i] = f[i];
+  return r.family == FC_WFAM_INVALID ? FC_EINVAL : FC_OK;
+}
+
 int64_t fc_conv_wgrad_ws_bytes(int64_t n_out, int K, int Cin, int Cout, int flags) {
-  int S, S2; int64_t rps;
-  wgrad_plan(n_out, K, Cin, Cout, flags, false, &S, &rps);
-  wgrad_plan(n_out, K, Cin, Cout, flags, true, &S2, &rps);        // dense tables may take the multi-offset kernel
-  if (S2 > S) S = S2;
+  int S = 0;                                   // the caller's table kind is not known here: the largest split of any route the shape has
+  for (int table : {FC_TABLE_NONE, FC_TABLE_DENSE, FC_TABLE_PAIRS}) {      // (dense tables may take the multi-offset kernel)
+    const WgradRoute r = wgrad_route({n_out, n_out, K, Cin, Cout}, flags, table, route_env());
+    if (r.family != FC_WFAM_INVALID && r.S > S) S = r.S;
+  }
   return (int64_t)S * K * Cin * Cout * (int64_t)sizeof(float);
 }
 
@@ -2275,123 +2155,19 @@ static int conv_wgrad_impl(const float* in, const float* gout, const int* nbr, c
   AmaxHintScope hint_scope;
   if (n_in < 0 || n_out < 0 || K < 1 || Cin < 1 || Cout < 1) return FC_EINVAL;
   const int64_t elems = (int64_t)K * Cin * Cout;
-  if (n_out == 0) {
-    FC_HIP(hipMemsetAsync(gW, 0, elems * sizeof(float), stream));
-    return FC_OK;
+  if (n_out == 0) { FC_HIP(hipMemsetAsync(gW, 0, elems * sizeof(float), stream)); return FC_OK; }
+  const WgradRoute r = wgrad_route({n_in, n_out, K, Cin, Cout}, flags, cnt ? FC_TABLE_PAIRS : nbr ? FC_TABLE_DENSE : FC_TABLE_NONE, route_env());
+  if (r.family == FC_WFAM_INVALID) return FC_EINVAL;
+  if (ws_bytes < (int64_t)r.S * elems * (int64_t)sizeof(float)) return FC_EWS;
+  WgradArgs a = {in, gout, nbr, row_index, cnt, (r.S == 1) ? gW : (float*)ws, n_out, K, Cin, Cout, nullptr, nullptr, stream};
+  int rc = FC_OK;
+  if (r.mode == FC_MODE_H3) {                  // the operands' amax words: the caller's hints or passes of our own
+    rc = operand_amax(in, n_in * (int64_t)Cin, 0, stream, &a.amax_in);
+    if (rc == FC_OK) rc = operand_amax(gout, n_out * (int64_t)Cout, 1, stream, &a.amax_gout);
   }
-  if (!nbr && (K != 1 || n_in != n_out)) return FC_EINVAL;
-  int S; int64_t rps;
-  const bool dense_table = nbr && !cnt;
-  wgrad_plan(n_out, K, Cin, Cout, flags, dense_table, &S, &rps);
-  if (ws_bytes < (int64_t)S * elems * (int64_t)sizeof(float)) return FC_EWS;
-  float* part = (S == 1) ? gW : (float*)ws;
-  bool mfma_ok = !(flags & FC_CONV_FMA) && (Cin % 64 == 0) && (Cout % 64 == 0);
-  if (cnt && !mfma_ok) return FC_EINVAL;       // pair lists are an MFMA-path feature
-  // h3 (conv_x6.h): the k_wgrad_x6t launches below split both operands into two fp16 pieces, scaled by their amax words
-  const bool x6t = mfma_ok && (flags & FC_CONV_SPLIT) &&
-                   (wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table) || cnt || (!nbr && !cnt));
-  const bool h3 = x6t && split_mode() == 2;
-  // buffer addressing of both operands (wgrad_x6.h): below 2 GB each, row indices below 2^24; FC_CONV_FLAT: flat addresses (A/B, tests)
-  const int wbuf = (!(flags & FC_CONV_FLAT) && (uint64_t)n_in * (uint64_t)Cin * 4u < (1ull << 31) - 4096u && (uint64_t)n_out * (uint64_t)Cout * 4u < (1ull << 31) - 4096u &&
-                    n_in < (1 << 24) && n_out < (1 << 24) && (uint64_t)K * (uint64_t)n_out * 4u < (1ull << 31) - 4096u) ? 1 : 0;
-  const unsigned *am_a = nullptr, *am_g = nullptr;
-  if (h3) {
-    int rc = operand_amax(in, n_in * (int64_t)Cin, 0, stream, &am_a);
-    if (rc == FC_OK) rc = operand_amax(gout, n_out * (int64_t)Cout, 1, stream, &am_g);
-    if (rc != FC_OK) return rc;
-  }
-  if (!(flags & FC_CONV_FMA) && nbr && Cin == STEM_CIN && Cout == STEM_COUT && K <= 27) {
-    size_t smem = (size_t)(STEM_ROWS * STEM_JP + STEM_ROWS * 64) * sizeof(float);
-    k_stem_wgrad<<<(unsigned)S, 256, smem, stream>>>(in, gout, nbr, part, n_out, K, rps);
-  } else if (mfma_ok && wgrad_multi_ok(n_out, K, Cin, Cout, flags, dense_table)) {
-    const int bn = (Cout % 128 == 0) ? 128 : 64;
-    dim3 grid((unsigned)S, (unsigned)((K / WGRAD_KO) * (Cin / 64) * (Cout / bn)));
-    if (flags & FC_CONV_SPLIT) {                 // split-bf16 (wgrad_x6.h)
-      if (g_bf16_fast && bn == 128) k_wgrad_x6t<64, 128, WGRAD_KO, false, 1><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
-      else if (g_bf16_fast) k_wgrad_x6t<64, 64, WGRAD_KO, false, 1><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
-      else if (h3 && bn == 128) k_wgrad_x6t<64, 128, WGRAD_KO, false, 2><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, am_a, am_g, wbuf);
-      else if (h3) k_wgrad_x6t<64, 64, WGRAD_KO, false, 2><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, am_a, am_g, wbuf);
-      else if (bn == 128) k_wgrad_x6t<64, 128, WGRAD_KO, false><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
-      else k_wgrad_x6t<64, 64, WGRAD_KO, false><<<grid, 256, 0, stream>>>(in, gout, nbr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);
-    } else
-    if (bn == 128) k_wgrad_multi<128, WGRAD_KO><<<grid, 256, 0, stream>>>(in, gout, nbr, part, n_out, K, Cin, Cout, rps);
-    else k_wgrad_multi<64, WGRAD_KO><<<grid, 256, 0, stream>>>(in, gout, nbr, part, n_out, K, Cin, Cout, rps);
-  } else if (mfma_ok && cnt && (flags & FC_CONV_SPLIT)) {
-    // split-bf16 over the pair lists (r3 nbench: 128 x 128 tiles 119 -> 95 us on 15k rows 128->128, 111 -> 89 / 109 -> 87 on
-    // the 256- and 512-channel levels; 64 x 64 tiles — one accumulator per wave, a dependent MFMA chain — lost to the fp32
-    // kernel with the r3 kernel and win with k_wgrad_x6t).  128-channel Cin tiles only while they still fill the
-    // chip (862 rows, 512->128: 216 workgroups of 128 x 128 tiles 49 us, fp32 36 us)
-    const int bn = (Cout % 128 == 0) ? 128 : 64;
-    int bm = (Cin % 128 == 0) ? 128 : 64;
-    if (bm == 128 && bn == 128 && (int64_t)S * K * (Cin / 128) * (Cout / 128) < 512) bm = 64;
-    dim3 grid((unsigned)S, (unsigned)(K * (Cin / bm) * (Cout / bn)));
-#define FC_WX6(BM_, BN_)                                                                                                             \
-  do {                                                                                                                               \
-    if (g_bf16_fast) k_wgrad_x6t<BM_, BN_, 1, true, 1><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf); \
-    else if (h3) k_wgrad_x6t<BM_, BN_, 1, true, 2><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps, am_a, am_g, wbuf); \
-    else k_wgrad_x6t<BM_, BN_, 1, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf); \
-  } while (0)
-    if (bm == 128 && bn == 128) FC_WX6(128, 128);
-    else if (bm == 128) FC_WX6(128, 64);
-    else if (bn == 128) FC_WX6(64, 128);
-    else FC_WX6(64, 64);
-#undef FC_WX6
-  } else if (mfma_ok && !nbr && !cnt && (flags & FC_CONV_SPLIT)) {
-    // table-free dense GEMM gW = in^T gout over the rows (K = 1): the same kernel with the row itself as the index
-    const int bn = (Cout % 128 == 0) ? 128 : 64;
-    int bm = (Cin % 128 == 0) ? 128 : 64;
-    if (bm == 128 && bn == 128 && (int64_t)S * (Cin / 128) * (Cout / 128) < 512) bm = 64;
-    dim3 grid((unsigned)S, (unsigned)(K * (Cin / bm) * (Cout / bn)));
-#define FC_WX6D(BM_, BN_)                                                                                                              \
-  do {                                                                                                                                \
-    if (g_bf16_fast) k_wgrad_x6t<BM_, BN_, 1, false, 1><<<grid, 256, 0, stream>>>(in, gout, nullptr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf); \
-    else if (h3) k_wgrad_x6t<BM_, BN_, 1, false, 2><<<grid, 256, 0, stream>>>(in, gout, nullptr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, am_a, am_g, wbuf); \
-    else k_wgrad_x6t<BM_, BN_, 1, false><<<grid, 256, 0, stream>>>(in, gout, nullptr, nullptr, nullptr, part, n_out, K, Cin, Cout, rps, nullptr, nullptr, wbuf);   \
-  } while (0)
-    if (bm == 128 && bn == 128) FC_WX6D(128, 128);
-    else if (bm == 128) FC_WX6D(128, 64);
-    else if (bn == 128) FC_WX6D(64, 128);
-    else FC_WX6D(64, 64);
-#undef FC_WX6D
-  } else if (mfma_ok) {
-    int bm, bn;
-    wgrad_tiles(Cin, Cout, flags, &bm, &bn);
-    if (cnt) bm = 64;
-    dim3 grid((unsigned)S, (unsigned)(K * (Cin / bm) * (Cout / bn)));
-    const bool deep = (flags & FC_CONV_WGRAD_DEEP) && bm == 64 && nbr;          // 64-row chunks (tuning flag)
-    // k_wgrad_mfma_p where it measured ahead (r2 nbench, same box: pair lists with 128-wide gout tiles +3..7 %; 64-wide
-    // tiles -5 %, dense tables -7..13 %).  FC_CONV_WGRAD_PIPE_OFF: never, _ON: wherever it applies (tests / A-B).
-    const bool wpipe = bm == 64 && !(flags & FC_CONV_WGRAD_DEEP) && !(flags & FC_CONV_WGRAD_PIPE_OFF) &&
-                       ((flags & FC_CONV_WGRAD_PIPE_ON) || (cnt && bn == 128));
-    if (wpipe && cnt) {
-      if (bn == 128) k_wgrad_mfma_p<128, true, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-      else k_wgrad_mfma_p<64, true, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-    } else if (wpipe && nbr) {
-      if (bn == 128) k_wgrad_mfma_p<128, true, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-      else k_wgrad_mfma_p<64, true, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-    } else if (wpipe) {
-      if (bn == 128) k_wgrad_mfma_p<128, false, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-      else k_wgrad_mfma_p<64, false, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-    } else
-    if (cnt) {
-      if (bn == 128) k_wgrad_mfma<64, 128, true, 32, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-      else k_wgrad_mfma<64, 64, true, 32, true><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-    } else
-    if (deep) {
-      if (bn == 128) k_wgrad_mfma<64, 128, true, 64, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-      else k_wgrad_mfma<64, 64, true, 64, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps);
-    } else
-    if (bm == 128 && bn == 128) { if (nbr) k_wgrad_mfma<128, 128, true, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); else k_wgrad_mfma<128, 128, false, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); }
-    else if (bm == 128) { if (nbr) k_wgrad_mfma<128, 64, true, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); else k_wgrad_mfma<128, 64, false, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); }
-    else if (bn == 128) { if (nbr) k_wgrad_mfma<64, 128, true, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); else k_wgrad_mfma<64, 128, false, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); }
-    else { if (nbr) k_wgrad_mfma<64, 64, true, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); else k_wgrad_mfma<64, 64, false, 32, false><<<grid, 256, 0, stream>>>(in, gout, nbr, row_index, cnt, part, n_out, K, Cin, Cout, rps); }
-  } else {
-    dim3 grid((unsigned)S, (unsigned)K);
-    k_wgrad_fma<<<grid, 256, 0, stream>>>(in, gout, nbr, part, n_out, K, Cin, Cout, rps);
-  }
-  FC_CHECK_LAUNCH();
-  if (S > 1) return wgrad_reduce(part, gW, elems, S, stream);
-  return FC_OK;
+  if (rc == FC_OK) rc = launch_wgrad(r, a);
+  if (rc == FC_OK && r.S > 1) rc = wgrad_reduce(a.part, gW, elems, r.S, stream);
+  return rc;
 }
 
 int fc_conv_wgrad(const float* in, const float* gout, const int* nbr, const int* row_index, float* gW, int64_t n_in,
@@ -2404,8 +2180,7 @@ int fc_conv_wgrad_pairs(const float* in, const float* gout, const int* pair_in, 
                         float* gW, int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, void* ws,
                         int64_t ws_bytes, hipStream_t stream) {
   if (!pair_in || !pair_out || !pair_cnt) return FC_EINVAL;
-  return conv_wgrad_impl(in, gout, pair_in, pair_out, pair_cnt, gW, n_in, n_out, K, Cin, Cout, flags & ~FC_CONV_WGRAD_DEEP, ws,
-                         ws_bytes, stream);
+  return conv_wgrad_impl(in, gout, pair_in, pair_out, pair_cnt, gW, n_in, n_out, K, Cin, Cout, flags, ws, ws_bytes, stream);
 }
 
 int fc_transpose_weight(const float* W, float* Wt, int K, int Cin, int Cout, hipStream_t stream) {

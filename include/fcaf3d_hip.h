@@ -33,9 +33,10 @@ extern "C" {
  * r6 -> 6 (fc_compact_rows takes the output capacity; fc_plan_*, fc_argsort27 added), r6 -> 7 (fc_set_split_mode / fc_get_split_mode / fc_amax /
  * fc_conv_amax_hint / fc_amax_out_hint added; weight images are mode-dependent and fc_x6_weight_images writes their amax word), -> 8
  * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation), -> 9 (fc_norm_act_maxpool8_fwd / fc_maxpool8_norm_act_bwd / fc_inverse_rows / fc_norm_act_add_fwd /
- * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates).  A caller built against another
+ * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates), -> 10 (fc_conv_fwd_route /
+ * fc_conv_wgrad_route added: the launch a convolution call becomes, as data).  A caller built against another
  * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 9
+#define FC_ABI_VERSION 10
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -320,6 +321,32 @@ int fc_stem_conv_wgrad(const float* col, const float* gout, float* gW, int64_t n
 /* (K,Cin,Cout) -> (K,Cout,Cin): the W[k]^T of ME's backward-data rule `gin[i] += gout[o] @ W[k]^T` (SURVEY.md Appendix A.3;
  * autograd of me_resnet.py:56-62), so that the pass runs through fc_conv_fwd on the transposed table. */
 int fc_transpose_weight(const float* W, float* Wt, int K, int Cin, int Cout, hipStream_t stream);
+
+/* Which launch a convolution call becomes (No reference counterpart: ME chooses its kernels inside MinkowskiConvolution, the call
+ * sites are me_resnet.py:56-62).  Pure host functions, no GPU needed: the route the entry points above compute before they launch
+ * (csrc/conv_route.h), under the CURRENT fc_set_split_mode / fc_set_bf16_fast / fc_debug_set_h3r settings, written as 16 ints
+ * (unused ones 0).  Return 0, or -1 exactly where the launch would (then out[0] = the INVALID family).
+ * table_kind: FC_TABLE_* — none (nbr == NULL), a dense neighbour table, a table in sorted-row order (out_index), pair lists; for
+ * fc_conv_fwd_route | FC_TABLE_STATS: the call asks for the statistics epilogue (fc_conv_fwd_stats and its kin), and live_tiles as
+ * in fc_conv_fwd_pairs_tiles.  out[] of fc_conv_fwd_route, by FC_ROUTE_*: kernel family (FC_FAM_*), tile rows, tile columns, waves
+ * along the rows, S = partial sums in the workspace (1: none), weight operand (FC_WSRC_*: fp32, fp32 read transposed, pre-split
+ * image), arithmetic (FC_MODE_*: fp32, six bf16 products, bf16-fast, h3), buffer (1) / flat (0) addressing, where a statistics
+ * epilogue runs (FC_EPI_*: not on this route, in the kernel, in the sum pass), the grid.  out[] of fc_conv_wgrad_route, by
+ * FC_WROUTE_*: family (FC_WFAM_*), Cin tile, Cout tile, offsets per workgroup, rows per chunk, table kind, arithmetic, S = row
+ * ranges, rows per range, buffer addressing, grid.y (grid.x = S). */
+enum { FC_TABLE_NONE, FC_TABLE_DENSE, FC_TABLE_SORTED, FC_TABLE_PAIRS, FC_TABLE_STATS = 8 };
+enum { FC_FAM_INVALID, FC_FAM_STEM, FC_FAM_FMA, FC_FAM_MFMA, FC_FAM_MFMA_P, FC_FAM_GLDS, FC_FAM_X6, FC_FAM_H3R };
+enum { FC_WFAM_INVALID, FC_WFAM_STEM, FC_WFAM_FMA, FC_WFAM_MFMA, FC_WFAM_MFMA_P, FC_WFAM_MULTI, FC_WFAM_X6T };
+enum { FC_WSRC_FP32, FC_WSRC_FP32_T, FC_WSRC_IMAGE };
+enum { FC_MODE_FP32, FC_MODE_SIX, FC_MODE_BF16, FC_MODE_H3 };
+enum { FC_EPI_NONE, FC_EPI_KERNEL, FC_EPI_SUM };
+enum { FC_ROUTE_FAMILY, FC_ROUTE_BM, FC_ROUTE_BN, FC_ROUTE_WM, FC_ROUTE_S, FC_ROUTE_WSRC, FC_ROUTE_MODE, FC_ROUTE_BUF, FC_ROUTE_EPI,
+       FC_ROUTE_GRID_X, FC_ROUTE_GRID_Y, FC_ROUTE_GRID_Z };
+enum { FC_WROUTE_FAMILY, FC_WROUTE_BM, FC_WROUTE_BN, FC_WROUTE_KO, FC_WROUTE_BKR, FC_WROUTE_TABLE, FC_WROUTE_MODE, FC_WROUTE_S,
+       FC_WROUTE_RPS, FC_WROUTE_WBUF, FC_WROUTE_GRID_Y };
+int fc_conv_fwd_route(int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, int table_kind, int64_t live_tiles,
+                      int* out);
+int fc_conv_wgrad_route(int64_t n_in, int64_t n_out, int K, int Cin, int Cout, int flags, int table_kind, int* out);
 
 /* ---- normalisation / pooling / rows ------------------------------------------------------- */
 

@@ -75,3 +75,72 @@ def test_statistics_table_sizes_fit_the_executors_arena_bound():
                     assert nb <= 64, (n, nb)      # up to 4 096 rows: at most 64 row blocks -> the BatchNorm behind it is ONE launch
     assert L.query('fc_conv_stats_blocks', 1000, 27, 64, 64, 0, 0) == 0                # fp32 route: no statistics epilogue
     assert L.query('fc_conv_stats_blocks', 1000, 27, 3, 64, X6, 0) == 0                # stem shape: not an MFMA launch
+
+
+# ---- the route queries (fc_conv_fwd_route / fc_conv_wgrad_route, csrc/conv_route.h) -------------------------------------------------
+
+def _route_grid():
+    """the shapes and flag words the size queries were compared on against the parent of the route refactor (profiles/r7_notes.md)"""
+    import itertools
+    import fcaf3d_amd.functional as Fn
+    X6 = Fn.CONV_SPLIT | Fn.CONV_IMAGE
+    n_out = (1, 50, 64, 65, 511, 512, 862, 3500, 4095, 4096, 6900, 14900, 32767, 32768, 55000, 64000, 98304, 262144, 441000, 580000)
+    chans = ((3, 64), (64, 64), (64, 128), (128, 64), (128, 128), (256, 256), (512, 128), (48, 64), (64, 96))
+    flags = (0, Fn.CONV_SPLIT, X6, Fn.CONV_FMA, X6 | Fn.CONV_FLAT, Fn.CONV_PIPE_ON, Fn.CONV_PIPE_OFF, Fn.CONV_GLDS, Fn.CONV_GLDS_OFF,
+             Fn.CONV_WGRAD_MULTI_OFF, Fn.CONV_WGRAD_MULTI_FIRST, Fn.CONV_SPLIT | Fn.CONV_WGRAD_MULTI_OFF,
+             1 << Fn.CONV_BM_SHIFT, 2 << Fn.CONV_BM_SHIFT, 3 << Fn.CONV_BM_SHIFT, 1 << Fn.CONV_BN_SHIFT, 2 << Fn.CONV_BN_SHIFT,
+             5 << Fn.CONV_S_SHIFT)
+    return itertools.product(n_out, (1, 8, 27), chans, flags)
+
+
+def test_size_queries_agree_with_the_route_queries():
+    """fc_conv_fwd_ws_bytes, fc_conv_stats_blocks and fc_conv_wgrad_ws_bytes are read off the route the launch will take: over the
+    whole grid, in both split modes, they equal what fc_conv_fwd_route / fc_conv_wgrad_route report"""
+    E = L.header_enums()
+    l = L.lib()
+    try:
+        for mode in (0, 2):
+            assert l.fc_set_split_mode(mode) == 0
+            for n, K, (ci, co), f in _route_grid():
+                _, r = L.route('fc_conv_fwd_route', n, n, K, ci, co, f, E['FC_TABLE_DENSE'], 0)
+                assert l.fc_conv_fwd_ws_bytes(n, K, ci, co, f) == (r['s'] * n * co * 4 if r['s'] > 1 else 0), (mode, n, K, ci, co, f, r)
+                assert (l.fc_conv_stats_blocks(n, K, ci, co, f, 0) > 0) == (r['epi'] != E['FC_EPI_NONE']), (mode, n, K, ci, co, f, r)
+                _, rp = L.route('fc_conv_fwd_route', n, n, K, ci, co, f, E['FC_TABLE_PAIRS'], 0)
+                assert (l.fc_conv_stats_blocks(n, K, ci, co, f, 1) > 0) == (rp['epi'] != E['FC_EPI_NONE']), (mode, n, K, ci, co, f, rp)
+                splits = [w['s'] for rc, w in (L.route('fc_conv_wgrad_route', n, n, K, ci, co, f, E[t])
+                                               for t in ('FC_TABLE_NONE', 'FC_TABLE_DENSE', 'FC_TABLE_PAIRS')) if rc == 0]
+                assert l.fc_conv_wgrad_ws_bytes(n, K, ci, co, f) == max(splits) * K * ci * co * 4, (mode, n, K, ci, co, f, splits)
+    finally:
+        l.fc_set_split_mode(2)
+
+
+def test_route_queries_refuse_what_the_launch_refuses():
+    """fc_conv_fwd_route / fc_conv_wgrad_route return -1 exactly for the calls the entry points answer with -1"""
+    import fcaf3d_amd.functional as Fn
+    E = L.header_enums()
+    X6 = Fn.CONV_SPLIT | Fn.CONV_IMAGE
+    NONE, DENSE, SORTED, PAIRS, STATS = (E['FC_TABLE_' + k] for k in ('NONE', 'DENSE', 'SORTED', 'PAIRS', 'STATS'))
+    fwd = lambda *a: L.route('fc_conv_fwd_route', *a)[0]
+    wgrad = lambda *a: L.route('fc_conv_wgrad_route', *a)[0]
+    n = 1000
+    # transposed weights need a table
+    assert fwd(n, n, 1, 64, 64, Fn.CONV_WT, NONE, 0) == -1 and fwd(n, n, 1, 64, 64, 0, NONE, 0) == 0
+    assert fwd(n, n, 27, 64, 64, Fn.CONV_WT, DENSE, 0) == 0
+    # a table-free launch is the identity map
+    assert fwd(n, n, 27, 64, 64, 0, NONE, 0) == -1 and fwd(n + 1, n, 1, 64, 64, 0, NONE, 0) == -1
+    assert wgrad(n, n, 27, 64, 64, 0, NONE) == -1 and wgrad(n, n, 1, 64, 64, 0, NONE) == 0
+    # sorted-row tables and weight images are MFMA-path features
+    for ci, f in ((48, 0), (64, Fn.CONV_FMA)):
+        assert fwd(n, n, 27, ci, 64, f, DENSE, 0) == 0
+        assert fwd(n, n, 27, ci, 64, f, SORTED, 0) == -1
+        assert fwd(n, n, 27, ci, 64, f | X6, DENSE, 0) == -1
+    assert fwd(n, n, 27, 64, 64, X6, SORTED, 0) == 0
+    # statistics: the split route only
+    assert fwd(n, n, 27, 64, 64, 0, DENSE | STATS, 0) == -1 and fwd(n, n, 27, 64, 64, 0, PAIRS | STATS, 0) == -1
+    assert fwd(n, n, 27, 48, 64, X6, DENSE | STATS, 0) == -1 and fwd(n, n, 27, 3, 64, X6, DENSE | STATS, 0) == -1
+    assert fwd(n, n, 27, 64, 64, X6, DENSE | STATS, 0) == 0 and fwd(n, n, 27, 64, 64, X6, PAIRS | STATS, 37) == 0
+    # pair lists: MFMA shapes only
+    assert fwd(n, n, 27, 48, 64, 0, PAIRS, 0) == -1 and fwd(n, n, 27, 64, 96, 0, PAIRS, 0) == -1 and fwd(n, n, 27, 32, 64, 0, PAIRS, 0) == 0
+    assert wgrad(n, n, 27, 48, 64, 0, PAIRS) == -1 and wgrad(n, n, 27, 64, 64, Fn.CONV_FMA, PAIRS) == -1 and wgrad(n, n, 27, 64, 64, 0, PAIRS) == 0
+    assert wgrad(n, n, 27, 64, 64, 0, SORTED) == -1          # (row_index of fc_conv_wgrad is reserved)
+    assert L.route('fc_conv_fwd_route', n, n, 27, 48, 64, 0, PAIRS, 0)[1]['family'] == E['FC_FAM_INVALID']

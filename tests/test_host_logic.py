@@ -267,6 +267,7 @@ def test_committed_profile_tables_follow_from_the_committed_traces():
 DEVICE_IDENTICAL_SOURCES = {
     '66ec67355c91a62d': '5b97211d4d40026d',      # retired A/B switches, named FC_CONV_* flag bits
     'f17a9bc9f17e6a93': '7094ae11604f2248',      # csrc/exec_ops.h: the executor's row and descriptor layouts by name (host code only)
+    'db8f1d2038ec0dfd': '7094ae11604f2248',      # csrc/conv_route.h: every convolution launch's route decided once, as data (host code only)
 }
 
 
@@ -309,3 +310,64 @@ def test_r6_profiles_were_taken_on_device_identical_kernels():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     traffic = json.load(open(os.path.join(root, 'profiles', 'r6_traffic.json')))
     assert line['roofline']['traffic'] == round(traffic['hbm_bytes_per_launch'])
+
+
+def test_recorded_routing_decisions():
+    """The routing decisions the measurement comments of csrc/conv_route.h record, as facts of fc_conv_fwd_route /
+    fc_conv_wgrad_route (pure host functions): the benchmark's levels under the default switches (split mode 2, h3r 1, bf16-fast
+    off), the same with flat addressing, and what each process-global switch changes."""
+    import fcaf3d_amd.functional as Fn
+    from fcaf3d_amd import _lib as L
+    E = L.header_enums()
+    X6, DENSE = Fn.CONV_SPLIT | Fn.CONV_IMAGE, E['FC_TABLE_DENSE']
+    l = L.lib()
+    assert (l.fc_get_split_mode(), l.fc_set_bf16_fast(0), l.fc_debug_set_h3r(1)) == (2, 0, 0)
+
+    def fwd(n, K, ci, co, flags):
+        rc, r = L.route('fc_conv_fwd_route', n, n, K, ci, co, flags, DENSE, 0)
+        assert rc == 0
+        return r
+
+    def expect(r, **want):
+        want = {k: E[v] if isinstance(v, str) else v for k, v in want.items()}
+        assert {k: r[k] for k in want} == want, (r, want)
+
+    big, mid = (441000, 27, 64, 64, X6), (55000, 27, 128, 128, X6)
+    for flat in (0, Fn.CONV_FLAT):
+        buf = 0 if flat else 1
+        expect(fwd(*big[:4], X6 | flat), family='FC_FAM_X6', bm=128, bn=64, mode='FC_MODE_H3', wsrc='FC_WSRC_IMAGE', buf=buf, s=1, epi='FC_EPI_KERNEL')
+        expect(fwd(*mid[:4], X6 | flat), family='FC_FAM_H3R', bm=128, bn=128, mode='FC_MODE_H3', buf=buf, s=1, epi='FC_EPI_KERNEL')
+        expect(fwd(6900, 27, 256, 256, X6 | flat), family='FC_FAM_H3R', bm=128, bn=128, buf=buf, s=9, epi='FC_EPI_SUM')
+        expect(fwd(50, 27, 64, 64, X6 | flat), family='FC_FAM_X6', bm=128, bn=64, buf=buf, s=27, epi='FC_EPI_SUM')
+        expect(fwd(441000, 27, 64, 64, flat), family='FC_FAM_MFMA_P', bm=256, bn=64, wm=4, s=1, mode='FC_MODE_FP32', buf=0, epi='FC_EPI_NONE')
+        for n in (1, 1000, 580000):
+            expect(fwd(n, 27, 3, 64, X6 | flat), family='FC_FAM_STEM')
+        expect(fwd(1000, 27, 48, 64, flat), family='FC_FAM_FMA')
+    assert fwd(*big[:4], X6 | Fn.CONV_FLAT) == dict(fwd(*big), buf=0) and fwd(*mid[:4], X6 | Fn.CONV_FLAT) == dict(fwd(*mid), buf=0)
+
+    rc, w = L.route('fc_conv_wgrad_route', 441000, 441000, 27, 64, 64, Fn.CONV_SPLIT, DENSE)
+    assert rc == 0
+    expect(w, family='FC_WFAM_X6T', bm=64, bn=64, ko=3, mode='FC_MODE_H3', s=56, rps=7936, table=DENSE)
+
+    # the process-global switches, each restored afterwards
+    try:
+        assert l.fc_set_split_mode(0) == 0
+        expect(fwd(*big), family='FC_FAM_X6', bm=128, bn=64, mode='FC_MODE_SIX', buf=1)
+        expect(fwd(*mid), family='FC_FAM_X6', bm=128, bn=128, mode='FC_MODE_SIX', buf=1)
+    finally:
+        l.fc_set_split_mode(2)
+    try:
+        assert l.fc_set_bf16_fast(1) == 0 and l.fc_get_split_mode() == 0          # (mode 0 implied)
+        expect(fwd(*big), family='FC_FAM_X6', bm=128, bn=64, mode='FC_MODE_BF16', buf=0)
+        expect(fwd(*mid), family='FC_FAM_X6', bm=128, bn=128, mode='FC_MODE_BF16', buf=0)
+    finally:
+        l.fc_set_bf16_fast(0)
+    try:
+        assert l.fc_debug_set_h3r(0) == 0
+        expect(fwd(*mid), family='FC_FAM_X6', bm=128, bn=128, mode='FC_MODE_H3', buf=1)
+        assert l.fc_debug_set_h3r(2) == 0
+        expect(fwd(*big), family='FC_FAM_H3R', bm=128, bn=64, mode='FC_MODE_H3', buf=1)
+    finally:
+        l.fc_debug_set_h3r(1)
+    expect(fwd(*big), family='FC_FAM_X6', mode='FC_MODE_H3')
+    expect(fwd(*mid), family='FC_FAM_H3R', mode='FC_MODE_H3')
