@@ -118,6 +118,14 @@ class NetProgram:
         self.map_names = {}
         self.grad_refs = []         # (addr index, float offset into the gradient buffer)
         self.keep = []              # tensors that must outlive the program build (persistent buffers)
+        # what the walk records for the runtime, each a (tensor, rows dim, C) unless said otherwise
+        self.relu_outs = []         # every fused norm + ReLU output, forward order (decisions)
+        self.pool_arg = None        # the stem pool's arg-max rows (decisions)
+        self.out_idx = None         # (cent_all, bbox_all, cls_all, cmax_all): the tensors of all head locations
+        self.gout_idx = self.x0_idx = ()        # training: the dyn indices of the three loss gradients; tail0: the finest level's union
+        self.in_sums = None         # training: the stem instance norm's (B, 2 x 64) d beta / d gamma sums (backward arena)
+        self.small = []             # normalisation layers in BACKWARD emission order: (sums address | None, nseg dim | None, C, weight, bias)
+        self._pready = {}           # id(parameter) -> number of backward operators after which its gradient is final
         self._params = [p for p in det.parameters() if p.requires_grad]
         self._goff, off = {}, 0
         flat = getattr(self._params[0], '_fc_flat', None)
@@ -132,7 +140,7 @@ class NetProgram:
         self._gtotal = self.flat.n if self.flat is not None else off
         self._sig = self.signature(det)
         self._build_weights()
-        self._build()
+        self._build(_Emitter(self))
         self._finalise()
 
     @staticmethod
@@ -206,29 +214,6 @@ class NetProgram:
             w, p1 = layout[k]
             row[w] = v + 1 if p1 else v
 
-    # ---- r6: amax words of the convolutions' operands (csrc/conv_x6.h "h3": the scale of the two-piece fp16 split) ------------
-    # One fc_amax pass per operand TENSOR and stream instead of one per consuming launch: a forward activation's word serves its
-    # forward convolution(s) and, a pass later, their weight gradients; a gradient's word serves the backward-data convolution and the
-    # weight gradient of its layer.  Slots are 2 KB of one persistent buffer (32 sub-words, fc_common.h; fc_amax returns its scratch words to zero).
-    AMAX_SLOTS = 1024
-    AMAX_SLOT_BYTES = 2048           # include/fcaf3d_hip.h FC_AMAX_SLOT_BYTES: 32 sub-words at a 64-byte stride
-
-    def amax_slot(self):
-        if getattr(self, '_amax_buf', None) is None:
-            self._amax_buf = torch.zeros(self.AMAX_SLOTS * self.AMAX_SLOT_BYTES // 4, dtype=torch.int32, device=self.dev)
-            self._amax_used = 0
-            self.keep.append(self._amax_buf)
-        assert self._amax_used < self.AMAX_SLOTS
-        i = self.SA(self._amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * self._amax_used)
-        self._amax_used += 1
-        return i
-
-    def amax_op(self, lst, stream, x, rows, cols):
-        """emit the amax pass of tensor x ((rows, cols) floats) on `stream` -> address index of its word"""
-        slot = self.amax_slot()
-        self.emit(lst, OP_AMAX, stream, x=x, n=self.D(rows), c=cols, slot=slot)
-        return slot
-
     # ---- weights: pre-split images of every kernel, incl. the packed head kernel and the generative convolutions' GEMM form; ONE
     # set per detector, shared by its programs (training / inference, stream configurations, pruned-tail variant)
     def _build_weights(self):
@@ -255,450 +240,31 @@ class NetProgram:
         return self.S(v[1 if transposed else 0])
 
     # ---- program ---------------------------------------------------------------------------------------------------------
-    def _build(self):
-        det = self.det
-        bb, nh = det.backbone, det.neck_with_head
-        tr = self.training
-        F, Bk = self.ops_f, self.ops_b
-        tape = []                        # (stream, backward emitter) in forward order
-        self.relu_outs = []              # (tensor, rows dim, C) of every fused norm + ReLU output, forward order (NetProgram.decisions)
-        self.small = []                  # (sums address index or dyn name, nseg dim name or None, C, weight param, bias param)
-        relu, elu, none = Fn.ACT['relu'], Fn.ACT['elu'], Fn.ACT['none']
-        grad = {}                        # forward tensor -> gradient tensor (backward arena)
-        head_grads = {}                  # forward tensor -> (gradient from its head branch on the head stream, level)
-        self._pready = {}                # id(parameter) -> number of backward operators after which its gradient is final
-        small_rows = []                  # normalisation layers in BACKWARD emission order: (sums address | None, nseg dim, C, weight, bias)
-        flushed = [0]
-
-        head_lvl = [None]                # the neck level whose head branch (S_HEAD) is being emitted, None: main chain
-        head_written = {}                # level -> parameters whose gradient is written on S_HEAD by that branch
-
-        def wrote(*params):
-            for prm in params:
-                self._pready[id(prm)] = len(Bk)
-            if head_lvl[0] is not None:
-                # written on the head stream (or behind it): final for a data-parallel bucket only once the MAIN stream has
-                # joined this branch (take(): OP_WAIT EV_HB + level) — GradientAverager.launch_next orders the collective behind
-                # the main and the weight-gradient stream, not behind S_HEAD
-                head_written.setdefault(head_lvl[0], []).extend(params)
-
-        def flush_small(stream):
-            """the d gamma / d beta sums of the normalisation layers whose backward has been emitted since the last flush -> their
-            gradient slices (one launch); called where a group of layers ends, so that a data-parallel bucket is complete early"""
-            n = len(small_rows) - flushed[0]
-            if n:
-                self.emit(Bk, OP_SMALL_GRADS, stream, desc=self.DY('small_desc'), first=2 * flushed[0], count=2 * n)
-                for _, _, _, w_, b_ in small_rows[flushed[0]:]:
-                    wrote(w_, b_)
-                flushed[0] = len(small_rows)
-        head_wgrads = [0]
-
-        def head_wfin(stream):
-            lo = 1 if self.tail0 else 0
-            self.emit(Bk, OP_HEAD_WFIN, stream, part=self.SA(head_part[lo].data_ptr()), nl=self.nl - lo, r=Cn, ld=64, n_reg=n_reg, n_cls=n_cls,
-                      g_cent=self.G(nh.centerness_conv.kernel), g_reg=self.G(nh.reg_conv.kernel), g_cls=self.G(nh.cls_conv.kernel),
-                      bias_part=self.SA(bias_part[lo].data_ptr()), g_bias=self.G(nh.cls_conv.bias))
-            wrote(nh.centerness_conv.kernel, nh.reg_conv.kernel, nh.cls_conv.kernel, nh.cls_conv.bias)
-
-        def wstream(cur):
-            return S_WGRAD if self.wgrad_async else cur
-
-        grad2 = {}                       # forward tensor -> (second gradient contribution, rows, cols, stream), not yet added
-
-        def flush2(t):
-            g2, rows, cols, stream = grad2.pop(t)
-            self.emit(Bk, OP_ADD, stream, dst=grad[t], src=g2, n=self.D(rows), c=cols)
-            grad_src.pop(grad[t], None)          # added to in place: no longer the plain result of the convolution that wrote it
-            amax_of.pop(grad[t], None)           # ... nor bounded by its producer's amax word
-
-        def accumulate(t, g, rows, cols, stream):
-            """gradient `g` (a backward tensor) arrives for forward tensor t.  The SECOND contribution is kept aside: if the
-            consumer of the sum is a BatchNorm backward it adds the two on the fly (norm.hip gy2) and no add pass runs; a third
-            arrival, or any other consumer, adds the first two as before (same operands, same order: same bits)"""
-            if t not in grad:
-                grad[t] = g
-            elif Fn.BN_FUSE and t not in grad2:
-                grad2[t] = (g, rows, cols, stream)
-            else:
-                if t in grad2:
-                    flush2(t)
-                self.emit(Bk, OP_ADD, stream, dst=grad[t], src=g, n=self.D(rows), c=cols)
-                grad_src.pop(grad[t], None)
-                amax_of.pop(grad[t], None)
-
-        def take(t, rows, cols, pair=False):
-            """the complete gradient of forward tensor t, for the emitter of the operator that produced t (main stream); pair:
-            the caller adds a second contribution itself -> (gradient, second contribution | None)"""
-            if t in head_grads:
-                g, lvl = head_grads.pop(t)
-                self.emit(Bk, OP_WAIT, S_MAIN, event=EV_HB + lvl)          # the head branch of this level has delivered
-                for prm in head_written.pop(lvl, ()):
-                    self._pready[id(prm)] = max(self._pready[id(prm)], len(Bk))
-                accumulate(t, g, rows, cols, S_MAIN)
-            if pair:
-                return grad[t], (grad2.pop(t)[0] if t in grad2 else None)
-            if t in grad2:
-                flush2(t)
-            return grad[t]
-
-        def got(t):
-            """grad[t] for a consumer on the tensor's own (head) stream"""
-            if t in grad2:
-                flush2(t)
-            return grad[t]
-
-        def emit_wgrad(cur, **fields):
-            if self.wgrad_async:
-                ev = EV_W0 if cur == S_MAIN else EV_W1
-                self.emit(Bk, OP_RECORD, cur, event=ev)
-                self.emit(Bk, OP_WAIT, S_WGRAD, event=ev)
-            self.emit(Bk, OP_WGRAD, wstream(cur), **fields)
-
-        AMAX = Fn.X6 and Fn.split_mode() == 2          # the convolutions scale their operands by their amax words (csrc/conv_x6.h h3)
-        amax_f = {}                      # (forward tensor, stream) -> address index of its amax word
-        amax_of = {}                     # tensor -> address index of the amax word its PRODUCER folds into (fc_amax_out_hint)
-        if AMAX:
-            # the words the producers fold into start every pass at zero: one fill per direction, its size patched in below
-            self.amax_slot()             # (slot 0 doubles as the buffer's base address)
-            self.emit(F, OP_CLEAR, S_MAIN, dst=self.SA(self._amax_buf.data_ptr()), bytes=0)
-
-        def fwd_amax(x, rows, cols, stream):
-            if not AMAX:
-                return -1
-            if x in amax_of:
-                return amax_of[x]
-            if (x, stream) not in amax_f:
-                amax_f[(x, stream)] = self.amax_op(F, stream, x, rows, cols)
-            return amax_f[(x, stream)]
-
-        producer = {}                    # forward tensor -> (index of the OP_CONV that wrote it, rows, columns)
-        grad_src = {}                    # backward tensor -> (index in Bk of the backward-data OP_CONV that wrote it, rows, columns, stream)
-
-        def conv(x, mod, mname, rows_in, rows_out, stream=S_MAIN):
-            """MinkowskiConvolution on a kernel map (functional._SparseConv)"""
-            Cin, Cout = mod.in_channels, mod.out_channels
-            y = self.T(rows_out, Cout)
-            m = self.M(mname)
-            ax = fwd_amax(x, rows_in, Cin, stream)
-            self.emit(F, OP_CONV, stream, x=x, img=self.IMG(mod.kernel, False), map=m, dir=0, out=y, n=-1, cin=Cin, cout=Cout, amax_x=ax)
-            producer[y] = (len(F) - 1, rows_out, Cout)
-            if tr:
-                def bwd():
-                    gy = take(y, rows_out, Cout) if stream == S_MAIN else got(y)
-                    gx = self.T(rows_in, Cin, 'b')
-                    ag = (amax_of[gy] if gy in amax_of else self.amax_op(Bk, stream, gy, rows_out, Cout)) if AMAX else -1
-                    self.emit(Bk, OP_CONV, stream, x=gy, img=self.IMG(mod.kernel, True), map=m, dir=1, out=gx, n=-1, cin=Cout, cout=Cin, amax_x=ag)
-                    grad_src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
-                    emit_wgrad(stream, x=x, gout=gy, map=m, gw=self.G(mod.kernel), n=-1, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
-                    wrote(mod.kernel)
-                    accumulate(x, gx, rows_in, Cin, stream)
-                tape.append((stream, bwd))
-            return y
-
-        def gemm(x, w_tensor, rows, Cin, Cout, gw_dst, stream=S_MAIN):
-            """dense GEMM (n, Cin) x (Cin, Cout): the generative transposed convolution, the fused 1x1 heads; gw_dst: the address
-            index the (Cin, Cout) weight gradient goes to"""
-            y = self.T(rows, Cout)
-            ax = fwd_amax(x, rows, Cin, stream)
-            self.emit(F, OP_CONV, stream, x=x, img=self.IMG(w_tensor, False), map=-1, dir=0, out=y, n=self.D(rows), cin=Cin, cout=Cout, amax_x=ax)
-            producer[y] = (len(F) - 1, rows, Cout)
-            if tr:
-                def bwd():
-                    gy = take(y, rows, Cout) if stream == S_MAIN else got(y)
-                    gx = self.T(rows, Cin, 'b')
-                    ag = (amax_of[gy] if gy in amax_of else self.amax_op(Bk, stream, gy, rows, Cout)) if AMAX else -1
-                    self.emit(Bk, OP_CONV, stream, x=gy, img=self.IMG(w_tensor, True), map=-1, dir=1, out=gx, n=self.D(rows), cin=Cout, cout=Cin, amax_x=ag)
-                    grad_src[gx] = (len(Bk) - 1, rows, Cin, stream)
-                    emit_wgrad(stream, x=x, gout=gy, map=-1, gw=gw_dst, n=self.D(rows), cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
-                    if w_tensor is self.packed:
-                        head_wgrads[0] += 1
-                        if head_wgrads[0] == self.nl - (1 if self.tail0 else 0) and self.wgrad_async:
-                            # every level's partial of the packed head kernel is on its way, all on the weight-gradient stream:
-                            # sum them there right away (the head's parameters sit in the first gradient bucket to leave)
-                            head_wfin(S_WGRAD)
-                    accumulate(x, gx, rows, Cin, stream)
-                tape.append((stream, bwd))
-            return y
-
-        def bn(x, mod, act, rows, res=None, stream=S_MAIN, add=None):
-            """MinkowskiBatchNorm (+ residual) + activation (functional.bn_train / norm_act); add = (inverse row map, tensor): the
-            apply kernel also adds tensor[inverse[r]] to row r behind the activation (the neck's sparse sum) — y IS the sum then"""
-            # ... which is legal because the layer's backward never reads y: without a residual act' is recomputed from x (y = -1 below)
-            assert add is None or res is None
-            b = mod.bn
-            C = b.num_features
-            y = self.T(rows, C)
-            mean, var, cnt = (self.T('one', C), self.T('one', C), self.T('one', 1)) if tr else (-1, -1, -1)
-            if act == relu:
-                self.relu_outs.append((y, rows, C))
-            prod, groups = -1, 1
-            if tr and Fn.BN_FUSE and x in producer:
-                # the convolution that wrote x leaves the column sums of x and x^2 per row block in its epilogue (conv_x6.h /
-                # k_sum_*_stats) and this BatchNorm takes its batch statistics from them: no statistics pass over x
-                pi, prows, pcols = producer[x]
-                groups = pcols // C
-                assert pcols == groups * C and groups in (1, 8)
-                # table: [blocks][2][pcols] floats, blocks <= rows / 16 + 1 (conv.hip fc_stat_rb)
-                self.patch(F[pi], stats=self.T(prows, pcols // 8, extra=8 * pcols + 256))
-                prod = pi
-            ay = -1
-            if AMAX:                     # the apply kernel folds max |y| into this word: a convolution gathering y needs no amax pass
-                ay = amax_of[y] = self.amax_slot()
-            add_inv, add_src = add if add is not None else (-1, -1)
-            self.emit(F, OP_BN_FWD, stream, x=x, n=self.D(rows), c=C, eps=_f(b.eps), gamma=self.S(b.weight), beta=self.S(b.bias),
-                      res=-1 if res is None else res, act=act, momentum=_f(b.momentum), y=y, mean=mean, var=var, cnt=cnt,
-                      rmean=self.S(b.running_mean), rvar=self.S(b.running_var), nbt=self.S(b.num_batches_tracked), train=1 if tr else 0,
-                      producer=prod, groups=groups, amax_y=ay, add_inv=add_inv, add_src=add_src)
-            if tr:
-                sums = torch.zeros((2, C), dtype=torch.float32, device=self.dev)
-                si = self.S(sums)
-
-                def bwd():
-                    small_rows.append((sums.data_ptr(), None, C, b.weight, b.bias))
-                    gy, gy2 = take(y, rows, C, pair=True) if stream == S_MAIN else (got(y), None)
-                    gx = self.T(rows, C, 'b')
-                    gres = self.T(rows, C, 'b') if res is not None else -1
-                    prod = -1
-                    # the LAST contribution to gy is the result of a backward-data convolution (and at most one other contribution
-                    # arrived before it): that launch leaves this layer's two reductions (sum g', sum g' xhat) in its epilogue
-                    # (fc_conv_fwd_bn_bwd_stats; `add` = the earlier contribution, bn_y = this layer's output where act' needs it)
-                    # — no reduction pass over x, gy (, y)
-                    last, first = (gy, None) if gy2 is None else (gy2, gy)
-                    src = grad_src.get(last)
-                    if Fn.BN_FUSE and src is not None and src[3] == stream and src[1:3] == (rows, C):
-                        pi = src[0]
-                        self.patch(Bk[pi], stats=self.T(rows, C // 8, 'b', extra=8 * C + 256), bn_x=x, bn_mean=mean, bn_var=var,
-                                   bn_gamma=self.S(b.weight), bn_beta=self.S(b.bias), bn_eps=_f(b.eps), bn_act=act,
-                                   bn_add=-1 if first is None else first, bn_y=-1 if res is None else y)
-                        prod = pi
-                    agx = -1
-                    if AMAX:
-                        agx = amax_of[gx] = self.amax_slot()
-                    self.emit(Bk, OP_BN_BWD, stream, x=x, y=y if res is not None else -1, gy=gy, n=self.D(rows), c=C, mean=mean, var=var,
-                              cnt=cnt, eps=_f(b.eps), gamma=self.S(b.weight), beta=self.S(b.bias), act=act, gx=gx, gres=gres, sums=si,
-                              gy2=-1 if gy2 is None else gy2, producer=prod, amax_gx=agx)
-                    accumulate(x, gx, rows, C, stream)
-                    if res is not None:
-                        accumulate(res, gres, rows, C, stream)
-                tape.append((stream, bwd))
-            return y
-
-        # ---- backbone (me_resnet.py:14-50) ----
-        x0 = self.DY('x0')
-        seg1 = self.DY('seg1')
-        stem, inorm = bb.conv1[0], bb.conv1[1]
-        t_stem = self.T('n1', 64)
-        col = self.T('n1', 84) if tr else -1
-        self.emit(F, OP_STEM_FWD, S_MAIN, x=x0, w=self.S(stem.kernel), map=self.M('stem'), out=t_stem, col=col)
-        mean_in, var_in, cnt_in = self.T('B', 64), self.T('B', 64), self.T('B', 1)
-        self.emit(F, OP_COL_STATS, S_MAIN, x=t_stem, seg=seg1, n=self.D('n1'), c=64, nseg=self.D('B'), mean=mean_in, var=var_in, cnt=cnt_in)
-        # instance norm + ReLU + max pool in ONE pass (norm.hip k_norm_act_maxpool8_fwd, bit for bit the two operators): the
-        # normalised tensor's only consumer is the pool, and the backward pass recomputes act' from t_stem — it is stored only for
-        # `decisions` (keep_state)
-        t_in = self.T('n1', 64) if self.keep_state else -1
-        if self.keep_state:
-            self.relu_outs.append((t_in, 'n1', 64))
-        t_pool, arg = self.T('n2', 64), self.T('n2', 64)
-        self.pool_arg = (arg, 'n2', 64)
-        ap = -1
-        if AMAX:
-            ap = amax_of[t_pool] = self.amax_slot()
-        pool_parent = self.T('n1', 1) if tr else -1       # child row -> pooled row (4 bytes per row), for the backward pass
-        self.emit(F, OP_NORM_POOL_FWD, S_MAIN, x=t_stem, seg=seg1, c=64, mean=mean_in, var=var_in, eps=_f(inorm.eps), gamma=self.S(inorm.weight),
-                  beta=self.S(inorm.bias), act=relu, map=self.M('pool'), out=t_pool, arg=arg, y=t_in, amax_out=ap, parent=pool_parent)
-        if tr:
-            in_sums = self.T('B', 2 * 64, 'b')
-            self.in_sums = in_sums
-
-            def bwd_stem():
-                small_rows.append((None, 'B', 64, inorm.weight, inorm.bias))
-                g_pool = take(t_pool, 'n2', 64)
-                g_stem = self.T('n1', 64, 'b')
-                # pool backward + instance-norm backward without the scattered gradient in between: the normalisation backward's
-                # kernels read row r's gradient as g_pool[parent[r]] where arg[parent[r]] == r, else 0 (norm.hip pool_parent) — the sums
-                # in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
-                self.emit(Bk, OP_POOL_NORM_BWD, S_MAIN, x=t_stem, g_pool=g_pool, arg=arg, parent=pool_parent, seg=seg1, n=self.D('n1'), c=64,
-                          nseg=self.D('B'), mean=mean_in, var=var_in, cnt=cnt_in, eps=_f(inorm.eps), gamma=self.S(inorm.weight),
-                          beta=self.S(inorm.bias), act=relu, gx=g_stem, sums=in_sums)
-                if self.wgrad_async:
-                    self.emit(Bk, OP_RECORD, S_MAIN, event=EV_W0)
-                    self.emit(Bk, OP_WAIT, S_WGRAD, event=EV_W0)
-                self.emit(Bk, OP_STEM_WGRAD, wstream(S_MAIN), col=col, gout=g_stem, map=self.M('stem'), gw=self.G(stem.kernel))
-                wrote(stem.kernel)
-            tape.append((S_MAIN, bwd_stem))
-        cur, cur_rows, cur_C = t_pool, 'n2', 64
+    def _build(self, em):
+        """the network as `extract_feat` runs it (me_resnet.py:14-50; fcaf3d_neck_with_head.py:94-108, :256-279): stem, backbone
+        levels, then neck level i and the head of level i from the coarsest down; last the backward schedule"""
+        bb, nh = self.det.backbone, self.det.neck_with_head
+        x = em.stem(bb.conv1[0], bb.conv1[1])
         levels = []
         for li in range(1, self.nl + 1):
-            rows = f'L{li}'
-            if tr:
-                tape.append((S_MAIN, lambda: flush_small(S_MAIN)))       # reversed walk: reached after this layer's backward
-            for j, blk in enumerate(getattr(bb, f'layer{li}')):
-                planes = blk.conv1.out_channels
-                if j == 0:
-                    assert blk.downsample is not None and blk.conv1.stride == 2
-                    t_ds = conv(cur, blk.downsample[0], f'ds{li}', cur_rows, rows)
-                    res = bn(t_ds, blk.downsample[1], none, rows)
-                    t1 = conv(cur, blk.conv1, f'down{li}', cur_rows, rows)
-                else:
-                    assert blk.downsample is None
-                    res = cur
-                    t1 = conv(cur, blk.conv1, f'same{li}', rows, rows)
-                t1 = bn(t1, blk.norm1, relu, rows)
-                t2 = conv(t1, blk.conv2, f'same{li}', rows, rows)
-                cur = bn(t2, blk.norm2, relu, rows, res=res)
-                cur_rows, cur_C = rows, planes
-            levels.append((cur, rows, cur_C))
-        # ---- neck + head (fcaf3d_neck_with_head.py:94-108, :256-279) ----
-        n_reg, n_cls = nh.n_reg_outs, nh.n_classes
-        Cn = nh.centerness_conv.in_channels
-        cent_all, bbox_all = self.T('Nall', 1), self.T('Nall', n_reg)
-        cls_all, cmax_all = self.T('Nall', n_cls), self.T('Nall', 1)
-        self.out_idx = (cent_all, bbox_all, cls_all, cmax_all)
-        head_part = None
-        if tr:
-            tape.append((S_MAIN, lambda: flush_small(S_MAIN)))           # ... after the whole neck's backward
+            x = em.level(li, getattr(bb, f'layer{li}'), x)
+            levels.append(x)
+        self.out_idx = (self.T('Nall', 1), self.T('Nall', nh.n_reg_outs), self.T('Nall', nh.n_classes), self.T('Nall', 1))
+        if self.training:
+            em.tape.append(lambda: em.flush_small(S_MAIN))               # reversed walk: reached after the whole neck's backward
             self.gout_idx = (self.DY('g_cent'), self.DY('g_bbox'), self.DY('g_cls'))
-            head_part = torch.zeros((self.nl, Cn, 64), dtype=torch.float32, device=self.dev)
-            # per level: the column sums of d loss / d cls_score (the class-bias gradient's share), left by OP_HEAD_BWD
-            bias_part = torch.zeros((self.nl, n_cls), dtype=torch.float32, device=self.dev)
-            self.keep += [head_part, bias_part]
-        x, x_rows, x_C = levels[-1]
         for i in range(self.nl - 1, -1, -1):
             if i < self.nl - 1:
-                up = getattr(nh, f'up_block_{i + 1}')
-                gi = self.gents.index(up[0])
-                g_rows = f'g{i}'
-                Ci = up[0].out_channels
-                # generative transposed convolution: one dense GEMM (n, Cin) x (Cin, 8 Cout) whose (n, 8 Cout) output IS the
-                # (8 n, Cout) children matrix (row 8 i + k); its weight gradient comes out in the GEMM's layout and is permuted
-                # into the layer's (8, Cin, Cout) kernel gradient afterwards
-                gw_tmp = torch.zeros((x_C, 8 * Ci), dtype=torch.float32, device=self.dev)
-                self.keep.append(gw_tmp)
-                gw_i = self.S(gw_tmp)
-                if tr:
-                    def bwd_perm(gw_i=gw_i, mod=up[0], Cin=x_C, Ci=Ci):
-                        self.emit(Bk, OP_PERMUTE_GENT, wstream(S_MAIN), src=gw_i, dst=self.G(mod.kernel), cin=Cin, cout=Ci)
-                        wrote(mod.kernel)
-                        flush_small(S_MAIN)                     # ... and after every neck level's up-block
-                    tape.append((S_MAIN, bwd_perm))          # forward order: BEFORE the GEMM, so the reversed walk reaches it after
-                t = gemm(x, self.gent_w[gi], x_rows, x_C, 8 * Ci, gw_i)
-                t = bn(t, up[1], elu, g_rows)
-                t = conv(t, up[3], f'gsame{i}', g_rows, g_rows)
-                # x = inputs[i] + t: every backbone voxel lies in the generated set -> the union IS the generated set (sparse.CoordMap.union)
-                # and the up block's last normalisation writes it (r7): its apply kernel adds the backbone row behind the activation
-                # through the inverse of rows{i} and folds the amax word of the SUM, complete when that kernel ends — before the head
-                # branch forks.  (The map is made here, two small launches, not by fc_plan_maps: the plan's outputs and interface stay.)
-                fb, fb_rows, fb_C = levels[i]
-                rows_i = self.DY(f'rows{i}')
-                inv_i = self.T(g_rows, 1)
-                self.emit(F, OP_INV_ROWS, S_MAIN, rows=rows_i, n=self.D(fb_rows), n_inv=self.D(g_rows), inv=inv_i)
-                u = bn(t, up[4], elu, g_rows, add=(inv_i, fb))
-                if tr:
-                    def bwd_union(u=u, fb=fb, fb_rows=fb_rows, rows_i=rows_i, g_rows=g_rows, Ci=Ci):
-                        # d u / d (normalisation output) = identity on all rows (n_a == n_union): the layer's backward, next in the
-                        # reversed walk, takes the gradient of u as its own
-                        gu = take(u, g_rows, Ci)
-                        gfb = self.T(fb_rows, Ci, 'b')
-                        self.emit(Bk, OP_GATHER, S_MAIN, src=gu, idx=rows_i, n=self.D(fb_rows), c=Ci, dst=gfb)
-                        accumulate(fb, gfb, fb_rows, Ci, S_MAIN)
-                    tape.append((S_MAIN, bwd_union))
-                x, x_rows, x_C = u, g_rows, Ci
-                kname = f'gsame{i}'
-            else:
-                kname = f'same{self.nl}'
+                x = em.up(i, getattr(nh, f'up_block_{i + 1}'), x, levels[i])
             if i == 0 and self.tail0:
-                self.x0_idx = (x, x_rows, x_C)              # the pruned level's tail runs outside the program
-                if tr:
-                    grad[x] = self.DY('g_x0')               # ... and hands back d loss / d x0
-                continue
-            # out_block_i + forward_single: on the head stream for i > 0
-            hs = S_HEAD if (self.head_overlap and i > 0) else S_MAIN
-            if hs == S_HEAD:
-                self.emit(F, OP_RECORD, S_MAIN, event=EV_FORK + i)
-                self.emit(F, OP_WAIT, S_HEAD, event=EV_FORK + i)
-            ob = getattr(nh, f'out_block_{i}')
-            o = conv(x, ob[0], kname, x_rows, x_rows, stream=hs)
-            o = bn(o, ob[1], elu, x_rows, stream=hs)
-            gw_head = self.SA(head_part[i].data_ptr()) if tr else -1
-            y = gemm(o, self.packed, x_rows, Cn, 64, gw_head, stream=hs)
-            off = f'off{i}'
-            outs = [self.AL(cent_all, off, 1), self.AL(bbox_all, off, n_reg), self.AL(cls_all, off, n_cls), self.AL(cmax_all, off, 1)]
-            self.emit(F, OP_HEAD_FWD, hs, y=y, ld=64, bias=self.S(nh.cls_conv.bias), scale=self.S(nh.scales[i].scale), n=self.D(x_rows), n_reg=n_reg,
-                      n_cls=n_cls, cent=outs[0], bbox=outs[1], cls=outs[2], cmax=outs[3])
-            if tr:
-                def bwd_head(y=y, outs=outs, off=off, hs=hs, rows=x_rows, lvl=i):
-                    gy = self.T(rows, 64, 'b')
-                    gin = [self.AL(g, off, c) for g, c in zip(self.gout_idx, (1, n_reg, n_cls))]
-                    # ... with d loss / d scale of this level and this level's share of the class-bias gradient (column sums of
-                    # d loss / d cls_score; summed over the levels by OP_HEAD_WFIN) out of the same pass (r5: they were single-block
-                    # reductions over every location, k_col_sum: 0.35 ms per step on the dependent chain)
-                    agy = -1
-                    if AMAX:                 # the kernel folds max |gy| for the backward-data GEMM behind it
-                        agy = amax_of[gy] = self.amax_slot()
-                    self.emit(Bk, OP_HEAD_BWD, hs, y=y, ld=64, scale=self.S(nh.scales[lvl].scale), bbox=outs[1], g_cent=gin[0], g_bbox=gin[1],
-                              g_cls=gin[2], n=self.D(rows), n_reg=n_reg, n_cls=n_cls, gy=gy, gs_row=-1, g_scale=self.G(nh.scales[lvl].scale),
-                              bias_part=self.SA(bias_part[lvl].data_ptr()), amax_gy=agy)
-                    wrote(nh.scales[lvl].scale)
-                    grad[y] = gy
-                tape.append((hs, bwd_head))
-                if hs == S_HEAD:
-                    tape.append((S_HEAD, ('join', x, x_rows, x_C, i)))      # marker: where this level's head branch begins in reverse
+                self.x0_idx = x                             # the pruned level's tail runs outside the program
+                if self.training:
+                    em.grads.arrive(x[0], self.DY('g_x0'), *x[1:], S_MAIN)       # ... and hands back d loss / d x0
+            else:
+                em.head(i, getattr(nh, f'out_block_{i}'), x)
         if self.head_overlap:
-            self.emit(F, OP_RECORD, S_HEAD, event=EV_HEAD_DONE)
-            self.emit(F, OP_WAIT, S_MAIN, event=EV_HEAD_DONE)
-        # ---- backward program -------------------------------------------------------------------------------------------
-        if AMAX:
-            n_fwd_slots = self._amax_used
-            self.patch(F[0], bytes=self.AMAX_SLOT_BYTES * n_fwd_slots)       # the forward pass clears its own words; they stay valid through the backward pass
-            if tr:
-                self.emit(Bk, OP_CLEAR, S_MAIN, dst=self.SA(self._amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * n_fwd_slots), bytes=0)
-                clear_b = len(Bk) - 1
-        if tr:
-            if self.head_overlap:
-                # the head branches depend on the loss gradients only: their backward is enqueued first, on the head stream, finest
-                # forked level first (the main chain needs that one first); each leaves the gradient of its neck tensor behind an event
-                self.emit(Bk, OP_RECORD, S_MAIN, event=EV_BWD0)          # the loss gradients are ready on the caller's stream
-                self.emit(Bk, OP_WAIT, S_HEAD, event=EV_BWD0)
-                branches, cur_b = [], None
-                for s, e in reversed(tape):
-                    if s != S_HEAD:
-                        continue
-                    if isinstance(e, tuple):
-                        cur_b = [e, []]
-                        branches.append(cur_b)
-                    else:
-                        cur_b[1].append(e)
-                for (_, xt, rows, C, lvl), ems in sorted(branches, key=lambda b: b[0][4]):
-                    saved = grad.pop(xt, None)
-                    assert saved is None
-                    head_lvl[0] = lvl
-                    for e in ems:
-                        e()
-                    flush_small(S_HEAD)                    # this branch's normalisation layer
-                    head_lvl[0] = None
-                    self.emit(Bk, OP_RECORD, S_HEAD, event=EV_HB + lvl)
-                    head_grads[xt] = (got(xt), lvl)
-                    grad.pop(xt)
-            for s, e in reversed(tape):
-                if s == S_MAIN:
-                    e()
-            assert not head_grads and not head_written, 'a head branch was never joined'
-            if not self.wgrad_async:
-                # without the weight-gradient stream the partials were written on the streams of their levels (main, head): the
-                # main stream has joined every head branch by now
-                head_wfin(S_MAIN)
-            flush_small(S_MAIN)                            # what is left: the stem's instance norm
-            assert head_wgrads[0] == self.nl - (1 if self.tail0 else 0)
-            self.small = small_rows
-            missing = [n for n, prm in det.named_parameters() if prm.requires_grad and id(prm) not in self._pready]
-            if self.tail0:                                 # out_block_0 and scales.0 get their gradients on the per-operator path
-                missing = [n for n in missing if not (n.startswith('neck_with_head.out_block_0.') or n == 'neck_with_head.scales.0.scale')]
-            assert not missing, missing
-            if self.wgrad_async:
-                self.emit(Bk, OP_RECORD, S_WGRAD, event=EV_WEND)
-                self.emit(Bk, OP_WAIT, S_MAIN, event=EV_WEND)
-            if AMAX:
-                self.patch(Bk[clear_b], bytes=self.AMAX_SLOT_BYTES * (self._amax_used - n_fwd_slots))
+            em.sync(self.ops_f, S_HEAD, S_MAIN, EV_HEAD_DONE)
+        em.backward()
 
     # ---- per-step tables ---------------------------------------------------------------------------------------------------
     def _finalise(self):
@@ -707,14 +273,12 @@ class NetProgram:
         self.addr0 = np.zeros(self.n_addr, dtype=np.int64)
         for i, a in self.static:
             self.addr0[i] = a
-        self._ar = {}
-        for k in ('f', 'b'):
-            a = self.arena[k]
-            self._ar[k] = (np.array([t[0] for t in a], dtype=np.int64), np.array([t[1] for t in a], dtype=np.int64),
-                           np.array([t[2] for t in a], dtype=np.int64), np.array([t[3] for t in a], dtype=np.int64))
-        self._al = (np.array([t[0] for t in self.alias], dtype=np.int64), np.array([t[1] for t in self.alias], dtype=np.int64),
-                    np.array([t[2] for t in self.alias], dtype=np.int64), np.array([t[3] for t in self.alias], dtype=np.int64))
-        self._gr = (np.array([t[0] for t in self.grad_refs], dtype=np.int64), np.array([t[1] for t in self.grad_refs], dtype=np.int64) * 4)
+
+        def columns(table, width):
+            return tuple(np.ascontiguousarray(np.array(table, dtype=np.int64).reshape(-1, width).T))
+        self._ar = {k: columns(a, 4) for k, a in self.arena.items()}
+        self._al = columns(self.alias, 4)
+        self._gr = columns([(i, 4 * off) for i, off in self.grad_refs], 2)
         self.n_dims, self.n_maps = len(self.dim_names), len(self.map_names)
         self._ws = [None, None, None]
         self._need = np.zeros(3, dtype=np.int64)
@@ -758,7 +322,7 @@ class NetProgram:
         cm0 = x.cmap
         dims = np.zeros(self.n_dims, dtype=np.int64)
         maps = np.zeros((self.n_maps, MAPW), dtype=np.int64)
-        dn, mn = self.dim_names, self.map_names
+        dn, mn, N = self.dim_names, self.map_names, _Names
 
         def setd(k, v):
             if k in dn:
@@ -772,10 +336,10 @@ class NetProgram:
         prev, lv = m2, []
         for li in range(1, nl + 1):
             mi = prev.strided(2)
-            kms[f'down{li}'], kms[f'ds{li}'], kms[f'same{li}'] = prev.kernel_map(mi, 3), prev.kernel_map(mi, 1), mi.kernel_map(mi, 3)
-            for k in (f'down{li}', f'ds{li}', f'same{li}'):
+            kms[N.down(li)], kms[N.ds(li)], kms[N.same(li)] = prev.kernel_map(mi, 3), prev.kernel_map(mi, 1), mi.kernel_map(mi, 3)
+            for k in (N.down(li), N.ds(li), N.same(li)):
                 maps[mn[k]] = kms[k].desc(True, backward)
-            setd(f'L{li}', mi.n)
+            setd(N.rows(li), mi.n)
             lv.append(mi)
             prev = mi
         xm = lv[-1]
@@ -786,10 +350,10 @@ class NetProgram:
             u, rows, swapped = lv[i].union(g)
             if not swapped or u is not g:
                 return None
-            kms[f'gsame{i}'] = g.kernel_map(g, 3)
-            maps[mn[f'gsame{i}']] = kms[f'gsame{i}'].desc(True, backward)
-            setd(f'g{i}', g.n)
-            dyn[f'rows{i}'] = rows
+            kms[N.gsame(i)] = g.kernel_map(g, 3)
+            maps[mn[N.gsame(i)]] = kms[N.gsame(i)].desc(True, backward)
+            setd(N.gen(i), g.n)
+            dyn[N.union(i)] = rows
             xm = g
             head_maps.append(g)
         head_maps = head_maps[::-1]                       # finest first
@@ -797,7 +361,7 @@ class NetProgram:
         for i, cm in enumerate(head_maps):
             if i == 0 and self.tail0:
                 continue                                  # (its head outputs come from the per-operator tail)
-            setd(f'off{i}', off)
+            setd(N.off(i), off)
             off += cm.n
         setd('Nall', off)
         st = dict(dims=dims, maps=maps, dyn=dyn, head_maps=head_maps, x=x, seg1=m1.coords, n_all=off)
@@ -842,14 +406,14 @@ class NetProgram:
         """(ReLU sign patterns in forward order, max-pool arg-max rows) of the forward pass bound in `st` — what
         oracle.DecisionTape replays (test infrastructure reads it; needs KEEP_STATE)"""
         assert self.keep_state, 'this program does not store the stem\'s normalised output: build it under executor.KEEP_STATE'
-        fa, addr, dims = st['fa'], st['addr'], st['dims']
+        relu = [(self._view(st, *t) > 0).cpu() for t in self.relu_outs]
+        return relu, self._view(st, *self.pool_arg, torch.int32).cpu()
 
-        def view(idx, rows, C, dtype):
-            n = int(dims[self.dim_names[rows]])
-            o = int(addr[idx] - fa.data_ptr())
-            return fa[o:o + n * C * 4].view(dtype).view(n, C)
-        relu = [(view(t, r, C, torch.float32) > 0).cpu() for t, r, C in self.relu_outs]
-        return relu, view(*self.pool_arg, torch.int32).cpu()
+    def _view(self, st, idx, rows, C, dtype=torch.float32):
+        """the (rows, C) view of forward-arena tensor `idx` in this step's state"""
+        fa, n = st['fa'], int(st['dims'][self.dim_names[rows]])
+        o = int(st['addr'][idx] - fa.data_ptr())
+        return fa[o:o + n * C * 4].view(dtype).view(n, C)
 
     def forward(self, st):
         """-> (cent_all, bbox_all, cls_all, cmax_all) for all head locations (levels finest first), autograd-connected in training"""
@@ -878,17 +442,10 @@ class NetProgram:
         addr[ai[fwd_alias]] = addr[ap[fwd_alias]] + dims[ad[fwd_alias]] * ab[fwd_alias]
         st['fa'], st['addr'] = fa, addr
         self._run(self.ops_f, addr, st)
-        n = st['n_all']
         nh = self.det.neck_with_head
-        outs = []
-        for idx, c in zip(self.out_idx, (1, nh.n_reg_outs, nh.n_classes, 1)):
-            o = int(addr[idx] - fa.data_ptr())
-            outs.append(fa[o:o + n * c * 4].view(torch.float32).view(n, c))
+        outs = [self._view(st, idx, 'Nall', c) for idx, c in zip(self.out_idx, (1, nh.n_reg_outs, nh.n_classes, 1))]
         if self.tail0:
-            t, rows, C = self.x0_idx
-            n0 = int(dims[self.dim_names[rows]])
-            o = int(addr[t] - fa.data_ptr())
-            outs.append(fa[o:o + n0 * C * 4].view(torch.float32).view(n0, C))
+            outs.append(self._view(st, *self.x0_idx))
         return tuple(outs)
 
     def _backward(self, st, g_cent, g_bbox, g_cls, g_x0=None):
@@ -910,8 +467,6 @@ class NetProgram:
             addr[self.dyn[k]] = g.data_ptr()
         ai, ap, ad, ab = self._al
         addr[ai] = addr[ap] + dims[ad] * ab
-        # gradients that are already there (a second backward pass without zero_grad: accumulation) are added to afterwards;
-        # then, and without flat storage, this pass writes into a buffer of its own (same layout)
         own = self._own_params()
         # Parameters that already hold a gradient when this pass starts: (a) a few, in tensors of their own — the pruned level's
         # per-operator tail has delivered the head kernels' share before this node ran: the program writes its share into the
@@ -994,6 +549,451 @@ class NetProgram:
             views = {id(p): gbuf[self._goff[id(p)]:self._goff[id(p)] + p.numel()].view(p.shape) for p in self._params}
             cache = self._gv = (key, views, gbuf)
         return cache[1]
+
+
+class _Names:
+    """the names under which the walk registers the per-level row counts (`dim_names`), kernel maps (`map_names`) and bound
+    tensors (`dyn`), and under which `bind` fills them in.  li = 1 ..: backbone level, i = 0 ..: neck level (finest first)"""
+    rows, down, ds, same = 'L{}'.format, 'down{}'.format, 'ds{}'.format, 'same{}'.format
+    gen, gsame, off, union = 'g{}'.format, 'gsame{}'.format, 'off{}'.format, 'rows{}'.format
+
+
+class _Grads:
+    """the gradient ledger of the backward walk: forward tensor -> its gradient (a tensor of the backward arena), from the first
+    contribution that arrives to the consumer that takes the sum"""
+
+    def __init__(self, em):
+        self.em = em
+        self.full = {}                   # forward tensor -> gradient tensor
+        self.second = {}                 # forward tensor -> (second contribution, rows, cols, stream), not yet added
+        self.behind = {}                 # forward tensor -> (gradient from its head branch on the head stream, level)
+        self.src = {}                    # gradient tensor -> (index in ops_b of the backward-data OP_CONV that wrote it, rows, cols, stream)
+
+    def _add(self, t, g, rows, cols, stream):
+        em, dst = self.em, self.full[t]
+        em.p.emit(em.Bk, OP_ADD, stream, dst=dst, src=g, n=em.p.D(rows), c=cols)
+        self.src.pop(dst, None)          # added to in place: no longer the plain result of the convolution that wrote it
+        em.amax_of.pop(dst, None)        # ... nor bounded by its producer's amax word
+
+    def arrive(self, t, g, rows, cols, stream):
+        """gradient `g` (a backward tensor) arrives for forward tensor t.  The SECOND contribution is kept aside: if the
+        consumer of the sum is a BatchNorm backward it adds the two on the fly (norm.hip gy2) and no add pass runs; a third
+        arrival, or any other consumer, adds the first two as before (same operands, same order: same bits)"""
+        if t not in self.full:
+            self.full[t] = g
+        elif Fn.BN_FUSE and t not in self.second:
+            self.second[t] = (g, rows, cols, stream)
+        else:
+            self.own(t)                  # (a contribution kept aside goes in first)
+            self._add(t, g, rows, cols, stream)
+
+    def take(self, t, rows, cols, pair=False):
+        """the complete gradient of forward tensor t, for the emitter of the operator that produced t (main stream); pair:
+        the caller adds a second contribution itself -> (gradient, second contribution | None)"""
+        if t in self.behind:
+            g, lvl = self.behind.pop(t)
+            self.em.join(lvl)
+            self.arrive(t, g, rows, cols, S_MAIN)
+        if pair:
+            return self.full[t], (self.second.pop(t)[0] if t in self.second else None)
+        return self.own(t)
+
+    def own(self, t):
+        """the gradient of t for a consumer on the tensor's own (head) stream"""
+        if t in self.second:
+            self._add(t, *self.second.pop(t))
+        return self.full[t]
+
+    def deliver(self, t, lvl):
+        """the head branch of level `lvl` has left its gradient of neck tensor t behind event EV_HB + lvl: `take` joins it"""
+        self.behind[t] = (self.own(t), lvl)
+        del self.full[t]
+
+
+class _Emitter:
+    """The walk over the module graph that fills a NetProgram's operator lists and tables; it lives for the program build only.
+    Every layer emits its forward operators as the walk passes and leaves an emitter of its backward operators on the current
+    tape; `backward` replays the tapes in reverse."""
+
+    # ---- r6: amax words of the convolutions' operands (csrc/conv_x6.h "h3": the scale of the two-piece fp16 split) ------------
+    # One fc_amax pass per operand TENSOR and stream instead of one per consuming launch: a forward activation's word serves its
+    # forward convolution(s) and, a pass later, their weight gradients; a gradient's word serves the backward-data convolution and the
+    # weight gradient of its layer.  Slots are 2 KB of one persistent buffer (32 sub-words, fc_common.h; fc_amax returns its scratch words to zero).
+    AMAX_SLOTS = 1024
+    AMAX_SLOT_BYTES = 2048           # include/fcaf3d_hip.h FC_AMAX_SLOT_BYTES: 32 sub-words at a 64-byte stride
+
+    def __init__(self, p):
+        self.p, self.F, self.Bk, self.tr = p, p.ops_f, p.ops_b, p.training
+        nh = p.det.neck_with_head
+        self.grads = _Grads(self)
+        self.main = []                   # backward emitters of the main chain, in forward order
+        self.branches = {}               # forked neck level -> (its neck tensor, backward emitters of its head branch (S_HEAD), in forward order)
+        self.tape = self.main            # where the layer being walked leaves its backward emitter
+        self.branch = None               # the neck level whose head branch's backward is being emitted, None: main chain
+        self.branch_params = {}          # level -> parameters whose gradient is written on S_HEAD by that branch
+        self.flushed = 0                 # rows of p.small that an OP_SMALL_GRADS covers already
+        self.producer = {}               # forward tensor -> (index of the OP_CONV that wrote it, rows, columns)
+        self.n_reg, self.n_cls, self.Cn = nh.n_reg_outs, nh.n_classes, nh.centerness_conv.in_channels
+        self.n_heads = p.nl - (1 if p.tail0 else 0)
+        self.head_partials = 0           # levels whose partial of the packed head kernel's gradient has been emitted
+        if self.tr:
+            self.head_part = torch.zeros((p.nl, self.Cn, 64), dtype=torch.float32, device=p.dev)
+            # per level: the column sums of d loss / d cls_score (the class-bias gradient's share), left by OP_HEAD_BWD
+            self.bias_part = torch.zeros((p.nl, self.n_cls), dtype=torch.float32, device=p.dev)
+            p.keep += [self.head_part, self.bias_part]
+        self.amax = Fn.X6 and Fn.split_mode() == 2       # the convolutions scale their operands by their amax words (csrc/conv_x6.h h3)
+        self.amax_f = {}                 # (forward tensor, stream) -> address index of its amax word
+        self.amax_of = {}                # tensor -> address index of the amax word its PRODUCER folds into (fc_amax_out_hint)
+        self.amax_used = 0
+        if self.amax:
+            self.amax_buf = torch.zeros(self.AMAX_SLOTS * self.AMAX_SLOT_BYTES // 4, dtype=torch.int32, device=p.dev)
+            p.keep.append(self.amax_buf)
+            # the words the producers fold into start every pass at zero: one fill per direction, its size patched in by `backward`
+            self.amax_slot()             # (slot 0 doubles as the buffer's base address)
+            p.emit(self.F, OP_CLEAR, S_MAIN, dst=p.SA(self.amax_buf.data_ptr()), bytes=0)
+
+    def amax_slot(self):
+        assert self.amax_used < self.AMAX_SLOTS
+        self.amax_used += 1
+        return self.p.SA(self.amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * (self.amax_used - 1))
+
+    def amax_op(self, lst, stream, x, rows, cols):
+        """emit the amax pass of tensor x ((rows, cols) floats) on `stream` -> address index of its word"""
+        slot = self.amax_slot()
+        self.p.emit(lst, OP_AMAX, stream, x=x, n=self.p.D(rows), c=cols, slot=slot)
+        return slot
+
+    def amax_fwd(self, x, rows, cols, stream):
+        if not self.amax:
+            return -1
+        if x in self.amax_of:
+            return self.amax_of[x]
+        if (x, stream) not in self.amax_f:
+            self.amax_f[(x, stream)] = self.amax_op(self.F, stream, x, rows, cols)
+        return self.amax_f[(x, stream)]
+
+    def folded(self, t):
+        """-> the amax word that the producer of tensor t folds max |t| into (-1: the convolutions take no amax words)"""
+        if self.amax:
+            self.amax_of[t] = self.amax_slot()
+        return self.amax_of.get(t, -1)
+
+    # ---- streams and gradient readiness ----------------------------------------------------------------------------------------
+    def sync(self, lst, src, dst, event):
+        """stream `dst` goes on behind what stream `src` holds now"""
+        self.p.emit(lst, OP_RECORD, src, event=event)
+        self.p.emit(lst, OP_WAIT, dst, event=event)
+
+    def wgrad(self, cur, op, **fields):
+        """a weight-gradient operator of a layer on stream `cur`: on the weight-gradient stream, behind `cur`, where there is one"""
+        if self.p.wgrad_async:
+            self.sync(self.Bk, cur, S_WGRAD, EV_W0 if cur == S_MAIN else EV_W1)
+        self.p.emit(self.Bk, op, S_WGRAD if self.p.wgrad_async else cur, **fields)
+
+    def wrote(self, *params):
+        for prm in params:
+            self.p._pready[id(prm)] = len(self.Bk)
+        if self.branch is not None:
+            # written on the head stream (or behind it): final for a data-parallel bucket only once the MAIN stream has
+            # joined this branch (join: OP_WAIT EV_HB + level) — GradientAverager.launch_next orders the collective behind
+            # the main and the weight-gradient stream, not behind S_HEAD (ADVICE r4)
+            self.branch_params.setdefault(self.branch, []).extend(params)
+
+    def join(self, lvl):
+        self.p.emit(self.Bk, OP_WAIT, S_MAIN, event=EV_HB + lvl)           # the head branch of this level has delivered
+        for prm in self.branch_params.pop(lvl, ()):
+            self.p._pready[id(prm)] = max(self.p._pready[id(prm)], len(self.Bk))
+
+    def flush_small(self, stream):
+        """the d gamma / d beta sums of the normalisation layers whose backward has been emitted since the last flush -> their
+        gradient slices (one launch); called where a group of layers ends, so that a data-parallel bucket is complete early"""
+        p, n = self.p, len(self.p.small) - self.flushed
+        if n:
+            p.emit(self.Bk, OP_SMALL_GRADS, stream, desc=p.DY('small_desc'), first=2 * self.flushed, count=2 * n)
+            for _, _, _, w_, b_ in p.small[self.flushed:]:
+                self.wrote(w_, b_)
+            self.flushed = len(p.small)
+
+    def head_wfin(self, stream):
+        p, nh, lo = self.p, self.p.det.neck_with_head, self.p.nl - self.n_heads
+        p.emit(self.Bk, OP_HEAD_WFIN, stream, part=p.SA(self.head_part[lo].data_ptr()), nl=self.n_heads, r=self.Cn, ld=64, n_reg=self.n_reg,
+               n_cls=self.n_cls, g_cent=p.G(nh.centerness_conv.kernel), g_reg=p.G(nh.reg_conv.kernel), g_cls=p.G(nh.cls_conv.kernel),
+               bias_part=p.SA(self.bias_part[lo].data_ptr()), g_bias=p.G(nh.cls_conv.bias))
+        self.wrote(nh.centerness_conv.kernel, nh.reg_conv.kernel, nh.cls_conv.kernel, nh.cls_conv.bias)
+
+    # ---- layers ------------------------------------------------------------------------------------------------------------
+    def conv(self, x, rows_in, rows_out, mod=None, mname=None, dense=None, stream=S_MAIN):
+        """one convolution launch and its backward.  Either MinkowskiConvolution `mod` on kernel map `mname`
+        (functional._SparseConv), or dense = (weights, address index their gradient goes to): the GEMM (n, Cin) x (Cin, Cout) of
+        the generative transposed convolution and of the fused 1x1 heads"""
+        p, F, Bk, G = self.p, self.F, self.Bk, self.grads
+        if dense is None:
+            w, gw, Cin, Cout, m, n = mod.kernel, None, mod.in_channels, mod.out_channels, p.M(mname), -1
+        else:
+            (w, gw), m, n = dense, -1, p.D(rows_in)
+            Cin, Cout = w.shape[-2:]
+        y = p.T(rows_out, Cout)
+        ax = self.amax_fwd(x, rows_in, Cin, stream)
+        p.emit(F, OP_CONV, stream, x=x, img=p.IMG(w, False), map=m, dir=0, out=y, n=n, cin=Cin, cout=Cout, amax_x=ax)
+        self.producer[y] = (len(F) - 1, rows_out, Cout)
+
+        def bwd():
+            gy = G.take(y, rows_out, Cout) if stream == S_MAIN else G.own(y)
+            gx = p.T(rows_in, Cin, 'b')
+            ag = (self.amax_of[gy] if gy in self.amax_of else self.amax_op(Bk, stream, gy, rows_out, Cout)) if self.amax else -1
+            p.emit(Bk, OP_CONV, stream, x=gy, img=p.IMG(w, True), map=m, dir=1, out=gx, n=n, cin=Cout, cout=Cin, amax_x=ag)
+            G.src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
+            self.wgrad(stream, OP_WGRAD, x=x, gout=gy, map=m, gw=p.G(w) if gw is None else gw, n=n, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
+            if gw is None:
+                self.wrote(w)
+            G.arrive(x, gx, rows_in, Cin, stream)
+        if self.tr:
+            self.tape.append(bwd)
+        return y
+
+    def bn(self, x, mod, act, rows, res=None, stream=S_MAIN, add=None):
+        """MinkowskiBatchNorm (+ residual) + activation (functional.bn_train / norm_act); add = (inverse row map, tensor): the
+        apply kernel also adds tensor[inverse[r]] to row r behind the activation (the neck's sparse sum) — y IS the sum then"""
+        # ... which is legal because the layer's backward never reads y: without a residual act' is recomputed from x (y = -1 below)
+        assert add is None or res is None
+        p, F, Bk, G, tr = self.p, self.F, self.Bk, self.grads, self.tr
+        b, C = mod.bn, mod.bn.num_features
+        y = p.T(rows, C)
+        mean, var, cnt = (p.T('one', C), p.T('one', C), p.T('one', 1)) if tr else (-1, -1, -1)
+        if act == Fn.ACT['relu']:
+            p.relu_outs.append((y, rows, C))
+        prod, groups = -1, 1
+        if tr and Fn.BN_FUSE and x in self.producer:
+            # the convolution that wrote x leaves the column sums of x and x^2 per row block in its epilogue (conv_x6.h /
+            # k_sum_*_stats) and this BatchNorm takes its batch statistics from them: no statistics pass over x
+            prod, prows, pcols = self.producer[x]
+            groups = pcols // C
+            assert pcols == groups * C and groups in (1, 8)
+            # table: [blocks][2][pcols] floats, blocks <= rows / 16 + 1 (conv.hip fc_stat_rb)
+            p.patch(F[prod], stats=p.T(prows, pcols // 8, extra=8 * pcols + 256))
+        ay = self.folded(y)              # the apply kernel folds max |y| into this word: a convolution gathering y needs no amax pass
+        add_inv, add_src = add if add is not None else (-1, -1)
+        p.emit(F, OP_BN_FWD, stream, x=x, n=p.D(rows), c=C, eps=_f(b.eps), gamma=p.S(b.weight), beta=p.S(b.bias),
+               res=-1 if res is None else res, act=act, momentum=_f(b.momentum), y=y, mean=mean, var=var, cnt=cnt,
+               rmean=p.S(b.running_mean), rvar=p.S(b.running_var), nbt=p.S(b.num_batches_tracked), train=1 if tr else 0,
+               producer=prod, groups=groups, amax_y=ay, add_inv=add_inv, add_src=add_src)
+        if not tr:
+            return y
+        sums = torch.zeros((2, C), dtype=torch.float32, device=p.dev)
+        si = p.S(sums)
+
+        def bwd():
+            p.small.append((sums.data_ptr(), None, C, b.weight, b.bias))
+            gy, gy2 = G.take(y, rows, C, pair=True) if stream == S_MAIN else (G.own(y), None)
+            gx = p.T(rows, C, 'b')
+            gres = p.T(rows, C, 'b') if res is not None else -1
+            prod = -1
+            # the LAST contribution to gy is the result of a backward-data convolution (and at most one other contribution
+            # arrived before it): that launch leaves this layer's two reductions (sum g', sum g' xhat) in its epilogue
+            # (fc_conv_fwd_bn_bwd_stats; `add` = the earlier contribution, bn_y = this layer's output where act' needs it)
+            # — no reduction pass over x, gy (, y)
+            last, first = (gy, None) if gy2 is None else (gy2, gy)
+            src = G.src.get(last)
+            if Fn.BN_FUSE and src is not None and src[3] == stream and src[1:3] == (rows, C):
+                prod = src[0]
+                p.patch(Bk[prod], stats=p.T(rows, C // 8, 'b', extra=8 * C + 256), bn_x=x, bn_mean=mean, bn_var=var,
+                        bn_gamma=p.S(b.weight), bn_beta=p.S(b.bias), bn_eps=_f(b.eps), bn_act=act,
+                        bn_add=-1 if first is None else first, bn_y=-1 if res is None else y)
+            agx = self.folded(gx)
+            p.emit(Bk, OP_BN_BWD, stream, x=x, y=y if res is not None else -1, gy=gy, n=p.D(rows), c=C, mean=mean, var=var,
+                   cnt=cnt, eps=_f(b.eps), gamma=p.S(b.weight), beta=p.S(b.bias), act=act, gx=gx, gres=gres, sums=si,
+                   gy2=-1 if gy2 is None else gy2, producer=prod, amax_gx=agx)
+            G.arrive(x, gx, rows, C, stream)
+            if res is not None:
+                G.arrive(res, gres, rows, C, stream)
+        self.tape.append(bwd)
+        return y
+
+    def stem(self, stem, inorm):
+        """me_resnet.py conv1: the 3-channel convolution, instance norm + ReLU, max pool -> (tensor, rows, channels)"""
+        p, F, tr, relu = self.p, self.F, self.tr, Fn.ACT['relu']
+        x0, seg1 = p.DY('x0'), p.DY('seg1')
+        t_stem = p.T('n1', 64)
+        col = p.T('n1', 84) if tr else -1
+        p.emit(F, OP_STEM_FWD, S_MAIN, x=x0, w=p.S(stem.kernel), map=p.M('stem'), out=t_stem, col=col)
+        mean_in, var_in, cnt_in = p.T('B', 64), p.T('B', 64), p.T('B', 1)
+        p.emit(F, OP_COL_STATS, S_MAIN, x=t_stem, seg=seg1, n=p.D('n1'), c=64, nseg=p.D('B'), mean=mean_in, var=var_in, cnt=cnt_in)
+        # instance norm + ReLU + max pool in ONE pass (norm.hip k_norm_act_maxpool8_fwd, bit for bit the two operators): the
+        # normalised tensor's only consumer is the pool, and the backward pass recomputes act' from t_stem — it is stored only for
+        # `decisions` (keep_state)
+        t_in = p.T('n1', 64) if p.keep_state else -1
+        if p.keep_state:
+            p.relu_outs.append((t_in, 'n1', 64))
+        t_pool, arg = p.T('n2', 64), p.T('n2', 64)
+        p.pool_arg = (arg, 'n2', 64)
+        ap = self.folded(t_pool)
+        pool_parent = p.T('n1', 1) if tr else -1          # child row -> pooled row (4 bytes per row), for the backward pass
+        p.emit(F, OP_NORM_POOL_FWD, S_MAIN, x=t_stem, seg=seg1, c=64, mean=mean_in, var=var_in, eps=_f(inorm.eps), gamma=p.S(inorm.weight),
+               beta=p.S(inorm.bias), act=relu, map=p.M('pool'), out=t_pool, arg=arg, y=t_in, amax_out=ap, parent=pool_parent)
+        if tr:
+            p.in_sums = p.T('B', 2 * 64, 'b')
+
+            def bwd():
+                p.small.append((None, 'B', 64, inorm.weight, inorm.bias))
+                g_pool = self.grads.take(t_pool, 'n2', 64)
+                g_stem = p.T('n1', 64, 'b')
+                # pool backward + instance-norm backward without the scattered gradient in between: the normalisation backward's
+                # kernels read row r's gradient as g_pool[parent[r]] where arg[parent[r]] == r, else 0 (norm.hip pool_parent) — the sums
+                # in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
+                p.emit(self.Bk, OP_POOL_NORM_BWD, S_MAIN, x=t_stem, g_pool=g_pool, arg=arg, parent=pool_parent, seg=seg1, n=p.D('n1'), c=64,
+                       nseg=p.D('B'), mean=mean_in, var=var_in, cnt=cnt_in, eps=_f(inorm.eps), gamma=p.S(inorm.weight),
+                       beta=p.S(inorm.bias), act=relu, gx=g_stem, sums=p.in_sums)
+                self.wgrad(S_MAIN, OP_STEM_WGRAD, col=col, gout=g_stem, map=p.M('stem'), gw=p.G(stem.kernel))
+                self.wrote(stem.kernel)
+            self.tape.append(bwd)
+        return t_pool, 'n2', 64
+
+    def level(self, li, layer, x):
+        """backbone level li (me_resnet.py BasicBlock: the first one strided, with a 1x1 downsample branch) -> (tensor, rows, channels)"""
+        relu, none, N = Fn.ACT['relu'], Fn.ACT['none'], _Names
+        (cur, cur_rows, _), rows = x, N.rows(li)
+        if self.tr:
+            self.tape.append(lambda: self.flush_small(S_MAIN))           # reversed walk: reached after this level's backward
+        for j, blk in enumerate(layer):
+            if j == 0:
+                assert blk.downsample is not None and blk.conv1.stride == 2
+                t_ds = self.conv(cur, cur_rows, rows, blk.downsample[0], N.ds(li))
+                res = self.bn(t_ds, blk.downsample[1], none, rows)
+                t1 = self.conv(cur, cur_rows, rows, blk.conv1, N.down(li))
+            else:
+                assert blk.downsample is None
+                res = cur
+                t1 = self.conv(cur, rows, rows, blk.conv1, N.same(li))
+            t1 = self.bn(t1, blk.norm1, relu, rows)
+            t2 = self.conv(t1, rows, rows, blk.conv2, N.same(li))
+            cur = self.bn(t2, blk.norm2, relu, rows, res=res)
+        return cur, rows, blk.conv1.out_channels
+
+    def up(self, i, up, x, fb):
+        """neck level i < nl - 1: up_block_{i + 1} on the coarser level's tensor x, joined with the backbone's `fb` -> (tensor, rows, channels)"""
+        p, F, Bk, G, tr, elu = self.p, self.F, self.Bk, self.grads, self.tr, Fn.ACT['elu']
+        (x, x_rows, x_C), (fb, fb_rows, _) = x, fb
+        g_rows, Ci = _Names.gen(i), up[0].out_channels
+        # generative transposed convolution: one dense GEMM (n, Cin) x (Cin, 8 Cout) whose (n, 8 Cout) output IS the
+        # (8 n, Cout) children matrix (row 8 i + k); its weight gradient comes out in the GEMM's layout and is permuted
+        # into the layer's (8, Cin, Cout) kernel gradient afterwards
+        gw_tmp = torch.zeros((x_C, 8 * Ci), dtype=torch.float32, device=p.dev)
+        gw_i = p.S(gw_tmp)
+
+        def bwd_perm():
+            p.emit(Bk, OP_PERMUTE_GENT, S_WGRAD if p.wgrad_async else S_MAIN, src=gw_i, dst=p.G(up[0].kernel), cin=x_C, cout=Ci)
+            self.wrote(up[0].kernel)
+            self.flush_small(S_MAIN)                     # ... and after every neck level's up-block
+        if tr:
+            self.tape.append(bwd_perm)                   # forward order: BEFORE the GEMM, so the reversed walk reaches it after
+        t = self.conv(x, x_rows, x_rows, dense=(p.gent_w[p.gents.index(up[0])], gw_i))
+        t = self.bn(t, up[1], elu, g_rows)
+        t = self.conv(t, g_rows, g_rows, up[3], _Names.gsame(i))
+        # x = inputs[i] + t: every backbone voxel lies in the generated set -> the union IS the generated set (sparse.CoordMap.union)
+        # and the up block's last normalisation writes it (r7): its apply kernel adds the backbone row behind the activation
+        # through the inverse of rows{i} and folds the amax word of the SUM, complete when that kernel ends — before the head
+        # branch forks.  (The map is made here, two small launches, not by fc_plan_maps: the plan's outputs and interface stay.)
+        rows_i = p.DY(_Names.union(i))
+        inv_i = p.T(g_rows, 1)
+        p.emit(F, OP_INV_ROWS, S_MAIN, rows=rows_i, n=p.D(fb_rows), n_inv=p.D(g_rows), inv=inv_i)
+        u = self.bn(t, up[4], elu, g_rows, add=(inv_i, fb))
+
+        def bwd_union():
+            # d u / d (normalisation output) = identity on all rows (n_a == n_union): the layer's backward, next in the
+            # reversed walk, takes the gradient of u as its own
+            gu = G.take(u, g_rows, Ci)
+            gfb = p.T(fb_rows, Ci, 'b')
+            p.emit(Bk, OP_GATHER, S_MAIN, src=gu, idx=rows_i, n=p.D(fb_rows), c=Ci, dst=gfb)
+            G.arrive(fb, gfb, fb_rows, Ci, S_MAIN)
+        if tr:
+            self.tape.append(bwd_union)
+        return u, g_rows, Ci
+
+    def head(self, i, ob, x):
+        """out_block_i + forward_single of neck level i on its tensor x: on the head stream for i > 0"""
+        p, F, Bk, tr = self.p, self.F, self.Bk, self.tr
+        nh, n_reg, n_cls = p.det.neck_with_head, self.n_reg, self.n_cls
+        x, rows, _ = x
+        hs = S_HEAD if (p.head_overlap and i > 0) else S_MAIN
+        if hs == S_HEAD:
+            self.sync(F, S_MAIN, S_HEAD, EV_FORK + i)
+            self.tape = []
+            self.branches[i] = (x, self.tape)
+        o = self.conv(x, rows, rows, ob[0], _Names.same(p.nl) if i == p.nl - 1 else _Names.gsame(i), stream=hs)
+        o = self.bn(o, ob[1], Fn.ACT['elu'], rows, stream=hs)
+        gw_head = p.SA(self.head_part[i].data_ptr()) if tr else -1
+
+        def partial_done():
+            self.head_partials += 1
+            if self.head_partials == self.n_heads and p.wgrad_async:
+                # every level's partial of the packed head kernel is on its way, all on the weight-gradient stream:
+                # sum them there right away (the head's parameters sit in the first gradient bucket to leave)
+                self.head_wfin(S_WGRAD)
+        if tr:
+            self.tape.append(partial_done)               # forward order: BEFORE the GEMM, so the reversed walk reaches it right after
+        y = self.conv(o, rows, rows, dense=(p.packed, gw_head), stream=hs)
+        off = _Names.off(i)
+        outs = [p.AL(t, off, c) for t, c in zip(p.out_idx, (1, n_reg, n_cls, 1))]
+        p.emit(F, OP_HEAD_FWD, hs, y=y, ld=64, bias=p.S(nh.cls_conv.bias), scale=p.S(nh.scales[i].scale), n=p.D(rows), n_reg=n_reg,
+               n_cls=n_cls, cent=outs[0], bbox=outs[1], cls=outs[2], cmax=outs[3])
+
+        def bwd():
+            gy = p.T(rows, 64, 'b')
+            gin = [p.AL(g, off, c) for g, c in zip(p.gout_idx, (1, n_reg, n_cls))]
+            # ... with d loss / d scale of this level and this level's share of the class-bias gradient (column sums of
+            # d loss / d cls_score; summed over the levels by OP_HEAD_WFIN) out of the same pass (r5: they were single-block
+            # reductions over every location, k_col_sum: 0.35 ms per step on the dependent chain)
+            agy = self.folded(gy)        # the kernel folds max |gy| for the backward-data GEMM behind it
+            p.emit(Bk, OP_HEAD_BWD, hs, y=y, ld=64, scale=p.S(nh.scales[i].scale), bbox=outs[1], g_cent=gin[0], g_bbox=gin[1],
+                   g_cls=gin[2], n=p.D(rows), n_reg=n_reg, n_cls=n_cls, gy=gy, gs_row=-1, g_scale=p.G(nh.scales[i].scale),
+                   bias_part=p.SA(self.bias_part[i].data_ptr()), amax_gy=agy)
+            self.wrote(nh.scales[i].scale)
+            self.grads.arrive(y, gy, rows, 64, hs)
+        if tr:
+            self.tape.append(bwd)
+        self.tape = self.main
+
+    # ---- backward program --------------------------------------------------------------------------------------------------
+    def backward(self):
+        p, Bk, tr = self.p, self.Bk, self.tr
+        if self.amax:
+            n_fwd_slots = self.amax_used
+            p.patch(self.F[0], bytes=self.AMAX_SLOT_BYTES * n_fwd_slots)     # the forward pass clears its own words; they stay valid through the backward pass
+            if tr:
+                p.emit(Bk, OP_CLEAR, S_MAIN, dst=p.SA(self.amax_buf.data_ptr() + self.AMAX_SLOT_BYTES * n_fwd_slots), bytes=0)
+        if not tr:
+            return
+        if p.head_overlap:
+            # the head branches depend on the loss gradients only: their backward is enqueued first, on the head stream, finest
+            # forked level first (the main chain needs that one first); each leaves the gradient of its neck tensor behind an event
+            self.sync(Bk, S_MAIN, S_HEAD, EV_BWD0)       # the loss gradients are ready on the caller's stream
+            for lvl in sorted(self.branches):
+                xt, tape = self.branches[lvl]
+                assert xt not in self.grads.full
+                self.branch = lvl
+                for e in reversed(tape):
+                    e()
+                self.flush_small(S_HEAD)                 # this branch's normalisation layer
+                self.branch = None
+                p.emit(Bk, OP_RECORD, S_HEAD, event=EV_HB + lvl)
+                self.grads.deliver(xt, lvl)
+        for e in reversed(self.main):
+            e()
+        assert not self.grads.behind and not self.branch_params, 'a head branch was never joined'
+        if not p.wgrad_async:
+            # without the weight-gradient stream the partials were written on the streams of their levels (main, head): the
+            # main stream has joined every head branch by now
+            self.head_wfin(S_MAIN)
+        self.flush_small(S_MAIN)                         # what is left: the stem's instance norm
+        assert self.head_partials == self.n_heads
+        missing = [n for n, prm in p.det.named_parameters() if prm.requires_grad and id(prm) not in p._pready]
+        if p.tail0:                                      # out_block_0 and scales.0 get their gradients on the per-operator path
+            missing = [n for n in missing if not (n.startswith('neck_with_head.out_block_0.') or n == 'neck_with_head.scales.0.scale')]
+        assert not missing, missing
+        if p.wgrad_async:
+            self.sync(Bk, S_WGRAD, S_MAIN, EV_WEND)
+        if self.amax:
+            p.patch(Bk[0], bytes=self.AMAX_SLOT_BYTES * (self.amax_used - n_fwd_slots))
 
 
 class _Weights:

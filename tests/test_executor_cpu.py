@@ -25,6 +25,9 @@ def _model(levels=4, name='fcaf3d_scannet-3d-18class'):
     return fa.build_detector(m, train_cfg=m.get('train_cfg'), test_cfg=m.get('test_cfg'))
 
 
+_cached_model = functools.lru_cache(None)(_model)       # for tests that only build programs from it
+
+
 @pytest.mark.parametrize('levels,wgrad_async,head_overlap', [(4, False, False), (4, True, True), (2, True, True), (1, False, False)])
 def test_training_program_structure(levels, wgrad_async, head_overlap):
     det = _model(levels)
@@ -124,3 +127,47 @@ def test_batchnorm_fusions_are_wired_consistently():
         assert int((p0.ops_b[:, OP] == E.OP_ADD).sum()) > int((p.ops_b[:, OP] == E.OP_ADD).sum())
     finally:
         Fn.BN_FUSE = True
+
+
+_GRAD_FIELDS = {E.OP_WGRAD: ('gw',), E.OP_STEM_WGRAD: ('gw',), E.OP_PERMUTE_GENT: ('dst',), E.OP_HEAD_BWD: ('g_scale',),
+                E.OP_HEAD_WFIN: ('g_cent', 'g_reg', 'g_cls', 'g_bias')}
+
+
+@pytest.mark.parametrize('tail0', [False, True])
+@pytest.mark.parametrize('head_overlap', [False, True])
+@pytest.mark.parametrize('wgrad_async', [False, True])
+@pytest.mark.parametrize('levels', [4, 2])
+def test_gradient_readiness_covers_every_write(levels, wgrad_async, head_overlap, tail0):
+    """`_pready` (what the data-parallel buckets leave by, NetProgram._bucket_ready) names exactly the parameters some backward
+    operator writes, and no parameter counts as final before its last writer is enqueued — nor, when that writer runs on the head
+    stream, before the main stream has waited for that head branch (the collectives are ordered behind the main and the
+    weight-gradient stream only)."""
+    p = E.NetProgram(_cached_model(levels), True, wgrad_async, head_overlap, tail0=tail0)
+    b = p.ops_b
+    param_at = {p._goff[id(q)]: q for q in p._params}
+    ref = dict(p.grad_refs)                           # address index -> float offset into the gradient buffer
+    writes = []                                       # (row, stream, parameter)
+    for i, row in enumerate(b):
+        op = int(row[OP])
+        for f in _GRAD_FIELDS.get(op, ()):
+            w, p1 = E.FIELDS[op][f]
+            if int(row[w]) - p1 in ref:               # (a dense launch's weight gradient goes to a scratch tensor: OP_PERMUTE_GENT / OP_HEAD_WFIN deliver it)
+                writes.append((i, int(row[STREAM]), param_at[ref[int(row[w]) - p1]]))
+        if op == E.OP_SMALL_GRADS:
+            first, count = (int(row[E.word(op, f)]) for f in ('first', 'count'))
+            writes += [(i, int(row[STREAM]), param_at[int(o) // 4]) for o in p._small_goff[first:first + count]]
+    assert {id(q) for _, _, q in writes} == set(p._pready)
+    for i, _, q in writes:
+        assert p._pready[id(q)] >= i + 1
+    if p.head_overlap:
+        ev = E.word(E.OP_WAIT, 'event')
+        assert E.word(E.OP_RECORD, 'event') == ev
+        # the head branches are enqueued one after the other on stream 1, each ended by the record of EV_HB + its level
+        ends = [(i, int(r[ev])) for i, r in enumerate(b) if r[OP] == E.OP_RECORD and r[STREAM] == E.S_HEAD and r[ev] >= E.EV_HB]
+        joins = {int(r[ev]): i for i, r in enumerate(b) if r[OP] == E.OP_WAIT and r[STREAM] == E.S_MAIN and r[ev] >= E.EV_HB}
+        assert len(ends) == p.nl - 1 and {e for _, e in ends} == set(joins)
+        on_head = [(i, q) for i, s, q in writes if s == E.S_HEAD]
+        assert on_head
+        for i, q in on_head:
+            event = next(e for at, e in ends if at > i)
+            assert p._pready[id(q)] >= joins[event] + 1
