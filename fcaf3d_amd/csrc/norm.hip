@@ -8,9 +8,7 @@
 // BasicBlock (MinkowskiEngine.modules.resnet_block), fcaf3d_neck_with_head.py:53-54,67-71,76,125.
 #include "fc_common.h"
 #include "../../include/fcaf3d_hip.h"
-
-#define MAXSEG 64
-#define MAXBLOCKS 1024       // partial-sum blocks of the two-level reductions
+#include "norm_route.h"      // every launch's geometry, the row-block caps, FIN_CB x FIN_SL
 
 __device__ static inline int seg_of(const int* seg, int seg_stride, int64_t row) {
   return seg ? seg[row * seg_stride] : 0;
@@ -168,12 +166,7 @@ __global__ __launch_bounds__(256) void k_seg_meanvar_final(const float* __restri
 
 // ---- pass 2: sum partials over blocks (fixed order); block = 16 channels x 64 slices -----------------
 // mode 0: out = sum / cnt (mean), also writes cnt[seg];  mode 1: out = sum / cnt (biased variance); mode 2: out = sum
-// r5: 4 channels x 64 slices = 256 threads per block (r1-r4: 64 channels x 16 slices = 1 024 threads).  These launches are pure
-// latency, and a 1 024-thread workgroup needs four free wave slots on every SIMD of ONE compute unit: beside the weight-gradient
-// stream (two resident 250-register workgroups per CU) it waited for a whole CU to drain — up to 1.8 ms for a 10 us kernel
-// (rocprofv3, r5).  256-thread workgroups fit next to anything; 64 slices keep the chain per thread at nb / 256 loads.
-#define FIN_CB 4
-#define FIN_SL 64
+// (FIN_CB channels x FIN_SL slices per block, 256 threads since r5: norm_route.h)
 __global__ __launch_bounds__(256) void k_stats_final(const float* __restrict__ part, const float* __restrict__ part_cnt,
                                                       int64_t nblocks, int nseg, int C, int mode, float* __restrict__ out,
                                                       float* __restrict__ cnt_io) {
@@ -622,7 +615,6 @@ __global__ void k_scatter_rows_add(const float* __restrict__ src, const int* __r
 // re-reduce the (<= 64) partials in its prologue (a few hundred KB out of L2) and apply straight away.
 // Forward statistics in one pass: sums of (x - s) and (x - s)^2 with the shift s = x[0][c] (a sample of the
 // column, so |mean - s| ~ sigma and E[(x-s)^2] - E[x-s]^2 loses no digits).
-#define BN1_MAXB 64
 
 // part [nb][2][C]
 __global__ void k_bn1_partial(const float* __restrict__ x, int64_t n, int C, int64_t rpb, float* __restrict__ part) {
@@ -1059,83 +1051,8 @@ __global__ __launch_bounds__(256) void k_bn2_finalize(const float* __restrict__ 
   }
 }
 
-extern "C" {
-
-static int stats_geometry(int C, int* threads, size_t* smem_fwd, size_t* smem_bwd) {
-  if (C < 4 || C % 4 || C > 1024) return FC_EINVAL;
-  int c4n = C / 4;
-  int nrl = 256 / c4n;
-  if (nrl < 1) nrl = 1;
-  if (nrl > 16) nrl = 16;
-  *threads = nrl * c4n;
-  *smem_fwd = (size_t)(nrl * C + nrl) * sizeof(float);
-  *smem_bwd = (size_t)(nrl * 2 * C) * sizeof(float);
-  return FC_OK;
-}
-
-static void red_plan(int64_t n, int64_t* nb, int64_t* rpb) {
-  int64_t m = n > 0 ? n : 1;
-  int64_t g = fc_cdiv(m, 64);
-  if (g > MAXBLOCKS) g = MAXBLOCKS;
-  *rpb = fc_cdiv(m, g);
-  *nb = fc_cdiv(m, *rpb);
-}
-
-int64_t fc_col_stats_ws_bytes(int64_t n, int C, int nseg) {
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  return nb * nseg * (2 * (int64_t)C + 1) * (int64_t)sizeof(float);
-}
-
-// mean (nseg,C), var (nseg,C) biased, cnt (nseg) ; seg = per-row segment id pointer (NULL -> one segment)
-int fc_col_stats(const float* x, const int* seg, int seg_stride, int64_t n, int C, int nseg, float* mean, float* var,
-                 float* cnt, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  if (n < 0 || nseg < 1 || nseg > MAXSEG) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_col_stats_ws_bytes(n, C, nseg)) return FC_EWS;
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  float* part_cnt = part + nb * nseg * 2 * C;
-  if (n == 0) {
-    FC_HIP(hipMemsetAsync(mean, 0, sizeof(float) * nseg * C, stream));
-    FC_HIP(hipMemsetAsync(var, 0, sizeof(float) * nseg * C, stream));
-    FC_HIP(hipMemsetAsync(cnt, 0, sizeof(float) * nseg, stream));
-    return FC_OK;
-  }
-  // r5: ONE pass over x (sums of x and of x^2 per block and segment), combined in fp64 — r1-r4 read x twice (mean, then the
-  // centred squares), four launches
-  k_stats_partial<<<(unsigned)nb, threads, sf, stream>>>(x, seg, seg_stride, n, C, nseg, nullptr, 2, rpb, part, part_cnt);
-  FC_CHECK_LAUNCH();
-  k_seg_meanvar_final<<<(unsigned)(nseg * ((C + 3) / 4)), 256, 0, stream>>>(part, part_cnt, nb, nseg, C, mean, var, cnt);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
-// out (nseg,C) = per-segment column sums of x (N,C) — deterministic two-level reduction
-int fc_seg_col_sums(const float* x, const int* seg, int seg_stride, int64_t n, int C, int nseg, float* out, void* ws,
-                    int64_t ws_bytes, hipStream_t stream) {
-  if (n < 0 || nseg < 1 || nseg > MAXSEG) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_col_stats_ws_bytes(n, C, nseg)) return FC_EWS;
-  if (n == 0) {
-    FC_HIP(hipMemsetAsync(out, 0, sizeof(float) * nseg * C, stream));
-    return FC_OK;
-  }
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  k_stats_partial<<<(unsigned)nb, threads, sf, stream>>>(x, seg, seg_stride, n, C, nseg, nullptr, 0, rpb, part, nullptr);
-  FC_CHECK_LAUNCH();
-  k_stats_final<<<(unsigned)(nseg * ((C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, nb, nseg, C, 2, out, nullptr);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
 // BatchNorm1d running statistics (momentum update with the unbiased variance) + num_batches_tracked, one launch
-__global__ void k_bn_running(const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ cnt,
+extern "C" __global__ void k_bn_running(const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ cnt,
                              float momentum, int C, float* __restrict__ rmean, float* __restrict__ rvar,
                              long long* __restrict__ nbt) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1147,6 +1064,128 @@ __global__ void k_bn_running(const float* __restrict__ mean, const float* __rest
   rvar[c] = (1.f - momentum) * rvar[c] + momentum * var[c] * unbias;
 }
 
+// ---- a route (norm_route.h) to its launches ------------------------------------------------------------------------------------------
+#define FC_GRID(l, stream) dim3((l).grid_x, (l).grid_y), (l).threads, (l).lds, stream
+
+// fc_bn_train_fwd / fc_bn_train_add_fwd / fc_bn_act_train_fwd, and with apply == false fc_bn_stats_train: the argument checks, the route, its
+// workspace, its launches.  table: the producer's [nb_part][2][groups * C]; amax (nullable): max |y| into the caller's (zeroed) word
+static int bn_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual, int act, float momentum,
+                  float* y, float* mean, float* var, float* cnt, float* rmean, float* rvar, long long* nbt, const float* table, int64_t nb_part, int groups,
+                  int64_t small_elems, const int* add_inv, const float* add_src, void* ws, int64_t ws_bytes, hipStream_t stream, unsigned* amax,
+                  bool apply = true) {
+  if (act < 0 || act > 2 || (add_inv == nullptr) != (add_src == nullptr)) return FC_EINVAL;
+  const NormRoute r = norm_fwd_route(n, C, table != nullptr, nb_part, groups, small_elems);
+  if (int rc = route_check(r, ws_bytes)) return rc;
+  float* part = (float*)ws;
+  if (r.red.threads) { k_bn1_partial<<<FC_GRID(r.red, stream)>>>(x, n, C, r.red_rpb, part); FC_CHECK_LAUNCH(); }
+  if (r.fin.threads) {
+    if (r.sums == FC_NSTATS_PARTIAL) k_bn_finalize<<<FC_GRID(r.fin, stream)>>>(part, (int)r.np, C, n, x, momentum, mean, var, cnt, rmean, rvar, nbt);
+    else k_bn2_finalize<<<FC_GRID(r.fin, stream)>>>(table, (int)r.np, C, groups, n, momentum, mean, var, cnt, rmean, rvar, nbt);
+    FC_CHECK_LAUNCH();
+  }
+  if (!apply) return FC_OK;
+  if (r.apply == FC_NAPPLY_BN1)
+    k_bn1_apply<<<FC_GRID(r.ap, stream)>>>(x, n, C, r.rpb, part, (int)r.np, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, rmean, rvar, nbt, add_inv, add_src);
+  else if (r.apply == FC_NAPPLY_BN2)
+    k_bn2_apply<<<FC_GRID(r.ap, stream)>>>(x, n, C, r.rpb, table, (int)r.np, groups, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, rmean, rvar, nbt, r.cg,
+                                   add_inv, add_src, amax);
+  else
+    k_norm_act_fwd<<<FC_GRID(r.ap, stream)>>>(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, amax);
+  FC_CHECK_LAUNCH();
+  if (r.amax == FC_NAMAX_PASS && amax) return fc_amax(y, n * (int64_t)C, amax, stream);      // (k_bn1_apply does not fold)
+  return FC_OK;
+}
+
+// every backward entry point: the argument checks, the route, its workspace, its launches.  gy2 (nullable): a second contribution to the
+// incoming gradient; table: gy's producer's [nb_part][2][C]; POOL: gy is the pooled gradient, read through parent / argrow; amax (nullable):
+// max |gx| into the caller's (zeroed) word — late_hint: the word of fc_amax_out_hint, consumed once the checks have passed
+template <bool POOL>
+static int norm_bwd(int form, const float* x, const float* y, const float* gy, const float* gy2, const int* parent, const int* argrow, const int* seg,
+                    int seg_stride, int64_t n, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps, const float* gamma,
+                    const float* beta, int act, float* gx, float* gres, float* sums, const float* table, int64_t nb_part, int64_t small_elems, void* ws,
+                    int64_t ws_bytes, hipStream_t stream, unsigned* amax, bool late_hint = false) {
+  if (act < 0 || act > 2) return FC_EINVAL;
+  const NormRoute r = norm_bwd_route(n, C, nseg, table != nullptr, nb_part, small_elems, form);
+  if (int rc = route_check(r, ws_bytes)) return rc;
+  if (late_hint) amax = take_amax_out();
+  if (r.apply == FC_NBAPPLY_NONE) {      // no rows
+    FC_HIP(hipMemsetAsync(sums, 0, sizeof(float) * nseg * 2 * C, stream));
+    return FC_OK;
+  }
+  if (r.sums == FC_NRED_PARTIAL) {
+    k_norm_bwd_partial<POOL><<<FC_GRID(r.red, stream)>>>(x, y, gy, gy2, parent, argrow, seg, seg_stride, n, C, nseg, mean, var, eps, act, gamma, beta, r.red_rpb, (float*)ws);
+    FC_CHECK_LAUNCH();
+    table = (const float*)ws;
+  }
+  if (r.apply == FC_NBAPPLY_PROLOGUE) {
+    k_bn1_bwd_apply<<<FC_GRID(r.ap, stream)>>>(x, y, gy, gy2, n, C, r.rpb, table, (int)r.np, mean, var, eps, gamma, beta, act, gx, gres, sums, r.cg, amax);
+  } else {
+    k_stats_final<<<FC_GRID(r.fin, stream)>>>(table, nullptr, r.np, nseg, 2 * C, 2, sums, nullptr);
+    FC_CHECK_LAUNCH();
+    k_norm_bwd_apply<POOL><<<FC_GRID(r.ap, stream)>>>(x, y, gy, gy2, parent, argrow, seg, seg_stride, n, C, mean, var, eps, gamma, beta, sums, cnt, act, gx, gres, amax);
+  }
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+static int route_out(const NormRoute& r, int* out) {
+  const int f[16] = {r.sums, r.apply, r.amax, (int)r.np, (int)r.nb, (int)r.rpb, r.cg, r.ap.threads, (int)r.ap.lds, (int)r.ap.grid_x, (int)r.ap.grid_y,
+                     (int)r.ws_bytes, (r.red.threads != 0) + (r.fin.threads != 0) + (r.ap.threads != 0)};
+  for (int i = 0; i < 16; ++i) out[i] = f[i];
+  return r.sums ? FC_OK : FC_EINVAL;
+}
+
+extern "C" {
+
+int64_t fc_col_stats_ws_bytes(int64_t n, int C, int nseg) {
+  return row_blocks(n, MAXBLOCKS).nb * nseg * (2 * (int64_t)C + 1) * (int64_t)sizeof(float);
+}
+
+// mean (nseg,C), var (nseg,C) biased, cnt (nseg) ; seg = per-row segment id pointer (NULL -> one segment)
+int fc_col_stats(const float* x, const int* seg, int seg_stride, int64_t n, int C, int nseg, float* mean, float* var,
+                 float* cnt, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  if (n < 0 || nseg < 1 || nseg > MAXSEG) return FC_EINVAL;
+  StatsGeometry g;
+  if (!stats_geometry(C, &g)) return FC_EINVAL;
+  if (ws_bytes < fc_col_stats_ws_bytes(n, C, nseg)) return FC_EWS;
+  const RowBlocks b = row_blocks(n, MAXBLOCKS);
+  float* part = (float*)ws;
+  float* part_cnt = part + b.nb * nseg * 2 * C;
+  if (n == 0) {
+    FC_HIP(hipMemsetAsync(mean, 0, sizeof(float) * nseg * C, stream));
+    FC_HIP(hipMemsetAsync(var, 0, sizeof(float) * nseg * C, stream));
+    FC_HIP(hipMemsetAsync(cnt, 0, sizeof(float) * nseg, stream));
+    return FC_OK;
+  }
+  // r5: ONE pass over x (sums of x and of x^2 per block and segment), combined in fp64 — r1-r4 read x twice (mean, then the
+  // centred squares), four launches
+  k_stats_partial<<<(unsigned)b.nb, g.threads, g.lds_fwd, stream>>>(x, seg, seg_stride, n, C, nseg, nullptr, 2, b.rpb, part, part_cnt);
+  FC_CHECK_LAUNCH();
+  k_seg_meanvar_final<<<(unsigned)(nseg * ((C + 3) / 4)), 256, 0, stream>>>(part, part_cnt, b.nb, nseg, C, mean, var, cnt);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+// out (nseg,C) = per-segment column sums of x (N,C) — deterministic two-level reduction
+int fc_seg_col_sums(const float* x, const int* seg, int seg_stride, int64_t n, int C, int nseg, float* out, void* ws,
+                    int64_t ws_bytes, hipStream_t stream) {
+  if (n < 0 || nseg < 1 || nseg > MAXSEG) return FC_EINVAL;
+  StatsGeometry g;
+  if (!stats_geometry(C, &g)) return FC_EINVAL;
+  if (ws_bytes < fc_col_stats_ws_bytes(n, C, nseg)) return FC_EWS;
+  if (n == 0) {
+    FC_HIP(hipMemsetAsync(out, 0, sizeof(float) * nseg * C, stream));
+    return FC_OK;
+  }
+  const RowBlocks b = row_blocks(n, MAXBLOCKS);
+  float* part = (float*)ws;
+  k_stats_partial<<<(unsigned)b.nb, g.threads, g.lds_fwd, stream>>>(x, seg, seg_stride, n, C, nseg, nullptr, 0, b.rpb, part, nullptr);
+  FC_CHECK_LAUNCH();
+  k_stats_final<<<(unsigned)(nseg * ((C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, b.nb, nseg, C, 2, out, nullptr);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
 int fc_bn_running_update(const float* mean, const float* var, const float* cnt, float momentum, int C, float* running_mean,
                          float* running_var, long long* num_batches_tracked, hipStream_t stream) {
   if (C < 1) return FC_EINVAL;
@@ -1156,90 +1195,48 @@ int fc_bn_running_update(const float* mean, const float* var, const float* cnt, 
   return FC_OK;
 }
 
-// ---- small-tensor BatchNorm, two launches per direction --------------------------------------------------
-static void bn1_plan(int64_t n, int64_t* nb, int64_t* rpb) {
-  int64_t m = n > 0 ? n : 1;
-  int64_t g = fc_cdiv(m, 64);
-  if (g > BN1_MAXB) g = BN1_MAXB;
-  *rpb = fc_cdiv(m, g);
-  *nb = fc_cdiv(m, *rpb);
+// ---- the normalisation entry points -------------------------------------------------------------------------------------------------
+int fc_bn_train_fwd_route(int64_t n, int C, int has_part, int64_t nb_part, int groups, int64_t small_elems, int* out) {
+  return out ? route_out(norm_fwd_route(n, C, has_part != 0, nb_part, groups, small_elems), out) : FC_EINVAL;
+}
+int fc_bn_train_bwd_route(int64_t n, int C, int nseg, int has_part, int64_t nb_part, int64_t small_elems, int form, int* out) {
+  if (!out || form < FC_NFORM_TRAIN || form > FC_NFORM_SEG) return FC_EINVAL;
+  return route_out(norm_bwd_route(n, C, nseg, has_part != 0, nb_part, small_elems, form), out);
 }
 
-int64_t fc_bn_small_ws_bytes(int C) { return (int64_t)BN1_MAXB * 2 * C * (int64_t)sizeof(float); }
-
-int64_t fc_bn_stats_ws_bytes(int64_t n, int C) {
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  return nb * 2 * (int64_t)C * (int64_t)sizeof(float);
-}
+// the byte counts the routes check (norm_route.h)
+int64_t fc_bn_small_ws_bytes(int C) { return small_ws_bytes(C); }
+int64_t fc_bn_stats_ws_bytes(int64_t n, int C) { return reduce_ws_bytes(n, C, 1); }
+int64_t fc_norm_act_bwd_ws_bytes(int64_t n, int C, int nseg) { return reduce_ws_bytes(n, C, nseg); }
+int64_t fc_maxpool8_norm_act_bwd_ws_bytes(int64_t n_in, int C, int nseg) { return reduce_ws_bytes(n_in, C, nseg); }
+// whichever route fc_bn_train_fwd / fc_bn_train_bwd take of (n, C): small or general without a table, none behind a table
+int64_t fc_bn_train_ws_bytes(int64_t n, int C) { return reduce_ws_bytes(n, C, 1) > small_ws_bytes(C) ? reduce_ws_bytes(n, C, 1) : small_ws_bytes(C); }
 
 // training-mode BatchNorm statistics of a feature matrix of any size in one pass over x (+ buffer update):
 // mean (C), biased var (C), cnt (1).  Follow with fc_norm_act_fwd.
 int fc_bn_stats_train(const float* x, int64_t n, int C, float momentum, float* mean, float* var, float* cnt,
                       float* running_mean, float* running_var, long long* num_batches_tracked, void* ws,
                       int64_t ws_bytes, hipStream_t stream) {
-  if (n < 1) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_bn_stats_ws_bytes(n, C)) return FC_EWS;
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  k_bn1_partial<<<(unsigned)nb, threads, sb, stream>>>(x, n, C, rpb, part);
-  FC_CHECK_LAUNCH();
-  k_bn_finalize<<<(unsigned)((C + 63) / 64), 1024, 0, stream>>>(part, (int)nb, C, n, x, momentum, mean, var, cnt, running_mean,
-                                                                running_var, num_batches_tracked);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
+  return bn_fwd(x, n, C, 0.f, nullptr, nullptr, nullptr, 0, momentum, nullptr, mean, var, cnt, running_mean, running_var, num_batches_tracked, nullptr, 0, 1,
+                -1, nullptr, nullptr, ws, ws_bytes, stream, nullptr, false);      // the statistics step of the general route (no n * C is <= -1)
 }
 
 // training-mode BatchNorm forward for one segment: statistics + running-buffer update + normalise/affine/residual/act.
 // mean/var (C) and cnt (1) are written for the backward pass; running_* / num_batches_tracked may be NULL.
-static int bn_act_train_fwd_add(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta,
-                                const float* residual, int act, float momentum, float* y, float* mean, float* var, float* cnt,
-                                float* running_mean, float* running_var, long long* num_batches_tracked, const int* add_inv,
-                                const float* add_src, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  if (n < 1 || act < 0 || act > 2) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_bn_small_ws_bytes(C)) return FC_EWS;
-  int64_t nb, rpb;
-  bn1_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  k_bn1_partial<<<(unsigned)nb, threads, sb, stream>>>(x, n, C, rpb, part);
-  FC_CHECK_LAUNCH();
-  k_bn1_apply<<<(unsigned)nb, threads, sb, stream>>>(x, n, C, rpb, part, (int)nb, eps, gamma, beta, residual, act, momentum, y,
-                                                    mean, var, cnt, running_mean, running_var, num_batches_tracked, add_inv, add_src);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
-}
-
 int fc_bn_act_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta,
                         const float* residual, int act, float momentum, float* y, float* mean, float* var, float* cnt,
                         float* running_mean, float* running_var, long long* num_batches_tracked, void* ws,
                         int64_t ws_bytes, hipStream_t stream) {
-  return bn_act_train_fwd_add(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
-                              num_batches_tracked, nullptr, nullptr, ws, ws_bytes, stream);
+  return bn_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, nullptr, 0, 1,
+                INT64_MAX, nullptr, nullptr, ws, ws_bytes, stream, nullptr);      // the two-launch route whatever the size; the hint is not consumed
 }
 
-// its backward: sums (2,C) = [d beta, d gamma]
+// its backward: sums (2,C) = [d beta, d gamma]; max |gx| into the word of fc_amax_out_hint
 int fc_bn_act_train_bwd(const float* x, const float* y, const float* gy, int64_t n, int C, const float* mean,
                         const float* var, float eps, const float* gamma, const float* beta, int act, float* gx, float* gres,
                         float* sums, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  if (n < 1 || act < 0 || act > 2) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_bn_small_ws_bytes(C)) return FC_EWS;
-  int64_t nb, rpb;
-  bn1_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  k_norm_bwd_partial<false><<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb, part);
-  FC_CHECK_LAUNCH();
-  unsigned* ao = take_amax_out();
-  k_bn1_bwd_apply<<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, n, C, rpb, part, (int)nb, mean, var, eps, gamma, beta, act, gx,
-                                                        gres, sums, C, ao);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
+  return norm_bwd<false>(FC_NFORM_SMALL, x, y, gy, nullptr, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, nullptr, eps, gamma, beta, act, gx, gres, sums,
+                         nullptr, 0, 0, ws, ws_bytes, stream, nullptr, true);
 }
 
 // add_inv / add_src (both or neither): y[r] += add_src[add_inv[r]] where add_inv[r] >= 0, behind the activation
@@ -1249,8 +1246,7 @@ int fc_norm_act_add_fwd(const float* x, const int* seg, int seg_stride, int64_t 
   unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
   if (n < 0 || C < 4 || C % 4 || act < 0 || act > 2 || (add_inv == nullptr) != (add_src == nullptr)) return FC_EINVAL;
   if (n == 0) return FC_OK;
-  k_norm_act_fwd<<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, seg, seg_stride, n, C, mean, var, eps, gamma,
-                                                                         beta, residual, act, add_inv, add_src, y, ao);
+  k_norm_act_fwd<<<FC_GRID(rows_launch(n, C), stream)>>>(x, seg, seg_stride, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, ao);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
@@ -1258,154 +1254,58 @@ int fc_norm_act_add_fwd(const float* x, const int* seg, int seg_stride, int64_t 
 int fc_norm_act_fwd(const float* x, const int* seg, int seg_stride, int64_t n, int C, const float* mean, const float* var,
                     float eps, const float* gamma, const float* beta, const float* residual, int act, float* y,
                     hipStream_t stream) {
-  return fc_norm_act_add_fwd(x, seg, seg_stride, n, C, mean, var, eps, gamma, beta, residual, act, nullptr, nullptr, y, stream);
-}
-
-int64_t fc_norm_act_bwd_ws_bytes(int64_t n, int C, int nseg) {
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  return nb * nseg * 2 * (int64_t)C * (int64_t)sizeof(float);
-}
-
-// sums (nseg,2,C): [.,0,.] = sum g' (= d beta per segment), [.,1,.] = sum g'*xhat (= d gamma per segment)
-int fc_norm_act_bwd(const float* x, const float* y, const float* gy, const int* seg, int seg_stride, int64_t n, int C,
-                    int nseg, const float* mean, const float* var, const float* cnt, float eps, const float* gamma,
-                    const float* beta, int act, float* gx, float* gres, float* sums, void* ws, int64_t ws_bytes,
-                    hipStream_t stream) {
-  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |gx| into the caller's (zeroed) word
-  if (n < 0 || nseg < 1 || nseg > MAXSEG || act < 0 || act > 2) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_norm_act_bwd_ws_bytes(n, C, nseg)) return FC_EWS;
-  if (n == 0) {
-    FC_HIP(hipMemsetAsync(sums, 0, sizeof(float) * nseg * 2 * C, stream));
-    return FC_OK;
-  }
-  int64_t nb, rpb;
-  red_plan(n, &nb, &rpb);
-  float* part = (float*)ws;
-  k_norm_bwd_partial<false><<<(unsigned)nb, threads, sb, stream>>>(x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, nseg, mean, var, eps, act,
-                                                          gamma, beta, rpb, part);
-  FC_CHECK_LAUNCH();
-  k_stats_final<<<(unsigned)(nseg * ((2 * C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, nb, nseg, 2 * C, 2, sums, nullptr);
-  FC_CHECK_LAUNCH();
-  k_norm_bwd_apply<false><<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, mean,
-                                                                           var, eps, gamma, beta, sums, cnt, act, gx, gres, ao);
+  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
+  if (n < 0 || C < 4 || C % 4 || act < 0 || act > 2) return FC_EINVAL;
+  if (n == 0) return FC_OK;
+  k_norm_act_fwd<<<FC_GRID(rows_launch(n, C), stream)>>>(x, seg, seg_stride, n, C, mean, var, eps, gamma, beta, residual, act, nullptr, nullptr, y, ao);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
 
+// sums (nseg,2,C): [.,0,.] = sum g' (= d beta per segment), [.,1,.] = sum g'*xhat (= d gamma per segment); max |gx| into the hint's word
+int fc_norm_act_bwd(const float* x, const float* y, const float* gy, const int* seg, int seg_stride, int64_t n, int C,
+                    int nseg, const float* mean, const float* var, const float* cnt, float eps, const float* gamma,
+                    const float* beta, int act, float* gx, float* gres, float* sums, void* ws, int64_t ws_bytes,
+                    hipStream_t stream) {
+  unsigned* ao = take_amax_out();
+  return norm_bwd<false>(FC_NFORM_SEG, x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums,
+                         nullptr, 0, 0, ws, ws_bytes, stream, ao);
+}
+
 // ---- r5: training-mode BatchNorm, one entry point per direction for every size ------------------------------------------------
-// channel window of the prologue-reducing apply kernels: with few row blocks (the deep levels: 872 x 512, 3.5k x 256) a block owns 64
-// channels and the grid's y dimension walks the windows — 8x the blocks, 16 row lanes each, the SAME total table traffic; else all of C
-static int ap_window(int64_t n, int C) { return (C >= 128 && C % 64 == 0 && fc_cdiv(n > 0 ? n : 1, 64) * (C / 64) <= 1024 && fc_cdiv(n > 0 ? n : 1, 64) < 128) ? 64 : C; }
-static void ap_plan(int64_t n, int64_t* nb, int64_t* rpb) {     // apply grid of the prologue-reducing kernels: up to 256 blocks
-  int64_t m = n > 0 ? n : 1;
-  int64_t g = fc_cdiv(m, 64);
-  if (g > 256) g = 256;
-  *rpb = fc_cdiv(m, g);
-  *nb = fc_cdiv(m, *rpb);
-}
-
-int64_t fc_bn_train_ws_bytes(int64_t n, int C) {
-  const int64_t a = fc_bn_stats_ws_bytes(n, C), b = fc_norm_act_bwd_ws_bytes(n, C, 1), c = fc_bn_small_ws_bytes(C);
-  return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-
-// Forward.  part == NULL: the statistics are computed here from x (n * C <= small_elems: fc_bn_act_train_fwd, else fc_bn_stats_train +
-// fc_norm_act_fwd — the r1-r4 routes).  part != NULL: nb_part row blocks of producer-written column sums [nb_part][2][groups * C]
-// (see k_bn2_apply); x is then (groups * n_rows_of_the_producer, C) = n rows.
+// Forward.  part == NULL: the statistics are computed here from x (n * C <= small_elems: the two launches of fc_bn_act_train_fwd, else
+// those of fc_bn_stats_train + fc_norm_act_fwd — the r1-r4 routes).  part != NULL: nb_part row blocks of producer-written column sums
+// [nb_part][2][groups * C] (see k_bn2_apply); x is then (groups * n_rows_of_the_producer, C) = n rows.
 // add_inv / add_src (both or neither, r7): the sparse sum behind the layer, y[r] += add_src[add_inv[r]] where add_inv[r] >= 0,
-// written (and folded into the amax word) by whichever apply kernel the size routes to
+// written (and folded into the amax word of fc_amax_out_hint) by whichever apply kernel the size routes to
 int fc_bn_train_add_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
                         int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
                         float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
                         int64_t small_elems, const int* add_inv, const float* add_src, void* ws, int64_t ws_bytes,
                         hipStream_t stream) {
-  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |y| into the caller's (zeroed) word
-  if (n < 1 || act < 0 || act > 2 || (add_inv == nullptr) != (add_src == nullptr)) return FC_EINVAL;
-  if (!part) {
-    if (n * C <= small_elems) {
-      int rc = bn_act_train_fwd_add(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
-                                    num_batches_tracked, add_inv, add_src, ws, ws_bytes, stream);
-      if (rc == FC_OK && ao) rc = fc_amax(y, n * (int64_t)C, ao, stream);          // (this route's apply kernel does not fold: a pass of its own)
-      return rc;
-    }
-    int rc = fc_bn_stats_train(x, n, C, momentum, mean, var, cnt, running_mean, running_var, num_batches_tracked, ws, ws_bytes, stream);
-    if (rc) return rc;
-    t_fc_amax_out = ao;
-    return fc_norm_act_add_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, stream);
-  }
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (nb_part < 1 || nb_part > 0x7fffffff / 64 || groups < 1 || groups > 64) return FC_EINVAL;
-  if (nb_part <= BN1_MAXB) {
-    int64_t nb, rpb;
-    ap_plan(n, &nb, &rpb);
-    const int CG = ap_window(n, C);
-    if (CG != C && stats_geometry(CG, &threads, &sf, &sb)) return FC_EINVAL;
-    const size_t smem = (size_t)(threads / (CG / 4)) * 2 * CG * sizeof(double);
-    k_bn2_apply<<<dim3((unsigned)nb, C / CG), threads, smem, stream>>>(x, n, C, rpb, part, (int)nb_part, groups, eps, gamma, beta, residual, act,
-                                                        momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, CG,
-                                                        add_inv, add_src, ao);
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  k_bn2_finalize<<<(unsigned)((C + FIN_CB - 1) / FIN_CB), FIN_CB * FIN_SL, 0, stream>>>(part, (int)nb_part, C, groups, n, momentum, mean, var, cnt,
-                                                                 running_mean, running_var, num_batches_tracked);
-  FC_CHECK_LAUNCH();
-  t_fc_amax_out = ao;
-  return fc_norm_act_add_fwd(x, nullptr, 0, n, C, mean, var, eps, gamma, beta, residual, act, add_inv, add_src, y, stream);
+  unsigned* ao = take_amax_out();
+  return bn_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, part, nb_part, groups,
+                small_elems, add_inv, add_src, ws, ws_bytes, stream, ao);
 }
 
 int fc_bn_train_fwd(const float* x, int64_t n, int C, float eps, const float* gamma, const float* beta, const float* residual,
                     int act, float momentum, float* y, float* mean, float* var, float* cnt, float* running_mean,
                     float* running_var, long long* num_batches_tracked, const float* part, int64_t nb_part, int groups,
                     int64_t small_elems, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  return fc_bn_train_add_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var,
-                             num_batches_tracked, part, nb_part, groups, small_elems, nullptr, nullptr, ws, ws_bytes, stream);
+  unsigned* ao = take_amax_out();
+  return bn_fwd(x, n, C, eps, gamma, beta, residual, act, momentum, y, mean, var, cnt, running_mean, running_var, num_batches_tracked, part, nb_part, groups,
+                small_elems, nullptr, nullptr, ws, ws_bytes, stream, ao);
 }
 
 // Backward.  gy2 (nullable): a second contribution to the incoming gradient, added on the fly.  part == NULL: the sums of g' and
-// g' xhat are reduced here (two or three launches by size, as fc_bn_act_train_bwd / fc_norm_act_bwd); part != NULL: nb_part blocks
-// [nb_part][2][C] written by the producer of gy.
+// g' xhat are reduced here (two or three launches by size); part != NULL: nb_part blocks [nb_part][2][C] written by the producer of gy.
 int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float* gy2, int64_t n, int C, const float* mean,
                     const float* var, const float* cnt, float eps, const float* gamma, const float* beta, int act, float* gx,
                     float* gres, float* sums, const float* part, int64_t nb_part, int64_t small_elems, void* ws, int64_t ws_bytes,
                     hipStream_t stream) {
-  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |gx| into the caller's (zeroed) word
-  if (n < 1 || act < 0 || act > 2) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  const float* p = part;
-  int64_t np = nb_part;
-  if (!p) {
-    const bool small = n * C <= small_elems;
-    if (ws_bytes < (small ? fc_bn_small_ws_bytes(C) : fc_norm_act_bwd_ws_bytes(n, C, 1))) return FC_EWS;
-    int64_t rpb;
-    if (small) bn1_plan(n, &np, &rpb); else red_plan(n, &np, &rpb);
-    k_norm_bwd_partial<false><<<(unsigned)np, threads, sb, stream>>>(x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, eps, act, gamma, beta, rpb,
-                                                            (float*)ws);
-    FC_CHECK_LAUNCH();
-    p = (const float*)ws;
-  }
-  if (np < 1) return FC_EINVAL;
-  if (np <= BN1_MAXB) {
-    int64_t nb, rpb;
-    if (!part) bn1_plan(n, &nb, &rpb); else ap_plan(n, &nb, &rpb);
-    const int CG = ap_window(n, C);
-    if (CG != C && stats_geometry(CG, &threads, &sf, &sb)) return FC_EINVAL;
-    k_bn1_bwd_apply<<<dim3((unsigned)nb, C / CG), threads, sb, stream>>>(x, y, gy, gy2, n, C, rpb, p, (int)np, mean, var, eps, gamma, beta, act, gx,
-                                                          gres, sums, CG, ao);
-    FC_CHECK_LAUNCH();
-    return FC_OK;
-  }
-  k_stats_final<<<(unsigned)((2 * C + FIN_CB - 1) / FIN_CB), FIN_CB * FIN_SL, 0, stream>>>(p, nullptr, np, 1, 2 * C, 2, sums, nullptr);
-  FC_CHECK_LAUNCH();
-  k_norm_bwd_apply<false><<<(unsigned)fc_cdiv(n * (C / 4), 256), 256, 0, stream>>>(x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, mean, var, eps, gamma,
-                                                                           beta, sums, cnt, act, gx, gres, ao);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
+  unsigned* ao = take_amax_out();
+  return norm_bwd<false>(FC_NFORM_TRAIN, x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums, part, nb_part,
+                         small_elems, ws, ws_bytes, stream, ao);
 }
 
 int fc_amax_out_hint(unsigned* amax_word) {
@@ -1463,34 +1363,15 @@ int fc_norm_act_maxpool8_fwd(const float* x, const int* seg, int seg_stride, int
   return FC_OK;
 }
 
-int64_t fc_maxpool8_norm_act_bwd_ws_bytes(int64_t n_in, int C, int nseg) { return fc_norm_act_bwd_ws_bytes(n_in, C, nseg); }
-
 // fc_norm_act_bwd (y == NULL, no residual) whose incoming gradient is read through the pool: the launches, the geometry and the order of
 // every sum are those of fc_norm_act_bwd over the n_in rows — gx and sums are bit for bit what zero fill + fc_maxpool_bwd + fc_norm_act_bwd give
 int fc_maxpool8_norm_act_bwd(const float* x, const float* gout, const int* argrow, const int* parent, const int* seg, int seg_stride,
                              int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps,
                              const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
                              hipStream_t stream) {
-  if (n_in < 0 || nseg < 1 || nseg > MAXSEG || act < 0 || act > 2 || !parent || !argrow) return FC_EINVAL;
-  int threads; size_t sf, sb;
-  if (stats_geometry(C, &threads, &sf, &sb)) return FC_EINVAL;
-  if (ws_bytes < fc_maxpool8_norm_act_bwd_ws_bytes(n_in, C, nseg)) return FC_EWS;
-  if (n_in == 0) {
-    FC_HIP(hipMemsetAsync(sums, 0, sizeof(float) * nseg * 2 * C, stream));
-    return FC_OK;
-  }
-  int64_t nb, rpb;
-  red_plan(n_in, &nb, &rpb);
-  float* part = (float*)ws;
-  k_norm_bwd_partial<true><<<(unsigned)nb, threads, sb, stream>>>(x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C, nseg, mean, var,
-                                                          eps, act, gamma, beta, rpb, part);
-  FC_CHECK_LAUNCH();
-  k_stats_final<<<(unsigned)(nseg * ((2 * C + FIN_CB - 1) / FIN_CB)), FIN_CB * FIN_SL, 0, stream>>>(part, nullptr, nb, nseg, 2 * C, 2, sums, nullptr);
-  FC_CHECK_LAUNCH();
-  k_norm_bwd_apply<true><<<(unsigned)fc_cdiv(n_in * (C / 4), 256), 256, 0, stream>>>(x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C,
-                                                                              mean, var, eps, gamma, beta, sums, cnt, act, gx, nullptr, nullptr);
-  FC_CHECK_LAUNCH();
-  return FC_OK;
+  if (!parent || !argrow) return FC_EINVAL;
+  return norm_bwd<true>(FC_NFORM_SEG, x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, nullptr,
+                        sums, nullptr, 0, 0, ws, ws_bytes, stream, nullptr);      // (the hint is not consumed)
 }
 
 int fc_inverse_rows(const int* rows, int64_t n, int64_t n_inv, int* inv, hipStream_t stream) {

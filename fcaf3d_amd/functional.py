@@ -410,57 +410,17 @@ import os as _os
 # r5: BatchNorm statistics from the producing convolution's epilogue, and the add of a two-consumer tensor's gradients inside the
 # BatchNorm backward kernels (csrc/norm.hip fc_bn_train_fwd / fc_bn_train_bwd); 0: the r4 kernels (A/B switch)
 BN_FUSE = _os.environ.get('FC_BN_FUSE', '1') != '0'
-# matrices up to this size take the two-launch BatchNorm path (measured r1: equal speed up to 1 M elements, fewer host
-# launches; at 4 M the <=64-block grid is slower than the general path)
+# matrices up to this size take the two-launch BatchNorm path (the `small_elems` of csrc/norm_route.h, where the r1 measurement stands)
 BN_SMALL_ELEMS = 1024 * 1024
 
 
-class _BNTrainSmall(torch.autograd.Function):
-    """Training-mode BatchNorm (+act, +residual) of a small (N,C) matrix: 2 launches forward, 2 backward
-    (statistics, running-buffer update and apply fused; csrc/norm.hip k_bn1_*)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, residual, eps, act, momentum, rmean, rvar, nbt):
-        _chk(x, gamma, beta, residual)
-        x = x.contiguous()
-        n, C = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        stats = torch.empty((2, C), dtype=torch.float32, device=dev)       # [mean, var]
-        cnt = torch.empty(1, dtype=torch.float32, device=dev)
-        res = residual.contiguous() if residual is not None else None
-        g = gamma.reshape(-1).contiguous()
-        b = beta.reshape(-1).contiguous()
-        ws = L.workspace(L.query('fc_bn_small_ws_bytes', C), dev)
-        L.call('fc_bn_act_train_fwd', L.ptr(x), n, C, float(eps), L.ptr(g), L.ptr(b), L.ptr(res), act, float(momentum),
-               L.ptr(y), L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(cnt), L.ptr(rmean), L.ptr(rvar), L.ptr(nbt), L.ptr(ws),
-               ws.numel(), L.stream())
-        ctx.save_for_backward(x, y if res is not None else None, g, stats, b)
-        ctx.cfg = (float(eps), act, residual is not None, gamma.shape, beta.shape)
-        ctx.mark_non_differentiable(stats, cnt)
-        ctx.set_materialize_grads(False)           # no zero-filled grads for the two statistics outputs
-        return y, stats, cnt
-
-    @staticmethod
-    def backward(ctx, gy, _gs, _gc):
-        x, y, g, stats, b = ctx.saved_tensors
-        eps, act, has_res, gshape, bshape = ctx.cfg
-        gy = gy.contiguous()
-        n, C = x.shape
-        dev = x.device
-        gx = torch.empty_like(x)
-        gres = torch.empty_like(x) if has_res else None
-        sums = torch.empty((2, C), dtype=torch.float32, device=dev)
-        ws = L.workspace(L.query('fc_bn_small_ws_bytes', C), dev)
-        L.call('fc_bn_act_train_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), n, C, L.ptr(stats[0]), L.ptr(stats[1]), eps, L.ptr(g),
-               L.ptr(b), act, L.ptr(gx), L.ptr(gres), L.ptr(sums), L.ptr(ws), ws.numel(), L.stream())
-        return gx, sums[1].reshape(gshape), sums[0].reshape(bshape), gres, None, None, None, None, None, None
-
-
-class _BNTrainFused(torch.autograd.Function):
-    """Training-mode BatchNorm (+act, +residual) whose batch statistics come from the statistics table of the convolution that
-    produced x (`part` (nb, 2, groups * C): csrc/norm.hip fc_bn_train_fwd) — the route the native executor takes, so that the
-    two paths stay bit for bit equal in the forward pass; the backward pass is the r4 one (fc_bn_train_bwd without a table)."""
+class _BNTrain(torch.autograd.Function):
+    """Training-mode BatchNorm (+act, +residual) of an (N,C) matrix through one entry point per direction, with the statistics,
+    the running-buffer update and the apply fused (csrc/norm.hip, routes: csrc/norm_route.h).
+    part is None: a small matrix, fc_bn_act_train_fwd / fc_bn_act_train_bwd — 2 launches forward, 2 backward (k_bn1_*).
+    part (nb, 2, groups * C): the statistics table of the convolution that produced x, fc_bn_train_fwd — the route the native
+    executor takes, so that the two paths stay bit for bit equal in the forward pass; the backward pass is the r4 one
+    (fc_bn_train_bwd without a table)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, eps, act, momentum, rmean, rvar, nbt, part, groups):
@@ -474,31 +434,48 @@ class _BNTrainFused(torch.autograd.Function):
         res = residual.contiguous() if residual is not None else None
         g = gamma.reshape(-1).contiguous()
         b = beta.reshape(-1).contiguous()
-        ws = L.workspace(L.query('fc_bn_train_ws_bytes', n, C), dev)
-        L.call('fc_bn_train_fwd', L.ptr(x), n, C, float(eps), L.ptr(g), L.ptr(b), L.ptr(res), act, float(momentum), L.ptr(y),
-               L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(cnt), L.ptr(rmean), L.ptr(rvar), L.ptr(nbt), L.ptr(part), part.shape[0],
-               groups, BN_SMALL_ELEMS, L.ptr(ws), ws.numel(), L.stream())
+        head = (L.ptr(x), n, C, float(eps), L.ptr(g), L.ptr(b), L.ptr(res), act, float(momentum), L.ptr(y), L.ptr(stats[0]),
+                L.ptr(stats[1]), L.ptr(cnt), L.ptr(rmean), L.ptr(rvar), L.ptr(nbt))
+        if part is None:
+            ws = L.workspace(L.query('fc_bn_small_ws_bytes', C), dev)
+            L.call('fc_bn_act_train_fwd', *head, L.ptr(ws), ws.numel(), L.stream())
+        else:
+            ws = L.workspace(L.query('fc_bn_train_ws_bytes', n, C), dev)
+            L.call('fc_bn_train_fwd', *head, L.ptr(part), part.shape[0], groups, BN_SMALL_ELEMS, L.ptr(ws), ws.numel(), L.stream())
         ctx.save_for_backward(x, y if res is not None else None, g, stats, b, cnt)
-        ctx.cfg = (float(eps), act, residual is not None, gamma.shape, beta.shape)
+        ctx.cfg = (float(eps), act, residual is not None, gamma.shape, beta.shape, part is None)
         ctx.mark_non_differentiable(stats, cnt)
-        ctx.set_materialize_grads(False)
+        ctx.set_materialize_grads(False)           # no zero-filled grads for the two statistics outputs
         return y, stats, cnt
 
     @staticmethod
     def backward(ctx, gy, _gs, _gc):
         x, y, g, stats, b, cnt = ctx.saved_tensors
-        eps, act, has_res, gshape, bshape = ctx.cfg
+        eps, act, has_res, gshape, bshape, small = ctx.cfg
         gy = gy.contiguous()
         n, C = x.shape
         dev = x.device
         gx = torch.empty_like(x)
         gres = torch.empty_like(x) if has_res else None
         sums = torch.empty((2, C), dtype=torch.float32, device=dev)
-        ws = L.workspace(L.query('fc_bn_train_ws_bytes', n, C), dev)
-        L.call('fc_bn_train_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), None, n, C, L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(cnt), eps,
-               L.ptr(g), L.ptr(b), act, L.ptr(gx), L.ptr(gres), L.ptr(sums), None, 0, BN_SMALL_ELEMS, L.ptr(ws), ws.numel(),
-               L.stream())
+        tail = (eps, L.ptr(g), L.ptr(b), act, L.ptr(gx), L.ptr(gres), L.ptr(sums))
+        if small:
+            ws = L.workspace(L.query('fc_bn_small_ws_bytes', C), dev)
+            L.call('fc_bn_act_train_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), n, C, L.ptr(stats[0]), L.ptr(stats[1]), *tail, L.ptr(ws),
+                   ws.numel(), L.stream())
+        else:
+            ws = L.workspace(L.query('fc_bn_train_ws_bytes', n, C), dev)
+            L.call('fc_bn_train_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), None, n, C, L.ptr(stats[0]), L.ptr(stats[1]), L.ptr(cnt), *tail,
+                   None, 0, BN_SMALL_ELEMS, L.ptr(ws), ws.numel(), L.stream())
         return gx, sums[1].reshape(gshape), sums[0].reshape(bshape), gres, None, None, None, None, None, None, None, None
+
+
+class _BNTrainSmall(_BNTrain):
+    """_BNTrain without a statistics table (a class of its own: oracle/record.py hooks `forward` per path)"""
+
+
+class _BNTrainFused(_BNTrain):
+    """_BNTrain behind a convolution's statistics table"""
 
 
 def bn_train(x, gamma, beta, residual, eps, act, momentum, rmean, rvar, nbt, part=None, groups=1):
@@ -510,7 +487,7 @@ def bn_train(x, gamma, beta, residual, eps, act, momentum, rmean, rvar, nbt, par
         y, stats, cnt = _BNTrainFused.apply(x, gamma, beta, residual, eps, ACT[act], momentum, rmean, rvar, nbt, part, groups)
         return y, (stats[0:1], stats[1:2], cnt)
     if 0 < n * C <= BN_SMALL_ELEMS and gamma is not None and beta is not None:
-        y, stats, cnt = _BNTrainSmall.apply(x, gamma, beta, residual, eps, ACT[act], momentum, rmean, rvar, nbt)
+        y, stats, cnt = _BNTrainSmall.apply(x, gamma, beta, residual, eps, ACT[act], momentum, rmean, rvar, nbt, None, 1)
         return y, (stats[0:1], stats[1:2], cnt)
     # general size: one statistics pass (shifted sums) + finalise/buffer update + apply = 3 launches
     xc = x.detach().contiguous()

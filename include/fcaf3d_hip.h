@@ -34,9 +34,10 @@ extern "C" {
  * fc_conv_amax_hint / fc_amax_out_hint added; weight images are mode-dependent and fc_x6_weight_images writes their amax word), -> 8
  * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation), -> 9 (fc_norm_act_maxpool8_fwd / fc_maxpool8_norm_act_bwd / fc_inverse_rows / fc_norm_act_add_fwd /
  * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates), -> 10 (fc_conv_fwd_route /
- * fc_conv_wgrad_route added: the launch a convolution call becomes, as data).  A caller built against another
+ * fc_conv_wgrad_route added: the launch a convolution call becomes, as data), -> 11 (fc_bn_train_fwd_route / fc_bn_train_bwd_route
+ * added: the launches a normalisation call becomes, as data).  A caller built against another
  * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 10
+#define FC_ABI_VERSION 11
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -412,6 +413,32 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
                     const float* var, const float* cnt, float eps, const float* gamma, const float* beta, int act, float* gx,
                     float* gres, float* sums, const float* part, int64_t nb_part, int64_t small_elems, void* ws, int64_t ws_bytes,
                     hipStream_t stream);
+
+/* Which launches a training-mode normalisation call becomes (fc_bn_train_fwd / _add_fwd and the backward entry points: ME.MinkowskiBatchNorm /
+ * MinkowskiInstanceNorm with their activations, me_resnet.py:3, :22-23, :56-63; fcaf3d_neck_with_head.py:53, :62, :68).  Pure host
+ * functions, no GPU needed: the route the entry points compute before they launch (csrc/norm_route.h), written as 16 ints (unused
+ * ones 0).  Return 0, or -1 exactly where the entry point would for these sizes (then out[0] = 0, the INVALID family).
+ * fc_bn_train_fwd_route: the arguments of fc_bn_train_fwd (fc_bn_act_train_fwd: small_elems = INT64_MAX; fc_bn_stats_train: the
+ * statistics step of small_elems = -1).  fc_bn_train_bwd_route, form (FC_NFORM_*): TRAIN fc_bn_train_bwd, SMALL fc_bn_act_train_bwd,
+ * SEG fc_norm_act_bwd and fc_maxpool8_norm_act_bwd (n = n_in); has_part / nb_part / small_elems as in fc_bn_train_bwd (TRAIN only).
+ * out[] of both, by FC_NROUTE_*: who makes the per-block sums — forward, the batch statistics (FC_NSTATS_*: the apply kernel's
+ * prologue over the producer's table, k_bn1_partial on <= 64 blocks, k_bn1_partial on <= 1024 blocks + k_bn_finalize,
+ * k_bn2_finalize over the table); backward, the sums of g' and g' xhat (FC_NRED_*: the producer's table, k_norm_bwd_partial) —,
+ * the apply step (forward FC_NAPPLY_*: k_bn1_apply, k_bn2_apply, k_norm_act_fwd; backward FC_NBAPPLY_*: none — no rows, sums
+ * zero-filled —, k_bn1_bwd_apply re-reducing in its prologue, k_stats_final + k_norm_bwd_apply), where the word of fc_amax_out_hint
+ * is filled (FC_NAMAX_*: by the apply kernel, by a pass of its own), the blocks of the table of sums, row blocks / rows per block /
+ * channels per block of a prologue-reducing apply kernel, threads / LDS bytes / grid of the apply kernel, the workspace bytes the
+ * entry point checks, the kernel launches (the amax pass not counted). */
+enum { FC_NFORM_TRAIN, FC_NFORM_SMALL, FC_NFORM_SEG };
+enum { FC_NSTATS_INVALID, FC_NSTATS_PROLOGUE, FC_NSTATS_PARTIAL_SMALL, FC_NSTATS_PARTIAL, FC_NSTATS_TABLE };
+enum { FC_NAPPLY_NONE, FC_NAPPLY_BN1, FC_NAPPLY_BN2, FC_NAPPLY_ROWS };
+enum { FC_NAMAX_NONE, FC_NAMAX_FOLDED, FC_NAMAX_PASS };
+enum { FC_NRED_INVALID, FC_NRED_TABLE, FC_NRED_PARTIAL };
+enum { FC_NBAPPLY_NONE, FC_NBAPPLY_PROLOGUE, FC_NBAPPLY_FINAL };
+enum { FC_NROUTE_SUMS, FC_NROUTE_APPLY, FC_NROUTE_AMAX, FC_NROUTE_NP, FC_NROUTE_NB, FC_NROUTE_RPB, FC_NROUTE_CG, FC_NROUTE_THREADS, FC_NROUTE_LDS,
+       FC_NROUTE_GRID_X, FC_NROUTE_GRID_Y, FC_NROUTE_WS_BYTES, FC_NROUTE_LAUNCHES };
+int fc_bn_train_fwd_route(int64_t n, int C, int has_part, int64_t nb_part, int groups, int64_t small_elems, int* out);
+int fc_bn_train_bwd_route(int64_t n, int C, int nseg, int has_part, int64_t nb_part, int64_t small_elems, int form, int* out);
 
 /* ME.MinkowskiMaxPooling(k=2,s=2) — me_resnet.py:24. */
 int fc_maxpool_fwd(const float* in, const int* nbr, int64_t n_out, int K, int C, float* out, int* argrow,

@@ -144,3 +144,71 @@ def test_route_queries_refuse_what_the_launch_refuses():
     assert wgrad(n, n, 27, 48, 64, 0, PAIRS) == -1 and wgrad(n, n, 27, 64, 64, Fn.CONV_FMA, PAIRS) == -1 and wgrad(n, n, 27, 64, 64, 0, PAIRS) == 0
     assert wgrad(n, n, 27, 64, 64, 0, SORTED) == -1          # (row_index of fc_conv_wgrad is reserved)
     assert L.route('fc_conv_fwd_route', n, n, 27, 48, 64, 0, PAIRS, 0)[1]['family'] == E['FC_FAM_INVALID']
+
+
+# ---- the normalisation route queries (fc_bn_train_fwd_route / fc_bn_train_bwd_route, csrc/norm_route.h) ---------------------------------
+
+NORM_N = (0, 1, 63, 64, 65, 872, 3500, 4096, 4097, 16383, 65536, 65537, 441000, 3000000)
+NORM_C = (4, 8, 64, 128, 192, 256, 512, 1024)
+NORM_NSEG = (1, 8, 64)
+
+
+def test_norm_size_queries_agree_with_the_route_queries():
+    """the grid the six norm size queries were compared on against the parent of the route refactor (profiles/r7_notes.md section 9):
+    every route fc_bn_train_fwd / fc_bn_train_bwd can take of (n, C) fits fc_bn_train_ws_bytes(n, C), and each specific size query
+    equals the workspace bytes of its entry point's route"""
+    import itertools
+    E = L.header_enums()
+    TRAIN, SMALL, SEG = (E['FC_NFORM_' + k] for k in ('TRAIN', 'SMALL', 'SEG'))
+    ALWAYS, NEVER = (1 << 63) - 1, -1                    # small_elems of fc_bn_act_train_fwd / of fc_bn_stats_train's statistics step
+    fwd = lambda *a: L.route('fc_bn_train_fwd_route', *a)
+    bwd = lambda *a: L.route('fc_bn_train_bwd_route', *a)
+    l = L.lib()
+    for n, C in itertools.product(NORM_N, NORM_C):
+        bound = l.fc_bn_train_ws_bytes(n, C)
+        assert bound == max(l.fc_bn_stats_ws_bytes(n, C), l.fc_norm_act_bwd_ws_bytes(n, C, 1), l.fc_bn_small_ws_bytes(C))
+        for has_part, nb_part, small in itertools.product((0, 1), (1, 64, 65, 200), (0, 1 << 20)):
+            for rc, r in (fwd(n, C, has_part, nb_part, 1, small), bwd(n, C, 1, has_part, nb_part, small, TRAIN)):
+                assert rc == (0 if n >= 1 else -1), (n, C, has_part, nb_part, small)
+                assert 0 <= r['ws_bytes'] <= bound, (n, C, has_part, nb_part, small, r, bound)
+                assert (r['ws_bytes'] == 0) == (has_part == 1 or n < 1), (n, C, has_part, r)
+        if n >= 1:
+            # without a table: the small or the general route's bytes, which fc_bn_act_train_* / fc_bn_stats_train ask for by themselves
+            assert fwd(n, C, 0, 0, 1, ALWAYS)[1]['ws_bytes'] == bwd(n, C, 1, 0, 0, ALWAYS, TRAIN)[1]['ws_bytes'] == l.fc_bn_small_ws_bytes(C)
+            assert bwd(n, C, 1, 0, 0, 0, SMALL)[1]['ws_bytes'] == l.fc_bn_small_ws_bytes(C)
+            assert fwd(n, C, 0, 0, 1, NEVER)[1]['ws_bytes'] == bwd(n, C, 1, 0, 0, 0, TRAIN)[1]['ws_bytes'] == l.fc_bn_stats_ws_bytes(n, C)
+        for nseg in NORM_NSEG:
+            rc, r = bwd(n, C, nseg, 0, 0, 0, SEG)
+            assert rc == 0 and r['ws_bytes'] == l.fc_norm_act_bwd_ws_bytes(n, C, nseg) == l.fc_maxpool8_norm_act_bwd_ws_bytes(n, C, nseg), (n, C, nseg, r)
+            # fc_col_stats: the same row blocks (cap 1024), 2 C sums + a count per block and segment
+            assert l.fc_col_stats_ws_bytes(n, C, nseg) * 2 * C == l.fc_norm_act_bwd_ws_bytes(n, C, nseg) * (2 * C + 1)
+
+
+def test_norm_route_queries_refuse_what_the_launch_refuses():
+    """fc_bn_train_fwd_route / fc_bn_train_bwd_route return -1 exactly for the sizes the entry point answers with -1"""
+    E = L.header_enums()
+    TRAIN, SMALL, SEG = (E['FC_NFORM_' + k] for k in ('TRAIN', 'SMALL', 'SEG'))
+    fwd = lambda *a: L.route('fc_bn_train_fwd_route', *a)[0]
+    bwd = lambda *a: L.route('fc_bn_train_bwd_route', *a)[0]
+    n = 1000
+    for C, rc in ((0, -1), (3, -1), (4, 0), (6, -1), (66, -1), (1024, 0), (1028, -1), (2048, -1)):      # C < 4, C % 4, C > 1024
+        for small in (0, 1 << 20):
+            assert fwd(n, C, 0, 0, 1, small) == rc and fwd(n, C, 1, 10, 1, small) == rc, (C, small)
+        for form in (TRAIN, SMALL, SEG):
+            assert bwd(n, C, 1, 0, 0, 0, form) == rc, (form, C)
+    assert fwd(0, 64, 0, 0, 1, 0) == -1 and fwd(-1, 64, 0, 0, 1, 0) == -1 and fwd(1, 64, 0, 0, 1, 0) == 0      # n < 1
+    assert bwd(0, 64, 1, 0, 0, 0, TRAIN) == -1 and bwd(0, 64, 1, 0, 0, 0, SMALL) == -1 and bwd(1, 64, 1, 0, 0, 0, TRAIN) == 0
+    # per-segment statistics (fc_norm_act_bwd, fc_maxpool8_norm_act_bwd): no rows is a call, 1..64 segments
+    assert bwd(0, 64, 1, 0, 0, 0, SEG) == 0 and bwd(-1, 64, 1, 0, 0, 0, SEG) == -1
+    assert bwd(n, 64, 0, 0, 0, 0, SEG) == -1 and bwd(n, 64, 64, 0, 0, 0, SEG) == 0 and bwd(n, 64, 65, 0, 0, 0, SEG) == -1
+    assert bwd(n, 64, 2, 0, 0, 0, TRAIN) == -1                      # (one segment there)
+    # a table: groups 1..64 (forward), at least one block
+    for groups, rc in ((0, -1), (1, 0), (8, 0), (64, 0), (65, -1)):
+        assert fwd(n, 64, 1, 10, groups, 0) == rc, groups
+    assert fwd(n, 64, 0, 0, 0, 0) == 0                              # (no table: groups is not looked at)
+    for nb_part, rc in ((-1, -1), (0, -1), (1, 0), (64, 0), (65, 0)):
+        assert fwd(n, 64, 1, nb_part, 1, 0) == rc and bwd(n, 64, 1, 1, nb_part, 0, TRAIN) == rc, nb_part
+    assert fwd(n, 64, 1, 0x7fffffff // 64 + 1, 1, 0) == -1
+    assert bwd(n, 64, 1, 0, 0, 0, 3) == -1 and bwd(n, 64, 1, 0, 0, 0, -1) == -1                          # unknown forms
+    assert L.route('fc_bn_train_fwd_route', n, 6, 0, 0, 1, 0)[1]['sums'] == E['FC_NSTATS_INVALID']
+    assert L.route('fc_bn_train_bwd_route', n, 6, 1, 0, 0, 0, TRAIN)[1]['sums'] == E['FC_NRED_INVALID']

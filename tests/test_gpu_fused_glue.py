@@ -276,3 +276,166 @@ def test_union_written_by_the_normalisation_is_bit_identical_eval(n_g, n_b, Cc):
            L.ptr(fb), L.ptr(u1), L.stream())
     assert torch.equal(u1, u0)
     assert _amax_word(slot1) == _amax_word(slot0) != 0
+
+
+# ---- every route of csrc/norm_route.h once, at the smallest shape that reaches it ------------------------------------------------------
+
+def _route_case_inputs(n, Cc, seed, dev):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(n, Cc, generator=g) * 1.5 + 0.3).to(dev)
+    gy = torch.randn(n, Cc, generator=g).to(dev)
+    gamma = (0.5 + torch.rand(Cc, generator=g)).to(dev)
+    beta = (0.2 * torch.randn(Cc, generator=g)).to(dev)
+    return x, gy, gamma, beta
+
+
+def _close(a, ref, what):
+    """the project's bound: max-abs error within 1e-4 of the tensor's scale, against float64 numpy"""
+    import numpy as np
+    a = a.detach().cpu().double().numpy().reshape(ref.shape)
+    err, scale = float(np.abs(a - ref).max()), float(np.abs(ref).max())
+    print(f'{what}: max-abs error {err:.3e}, scale {scale:.3e}')
+    assert np.isfinite(a).all() and err <= 1e-4 * scale, (what, err, scale)
+
+
+def _amax_bits(t):
+    t = t[torch.isfinite(t)].abs().max().reshape(1)
+    return int(t.view(torch.int32))
+
+
+def _elu_grad(pre):
+    import numpy as np
+    return np.where(pre > 0, 1.0, np.exp(np.minimum(pre, 0.0)))
+
+
+def test_every_batchnorm_route_against_fp64():
+    """Each family of norm_fwd_route / norm_bwd_route once (selected through small_elems and a torch-built table, so no shape is large):
+    y / gx, mean, var and sums against float64 numpy; the amax word (folded by the apply kernel, or the small route's pass of its own) bit-equal to max |.| of the tensor the
+    kernel wrote; the route query's workspace bytes are what the launch needs — it runs on exactly that many and answers one byte
+    less with FC_EWS, writing nothing."""
+    import numpy as np
+    dev = _dev()
+    E = L.header_enums()
+    l = L.lib()
+    TRAIN, SEG = E['FC_NFORM_TRAIN'], E['FC_NFORM_SEG']
+    nan = float('nan')
+
+    # ---- forward: (n, C, blocks of the table or 0, small_elems) -> the family it must reach
+    fwd_cases = [(100, 8, 0, 1 << 20, 'FC_NSTATS_PARTIAL_SMALL', 'FC_NAPPLY_BN1', 'FC_NAMAX_PASS', 8),
+                 (100, 8, 0, 0, 'FC_NSTATS_PARTIAL', 'FC_NAPPLY_ROWS', 'FC_NAMAX_FOLDED', 8),
+                 (130, 8, 65, 1 << 20, 'FC_NSTATS_TABLE', 'FC_NAPPLY_ROWS', 'FC_NAMAX_FOLDED', 8),
+                 (128, 64, 4, 1 << 20, 'FC_NSTATS_PROLOGUE', 'FC_NAPPLY_BN2', 'FC_NAMAX_FOLDED', 64),
+                 (70, 128, 2, 1 << 20, 'FC_NSTATS_PROLOGUE', 'FC_NAPPLY_BN2', 'FC_NAMAX_FOLDED', 64)]
+    for n, Cc, nbp, small, stats, apply, amax, cg in fwd_cases:
+        x, _, gamma, beta = _route_case_inputs(n, Cc, 100 + n + Cc + nbp, dev)
+        part = _part_table(x, nbp) if nbp else None
+        rc, r = L.route('fc_bn_train_fwd_route', n, Cc, 1 if nbp else 0, nbp, 1, small)
+        assert rc == 0 and (r['sums'], r['apply'], r['amax'], r['cg']) == (E[stats], E[apply], E[amax], cg), (n, Cc, nbp, small, r)
+        need = r['ws_bytes']
+        assert (need > 0) == (nbp == 0)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        y = torch.full((n, Cc), nan, device=dev)
+        mean, var, cnt = torch.full((Cc,), nan, device=dev), torch.full((Cc,), nan, device=dev), torch.full((1,), nan, device=dev)
+        slot = _new_slot(dev)
+        args = (L.ptr(x), n, Cc, EPS, L.ptr(gamma), L.ptr(beta), None, ELU, 0.1, L.ptr(y), L.ptr(mean), L.ptr(var), L.ptr(cnt), None, None, None,
+                L.ptr(part), nbp, 1, small, L.ptr(ws))
+        if need:
+            L.call('fc_amax_out_hint', L.ptr(slot))
+            assert l.fc_bn_train_fwd(*args, need - 1, L.stream()) == -2
+            torch.cuda.synchronize()
+            assert all(bool(torch.isnan(t).all()) for t in (y, mean, var, cnt)) and _amax_word(slot) == 0
+        L.call('fc_amax_out_hint', L.ptr(slot))
+        L.call('fc_bn_train_fwd', *args, need, L.stream())
+        torch.cuda.synchronize()
+        xd = x.cpu().double().numpy()
+        mu, va = xd.mean(0), xd.var(0)
+        pre = (xd - mu) / np.sqrt(va + EPS) * gamma.cpu().double().numpy() + beta.cpu().double().numpy()
+        tag = f'forward {n} x {Cc}, table {nbp}, small_elems {small}'
+        _close(y, np.where(pre > 0, pre, np.expm1(np.minimum(pre, 0.0))), tag + ' y')
+        _close(mean, mu, tag + ' mean')
+        _close(var, va, tag + ' var')
+        assert float(cnt) == n
+        assert _amax_word(slot) == _amax_bits(y) != 0, tag          # folded by the apply kernel, or the small route's pass of its own
+
+    # ---- backward: (n, C, blocks of the producer's table or 0, small_elems)
+    bwd_cases = [(100, 8, 0, 1 << 20, 'FC_NRED_PARTIAL', 'FC_NBAPPLY_PROLOGUE', 2, 8),
+                 (4097, 4, 0, 0, 'FC_NRED_PARTIAL', 'FC_NBAPPLY_FINAL', 65, 4),
+                 (70, 128, 2, 1 << 20, 'FC_NRED_TABLE', 'FC_NBAPPLY_PROLOGUE', 2, 64)]
+    for n, Cc, nbp, small, reduce, apply, np_blocks, cg in bwd_cases:
+        x, gy, gamma, beta = _route_case_inputs(n, Cc, 200 + n + Cc + nbp, dev)
+        xd, gd = x.cpu().double().numpy(), gy.cpu().double().numpy()
+        mean, var = torch.from_numpy(xd.mean(0)).float().to(dev), torch.from_numpy(xd.var(0)).float().to(dev)
+        cnt = torch.full((1,), float(n), device=dev)
+        mu, va = mean.cpu().double().numpy(), var.cpu().double().numpy()          # (the fp32 statistics the kernels are given)
+        inv_std = 1.0 / np.sqrt(va + EPS)
+        xh = (xd - mu) * inv_std
+        gp = gd * _elu_grad(xh * gamma.cpu().double().numpy() + beta.cpu().double().numpy())
+        s0, s1 = gp.sum(0), (gp * xh).sum(0)
+        gx_ref = gamma.cpu().double().numpy() * inv_std * (gp - s0 / n - xh * s1 / n)
+        part = None
+        if nbp:                                                                    # [nb][2][C]: column sums of g' and g' xhat per row block
+            gp_t = torch.from_numpy(gp).float().to(dev)
+            xh_t = torch.from_numpy(xh).float().to(dev)
+            edges = torch.linspace(0, n, nbp + 1).long().tolist()
+            part = torch.stack([torch.stack([gp_t[a:b].sum(0), (gp_t[a:b] * xh_t[a:b]).sum(0)]) for a, b in zip(edges[:-1], edges[1:])]).contiguous()
+        rc, r = L.route('fc_bn_train_bwd_route', n, Cc, 1, 1 if nbp else 0, nbp, small, TRAIN)
+        assert rc == 0 and (r['sums'], r['apply'], r['np'], r['cg']) == (E[reduce], E[apply], np_blocks, cg), (n, Cc, nbp, small, r)
+        need = r['ws_bytes']
+        assert (need > 0) == (nbp == 0)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        gx, sums = torch.full((n, Cc), nan, device=dev), torch.full((2, Cc), nan, device=dev)
+        slot = _new_slot(dev)
+        args = (L.ptr(x), None, L.ptr(gy), None, n, Cc, L.ptr(mean), L.ptr(var), L.ptr(cnt), EPS, L.ptr(gamma), L.ptr(beta), ELU, L.ptr(gx), None,
+                L.ptr(sums), L.ptr(part), nbp, small, L.ptr(ws))
+        if need:
+            L.call('fc_amax_out_hint', L.ptr(slot))
+            assert l.fc_bn_train_bwd(*args, need - 1, L.stream()) == -2
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(gx).all()) and bool(torch.isnan(sums).all()) and _amax_word(slot) == 0
+        L.call('fc_amax_out_hint', L.ptr(slot))
+        L.call('fc_bn_train_bwd', *args, need, L.stream())
+        torch.cuda.synchronize()
+        tag = f'backward {n} x {Cc}, table {nbp}, small_elems {small}'
+        _close(gx, gx_ref, tag + ' gx')
+        _close(sums, np.stack([s0, s1]), tag + ' sums')
+        assert _amax_word(slot) == _amax_bits(gx) != 0, tag                          # (both apply kernels fold)
+
+    # ---- the pooled stem form: 8 parents x 8 children, 2 scenes
+    n_out, n_in, Cc, nseg = 8, 64, 8, 2
+    g = torch.Generator().manual_seed(77)
+    x, _, gamma, beta = _route_case_inputs(n_in, Cc, 300, dev)
+    child = torch.randperm(n_in, generator=g).reshape(n_out, 8)                     # child[o][k]: the input row at offset k of pooled row o
+    parent = torch.empty(n_in, dtype=torch.long)
+    parent[child.reshape(-1)] = torch.arange(n_out).repeat_interleave(8)
+    arg = child.gather(1, torch.randint(0, 8, (n_out, Cc), generator=g))            # the winning child per pooled row and channel
+    g_pool = torch.randn(n_out, Cc, generator=g)
+    seg_in = torch.zeros((n_in, 4), dtype=torch.int32)
+    seg_in[:, 0] = (parent >= n_out // 2).int()
+    scene = seg_in[:, 0].long().numpy()
+    xd = x.cpu().double().numpy()
+    mean = torch.from_numpy(np.stack([xd[scene == s].mean(0) for s in range(nseg)])).float().to(dev)
+    var = torch.from_numpy(np.stack([xd[scene == s].var(0) for s in range(nseg)])).float().to(dev)
+    cnt = torch.tensor([float((scene == s).sum()) for s in range(nseg)], device=dev)
+    mu, va, cn = mean.cpu().double().numpy()[scene], var.cpu().double().numpy()[scene], cnt.cpu().double().numpy()[scene][:, None]
+    inv_std = 1.0 / np.sqrt(va + EPS)
+    xh = (xd - mu) * inv_std
+    gin = np.where(arg.numpy()[parent.numpy()] == np.arange(n_in)[:, None], g_pool.double().numpy()[parent.numpy()], 0.0)
+    gp = gin * _elu_grad(xh * gamma.cpu().double().numpy() + beta.cpu().double().numpy())
+    sums_ref = np.stack([np.stack([gp[scene == s].sum(0), (gp * xh)[scene == s].sum(0)]) for s in range(nseg)])
+    gx_ref = gamma.cpu().double().numpy() * inv_std * (gp - sums_ref[scene, 0] / cn - xh * sums_ref[scene, 1] / cn)
+    rc, r = L.route('fc_bn_train_bwd_route', n_in, Cc, nseg, 0, 0, 0, SEG)
+    assert rc == 0 and (r['sums'], r['apply'], r['launches']) == (E['FC_NRED_PARTIAL'], E['FC_NBAPPLY_FINAL'], 3)
+    need = r['ws_bytes']
+    assert need == L.query('fc_maxpool8_norm_act_bwd_ws_bytes', n_in, Cc, nseg) > 0
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    gx, sums = torch.full((n_in, Cc), nan, device=dev), torch.full((nseg, 2, Cc), nan, device=dev)
+    t = [v.contiguous().to(dev) for v in (g_pool, arg.int(), parent.int(), seg_in)]
+    args = (L.ptr(x), L.ptr(t[0]), L.ptr(t[1]), L.ptr(t[2]), L.ptr(t[3]), 4, n_in, Cc, nseg, L.ptr(mean), L.ptr(var), L.ptr(cnt), EPS, L.ptr(gamma),
+            L.ptr(beta), ELU, L.ptr(gx), L.ptr(sums), L.ptr(ws))
+    assert l.fc_maxpool8_norm_act_bwd(*args, need - 1, L.stream()) == -2
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(gx).all()) and bool(torch.isnan(sums).all())
+    L.call('fc_maxpool8_norm_act_bwd', *args, need, L.stream())
+    torch.cuda.synchronize()
+    _close(gx, gx_ref, 'pooled backward gx')
+    _close(sums, sums_ref, 'pooled backward sums')

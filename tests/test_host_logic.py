@@ -268,6 +268,7 @@ DEVICE_IDENTICAL_SOURCES = {
     '66ec67355c91a62d': '5b97211d4d40026d',      # retired A/B switches, named FC_CONV_* flag bits
     'f17a9bc9f17e6a93': '7094ae11604f2248',      # csrc/exec_ops.h: the executor's row and descriptor layouts by name (host code only)
     'db8f1d2038ec0dfd': '7094ae11604f2248',      # csrc/conv_route.h: every convolution launch's route decided once, as data (host code only)
+    'be6908a911e0989e': '7094ae11604f2248',      # csrc/norm_route.h: every normalisation launch's route decided once, as data (host code only)
 }
 
 
@@ -371,3 +372,65 @@ def test_recorded_routing_decisions():
         l.fc_debug_set_h3r(1)
     expect(fwd(*big), family='FC_FAM_X6', mode='FC_MODE_H3')
     expect(fwd(*mid), family='FC_FAM_H3R', mode='FC_MODE_H3')
+
+
+def test_recorded_norm_routing_decisions():
+    """The routing decisions the comments of csrc/norm_route.h and DESIGN.md section 4 record, as facts of fc_bn_train_fwd_route /
+    fc_bn_train_bwd_route (pure host functions).  The expected values were derived by hand from the host code before the routes
+    existed (red_plan / bn1_plan / ap_plan / ap_window / stats_geometry of csrc/norm.hip at 3936a8a)."""
+    from fcaf3d_amd import _lib as L
+    import fcaf3d_amd.functional as Fn
+    E = L.header_enums()
+    TRAIN, SEG = E['FC_NFORM_TRAIN'], E['FC_NFORM_SEG']
+    SMALL_ELEMS = Fn.BN_SMALL_ELEMS
+    assert SMALL_ELEMS == 1 << 20
+
+    def fwd(n, C, nb_part=0, small=SMALL_ELEMS):
+        rc, r = L.route('fc_bn_train_fwd_route', n, C, 1 if nb_part else 0, nb_part, 1, small)
+        assert rc == 0
+        return r
+
+    def bwd(n, C, nb_part=0, small=SMALL_ELEMS, form=TRAIN, nseg=1):
+        rc, r = L.route('fc_bn_train_bwd_route', n, C, nseg, 1 if nb_part else 0, nb_part, small, form)
+        assert rc == 0
+        return r
+
+    def expect(r, **want):
+        want = {k: E[v] if isinstance(v, str) else v for k, v in want.items()}
+        assert {k: r[k] for k in want} == want, (r, want)
+
+    # the deep levels behind a convolution's table: 64-channel windows, 16 row lanes — 14 x 8 and 55 x 4 blocks of 256 threads, both directions
+    expect(fwd(872, 512, 7), sums='FC_NSTATS_PROLOGUE', apply='FC_NAPPLY_BN2', cg=64, grid_x=14, grid_y=8, threads=256, nb=14, rpb=63, lds=16384)
+    expect(fwd(3500, 256, 28), sums='FC_NSTATS_PROLOGUE', apply='FC_NAPPLY_BN2', cg=64, grid_x=55, grid_y=4, threads=256, nb=55, rpb=64, lds=16384)
+    expect(bwd(872, 512, 7), sums='FC_NRED_TABLE', apply='FC_NBAPPLY_PROLOGUE', cg=64, grid_x=14, grid_y=8, threads=256, lds=8192)
+    expect(bwd(3500, 256, 28), sums='FC_NRED_TABLE', apply='FC_NBAPPLY_PROLOGUE', cg=64, grid_x=55, grid_y=4, threads=256, lds=8192)
+    # the big level: no windows (C < 128), the apply grid's cap of 256 blocks
+    expect(fwd(441000, 64, 64), apply='FC_NAPPLY_BN2', cg=64, grid_x=256, grid_y=1, threads=256, nb=256, rpb=1723)
+    # many row blocks: no windows either (3.5k x 256 has 55; from 128 on, or past 1024 blocks in all)
+    expect(fwd(8192, 256, 64), cg=256, grid_x=128, grid_y=1, threads=256)
+    expect(fwd(8128, 256, 64), cg=64, grid_x=127, grid_y=4)
+    expect(fwd(4097, 1024, 33), cg=1024, grid_x=65, grid_y=1, threads=256)      # 65 x 16 windows > 1024 blocks
+    # a table of <= 64 blocks is ONE launch with the amax folded; of 65, finalize + apply
+    for n, C in ((872, 512), (3500, 256), (441000, 64), (100, 8)):
+        expect(fwd(n, C, 64), sums='FC_NSTATS_PROLOGUE', launches=1, amax='FC_NAMAX_FOLDED', ws_bytes=0)
+        expect(fwd(n, C, 65), sums='FC_NSTATS_TABLE', apply='FC_NAPPLY_ROWS', launches=2, amax='FC_NAMAX_FOLDED', ws_bytes=0,
+               grid_x=-(-n * (C // 4) // 256), grid_y=1, threads=256, lds=0)
+    # no table: up to small_elems two launches plus an amax pass, above it three launches with the amax folded
+    expect(fwd(4096, 256), sums='FC_NSTATS_PARTIAL_SMALL', apply='FC_NAPPLY_BN1', launches=2, amax='FC_NAMAX_PASS', np=64, nb=64, rpb=64, ws_bytes=64 * 2 * 256 * 4)
+    expect(fwd(16384, 64), sums='FC_NSTATS_PARTIAL_SMALL', launches=2, amax='FC_NAMAX_PASS', nb=64, rpb=256)
+    expect(fwd(4097, 256), sums='FC_NSTATS_PARTIAL', apply='FC_NAPPLY_ROWS', launches=3, amax='FC_NAMAX_FOLDED', np=65, ws_bytes=65 * 2 * 256 * 4)
+    expect(fwd(441000, 64), sums='FC_NSTATS_PARTIAL', launches=3, amax='FC_NAMAX_FOLDED', np=1024, ws_bytes=1024 * 2 * 64 * 4)
+    # backward: the producer's table of <= 64 blocks is one launch, a longer one two; without a table two (small) or three
+    expect(bwd(441000, 64, 64), sums='FC_NRED_TABLE', apply='FC_NBAPPLY_PROLOGUE', launches=1, np=64, nb=256, rpb=1723, grid_x=256, grid_y=1)
+    expect(bwd(441000, 64, 65), sums='FC_NRED_TABLE', apply='FC_NBAPPLY_FINAL', launches=2, np=65)
+    expect(bwd(4096, 256), sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_PROLOGUE', launches=2, np=64, nb=64, rpb=64, cg=64, grid_x=64, grid_y=4)
+    expect(bwd(872, 512), sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_PROLOGUE', launches=2, np=14, cg=64, grid_x=14, grid_y=8)
+    expect(bwd(872, 512, form=E['FC_NFORM_SMALL']), apply='FC_NBAPPLY_PROLOGUE', launches=2, cg=512, grid_x=14, grid_y=1, threads=256)      # fc_bn_act_train_bwd: all of C
+    expect(bwd(4097, 4, small=0), sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_FINAL', launches=3, np=65)
+    expect(bwd(441000, 64), sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_FINAL', launches=3, np=1024, grid_x=-(-441000 * 16 // 256), threads=256)
+    # segments: always through k_stats_final, however few blocks; the pooled stem backward is that route over the n_in rows
+    expect(bwd(100, 64, form=SEG, nseg=8), sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_FINAL', launches=3, np=2, ws_bytes=2 * 8 * 2 * 64 * 4)
+    for n_in, nseg in ((64, 2), (180192, 8), (1187000, 8)):
+        r = bwd(n_in, 64, form=SEG, nseg=nseg)
+        expect(r, sums='FC_NRED_PARTIAL', apply='FC_NBAPPLY_FINAL', launches=3, grid_x=-(-n_in * 16 // 256), threads=256)
+        assert r['ws_bytes'] == L.query('fc_maxpool8_norm_act_bwd_ws_bytes', n_in, 64, nseg) == L.query('fc_norm_act_bwd_ws_bytes', n_in, 64, nseg)
