@@ -344,3 +344,41 @@ class TrainStep:
         self.optimizer.load_state_dict(sd['optimizer'])
         if self.lr is not None:
             self.lr.set_epoch(sd.get('epoch', 0))
+
+
+def evaluate(model, batches, gt_annos, metric=(0.25, 0.5), label2cat=None, in_flight=2, scene_ids=None, group=None):
+    """What the reference's tools/test.py:184-190 does with mmdet3d/apis/test.py:10 (single_gpu_test / multi_gpu_test) and the
+    dataset's indoor_eval: run `model` over a validation set and return the mAP / mAR dict.  `batches` yields (points, img_metas)
+    in `gt_annos` order.  `in_flight` batches stay enqueued as in simple_test_async (extract_feat, then get_bboxes(defer=True); the
+    next batch's coordinate phase runs on the host while the GPU works on this one); the results stay on the device and go to
+    evaluation.indoor_eval_device ONCE, after the last batch.  More than one rank: each passes its own batches, gt_annos and
+    global scene_ids (default rank + world_size * i); the ranks' tables are gathered over `group`, every rank returns the same
+    dict.  Runs in eval mode under no_grad and leaves the model in the mode it found it in.  label2cat=None names a class by its
+    number."""
+    from .evaluation import indoor_eval_device
+    modes = [(m, m.training) for m in model.modules()]                 # every module's own flag: frozen parts stay frozen
+    if any(t for _, t in modes):
+        model.eval()
+    pending, dets = [], []
+    try:
+        with torch.no_grad():
+            for points, img_metas in batches:
+                x = model.extract_feat(points, img_metas)
+                pending.append(model.neck_with_head.get_bboxes(*x, img_metas, defer=True))
+                if len(pending) >= max(int(in_flight), 1):
+                    dets.extend(pending.pop(0)())
+            while pending:
+                dets.extend(pending.pop(0)())
+            assert len(dets) == len(gt_annos), f'{len(dets)} scenes of detections for {len(gt_annos)} scenes of ground truth'
+            # a deferred batch builds its results on a read-back stream of its device: everything enqueued there must be done
+            # before the matching reads the results on the current stream (one wait per device, at the end of the set)
+            for dev in {d[1].device for d in dets if d[1].is_cuda}:
+                torch.cuda.synchronize(dev)
+            return indoor_eval_device(gt_annos, dets, tuple(metric), label2cat, scene_ids=scene_ids, group=group)
+    finally:
+        if any(m.training != t for m, t in modes):
+            for m, t in modes:
+                m.training = t
+            stale = getattr(model, '_stale_images', None)     # what the detector's own train() does besides the flags
+            if stale is not None:
+                stale()

@@ -35,9 +35,10 @@ extern "C" {
  * (fc_merge_sorted_segments / fc_merge_sorted_segments_ws_bytes added: test-time augmentation), -> 9 (fc_norm_act_maxpool8_fwd / fc_maxpool8_norm_act_bwd / fc_inverse_rows / fc_norm_act_add_fwd /
  * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates), -> 10 (fc_conv_fwd_route /
  * fc_conv_wgrad_route added: the launch a convolution call becomes, as data), -> 11 (fc_bn_train_fwd_route / fc_bn_train_bwd_route
- * added: the launches a normalisation call becomes, as data).  A caller built against another
+ * added: the launches a normalisation call becomes, as data), -> 12 (fc_eval_match / fc_eval_match_ws_bytes added: the matching
+ * of indoor_eval on the device).  A caller built against another
  * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 11
+#define FC_ABI_VERSION 12
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -603,6 +604,32 @@ int fc_merge_sorted_segments(const int64_t* desc, int nseg_out, int K, const int
                              const int64_t* ord, int ord_stride, const float* scores, int score_stride, const float* boxes,
                              int flags, int max_total, int cap, float* out_boxes, float* out_scores, int* out_src,
                              int* out_count, int stride_out, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+/* ---- evaluation: detection-to-ground-truth matching (fcaf3d_amd/csrc_post/eval.hip) ----------------------------------- */
+
+/* `flags` of fc_eval_match: the detection boxes are the bottom-centre tensor of DepthInstance3DBoxes (what get_bboxes returns);
+ * z += dz * 0.5 first, the gravity centre indoor_eval takes its IoU on. */
+#define FC_EVAL_DET_BOTTOM 1
+/* The matching of eval_det_cls (mmdet3d/core/evaluation/indoor_eval.py:86-146) for every scene and class of a set in one call.
+ * det_boxes (n_det, det_dim) with det_dim 6 (yaw 0) or 7, det_scores (n_det) finite fp32, det_labels (n_det) int64; gt_boxes
+ * (n_gt, 7) gravity centre, gt_labels (n_gt) int32; seg (n_scenes, 4) int64 (device) per scene: det_start, det_count, gt_start,
+ * gt_count — the caller checks that the ranges lie inside [0, n_det) / [0, n_gt) and do not overlap; thr: n_thr <= 8 IoU
+ * thresholds, fp64, on the device.  Per detection d of a scene, with label c:
+ *   best_gt[d]  = index WITHIN THE SCENE's ground-truth range of the first maximum, in scene order, of the 3D IoU over the
+ *                 scene's boxes of class c (the strict '>' scan of :131-136); -1 when the scene has no box of class c
+ *   best_iou[d] = that IoU (rotated BEV overlap x height overlap / clamped 3D union, the fp32 value of nms.boxes_iou3d_gpu);
+ *                 -inf when the scene has no box of class c
+ *   tp_bits[d]  bit t: (double)best_iou > thr[t] and d is, among the scene's detections with the same best_gt that pass the same
+ *                 test, the one with the highest score (equal scores: the lowest position in the scene) — the detection the
+ *                 reference's walk in descending confidence reaches first (:138-146).
+ * Detections outside every range get (-inf, -1, 0).  Any det_count / gt_count, zero included.  The winner is an unsigned 64-bit
+ * minimum per (ground-truth box, threshold) in the workspace: deterministic.  n_det == 0 launches nothing. */
+int64_t fc_eval_match_ws_bytes(int64_t n_det, int64_t n_gt, int n_thr);
+int fc_eval_match(const float* det_boxes, int det_dim /* 6 or 7 */, const float* det_scores, const int64_t* det_labels,
+                  const float* gt_boxes /* (n_gt,7) gravity centre */, const int* gt_labels,
+                  const int64_t* seg /* (n_scenes,4): det_start, det_count, gt_start, gt_count */, int n_scenes,
+                  int64_t n_det, int64_t n_gt, const double* thr /* device, n_thr <= 8 */, int n_thr, int flags,
+                  float* best_iou, int* best_gt, unsigned char* tp_bits, void* ws, int64_t ws_bytes, hipStream_t stream);
 
 /* ---- optimizer (the reference's recipe, configs/fcaf3d/fcaf3d.py:30-31) --------------------------------- */
 
