@@ -7,6 +7,7 @@ __version__ = '0.1.0'
 from .registry import (BACKBONES, BBOX_ASSIGNERS, DETECTORS, HEADS, LOSSES, Config, build_assigner,  # noqa: F401
                        build_backbone, build_detector, build_head, build_loss, build_model)
 from . import losses  # noqa: F401,E402
+from .losses import DIoU3DLoss, GIoU3DLoss, diou_3d, giou_3d  # noqa: F401,E402
 from .me_resnet import MEResNet3D  # noqa: F401,E402
 from .fcaf3d_neck_with_head import Fcaf3DAssigner, Fcaf3DNeckWithHead, compute_centerness  # noqa: F401,E402
 from .single_stage_sparse import SingleStageSparse3DDetector  # noqa: F401,E402

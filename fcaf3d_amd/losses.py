@@ -1,5 +1,7 @@
 """Loss modules of the FCAF3D head with the reference's registry names and call signatures:
   * IoU3DLoss(with_yaw, reduction, loss_weight)              — mmdet3d/models/losses/iou3d_loss.py:38-75
+  * GIoU3DLoss / DIoU3DLoss(with_yaw, reduction, loss_weight)  — iou3d_loss.py:77-81 over rotated_iou/oriented_iou_loss.py:112-152
+    (cal_giou_3d, cal_diou_3d; the reference registers the first and ships only the functions of the second); csrc_post/eiou.hip
   * FocalLoss(use_sigmoid, gamma, alpha, reduction, loss_weight)   — mmdet FocalLoss over mmcv's
     sigmoid_focal_loss op (defaults at fcaf3d_neck_with_head.py:29-34)
   * CrossEntropyLoss(use_sigmoid=True, ...)                   — mmdet (fcaf3d_neck_with_head.py:24-27)
@@ -188,6 +190,103 @@ class IoU3DLoss(nn.Module):
             # reference's early-out `if not torch.any(weight > 0): return pred.sum() * weight.sum()`
             loss = torch.where(weight > 0, loss, torch.zeros_like(loss))
         return self.loss_weight * _reduce(loss, weight, reduction, avg_factor)
+
+
+EIOU_KINDS = ('FC_EIOU_GIOU', 'FC_EIOU_DIOU')
+
+
+class _EnclosingIoUFn(torch.autograd.Function):
+    """per-row enclosing-box loss and IoU of (n,7) or (n,6) boxes (csrc_post/eiou.hip): the forward pass computes d loss / d pred
+    beside the value, the backward pass scales it"""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, kind):
+        if not pred.is_cuda:
+            raise RuntimeError('the enclosing-box 3D IoU losses run on the GPU only (HIP)')
+        pred = pred.contiguous()
+        target = target.contiguous()
+        weight = weight.to(torch.float32).contiguous() if weight is not None else None
+        n, box_dim = pred.shape
+        loss = torch.empty(n, dtype=torch.float32, device=pred.device)
+        iou = torch.empty(n, dtype=torch.float32, device=pred.device)
+        dpred = torch.empty((n, box_dim), dtype=torch.float32, device=pred.device)
+        L.call('fc_eiou3d_fwd_bwd', L.ptr(pred), L.ptr(target), target.shape[1], L.ptr(weight), n, box_dim,
+               L.header_enums()[kind], L.ptr(loss), L.ptr(iou), L.ptr(dpred), L.stream())
+        ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(iou)
+        return loss, iou
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dpred, = ctx.saved_tensors
+        # as _RotatedIoUFn / _AlignedIoUFn: a row that does not reach the loss (g == 0) gives an exact zero whatever its derivative holds
+        g = g[:, None]
+        return torch.where(g != 0, g * dpred, torch.zeros_like(dpred)), None, None, None
+
+
+def _enclosing_iou_3d(pred, target, weight, kind, return_iou):
+    assert pred.dim() == 2 and pred.shape[1] in (6, 7), f'boxes of 6 (axis-aligned) or 7 (with yaw) columns, got {tuple(pred.shape)}'
+    assert target.dim() == 2 and target.shape[0] == pred.shape[0] and target.shape[1] >= pred.shape[1], \
+        f'target {tuple(target.shape)} does not match pred {tuple(pred.shape)}'
+    assert weight is None or weight.shape == pred.shape[:1], 'one weight per row'
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError('the enclosing-box 3D IoU losses take float32 boxes')
+    loss, iou = _EnclosingIoUFn.apply(pred, target, weight, kind)
+    return (loss, iou) if return_iou else loss
+
+
+def giou_3d(pred, target, weight=None, return_iou=False):
+    """per-row 3D GIoU loss 1 - IoU + (V_c - U) / V_c of (n,7) boxes [cx,cy,cz,w,l,h,yaw] — cal_giou_3d,
+    rotated_iou/oriented_iou_loss.py:112-130 with the smallest enclosing rectangle of min_enclosing_box.py:142-172 — or of (n,6)
+    axis-aligned boxes (targets (n,>=6)) — iou3d_calculator.py:290-319, mode='giou'.  Rows whose `weight` is <= 0 are skipped by the
+    kernel: loss, IoU and gradient are exactly zero there.  return_iou: -> (loss, iou)."""
+    return _enclosing_iou_3d(pred, target, weight, EIOU_KINDS[0], return_iou)
+
+
+def diou_3d(pred, target, weight=None, return_iou=False):
+    """per-row 3D DIoU loss 1 - IoU + d^2 / c^2 (d: centre distance, c: diagonal of the enclosing box) — cal_diou_3d,
+    rotated_iou/oriented_iou_loss.py:132-152; (n,6) boxes: the axis-aligned enclosing box, c^2 clamped at 1e-6.  Otherwise as giou_3d."""
+    return _enclosing_iou_3d(pred, target, weight, EIOU_KINDS[1], return_iou)
+
+
+class _EnclosingIoU3DLoss(nn.Module):
+    """loss_weight * Σ w·loss / avg_factor with the contract of IoU3DLoss.forward.  `with_yaw` is this project's extension (the
+    reference's GIoU3DLoss takes 7 columns only) and must match the head's box width.  In the head a yaw-less config with one of
+    these losses takes the three-module path: the fused head loss is for IoU3DLoss."""
+    _fn = None
+
+    def __init__(self, with_yaw=True, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.with_yaw, self.reduction, self.loss_weight = with_yaw, reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override or self.reduction
+        want = 7 if self.with_yaw else 6
+        assert pred.dim() == 2 and pred.shape[1] == want, \
+            f'{type(self).__name__}(with_yaw={self.with_yaw}) takes boxes of {want} columns, got {tuple(pred.shape)}: with_yaw must match the head'
+        if weight is not None and weight.dim() > 1:
+            weight = weight.mean(-1)
+        if pred.shape[0] == 0:
+            return pred.sum() * 0.0
+        loss = type(self)._fn(pred, target, weight)
+        if weight is not None:
+            # the kernel has written exact zeros (value and gradient) for the rows without weight; the `where` keeps a weight
+            # that is not a number from reaching the sum
+            loss = torch.where(weight > 0, loss, torch.zeros_like(loss))
+        return self.loss_weight * _reduce(loss, weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class GIoU3DLoss(_EnclosingIoU3DLoss):
+    """iou3d_loss.py:77-81 (giou_3d_loss over cal_giou_3d)"""
+    _fn = staticmethod(giou_3d)
+
+
+@LOSSES.register_module()
+class DIoU3DLoss(_EnclosingIoU3DLoss):
+    """the DIoU counterpart over cal_diou_3d (oriented_iou_loss.py:132-152); not registered by the reference"""
+    _fn = staticmethod(diou_3d)
 
 
 class _FusedHeadLossFn(torch.autograd.Function):

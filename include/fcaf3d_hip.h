@@ -36,9 +36,9 @@ extern "C" {
  * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates), -> 10 (fc_conv_fwd_route /
  * fc_conv_wgrad_route added: the launch a convolution call becomes, as data), -> 11 (fc_bn_train_fwd_route / fc_bn_train_bwd_route
  * added: the launches a normalisation call becomes, as data), -> 12 (fc_eval_match / fc_eval_match_ws_bytes added: the matching
- * of indoor_eval on the device).  A caller built against another
- * version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 12
+ * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss).  A caller built
+ * against another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
+#define FC_ABI_VERSION 13
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -527,6 +527,19 @@ int fc_fcaf3d_loss_bwd(const float* points, const float* bbox_pred, const float*
  * weight (nullable): rows with weight <= 0 are skipped (iou = 0, dpred = 0). */
 int fc_riou3d_fwd_bwd(const float* pred, const float* target, const float* weight, int64_t n, float* iou, float* dpred,
                       hipStream_t stream);
+
+/* `kind` of fc_eiou3d_fwd_bwd */
+enum { FC_EIOU_GIOU = 0, FC_EIOU_DIOU = 1 };
+/* The enclosing-box losses and their gradient w.r.t. pred, fused — oriented_iou_loss.py:112-152 (cal_giou_3d, cal_diou_3d),
+ * min_enclosing_box.py:142-172 (smallest_bounding_box), iou3d_calculator.py:290-319 (axis-aligned giou; the aligned DIoU has no
+ * reference function: cal_diou_3d(enclosing_type='aligned') at yaw 0).  box_dim 7: rows [cx,cy,cz,w,l,h,yaw]; box_dim 6: axis-aligned
+ * rows; target rows are target_stride >= box_dim floats apart.  Outputs: loss (n), iou (n), dpred (n, box_dim) = d loss[i] / d pred[i].
+ * weight (nullable): a row with !(weight[i] > 0) gets loss = iou = 0 and a zero dpred row, and its boxes are not read (they may
+ * hold NaN or inf).  The extent along a candidate line uses the line's unit direction instead of the reference's slope
+ * (DESIGN.md section 16).  Pairs whose enclosing box has no extent give NaN / inf as in the reference.  n == 0: FC_OK, nothing
+ * launched; n < 0, another box_dim or kind: FC_EINVAL. */
+int fc_eiou3d_fwd_bwd(const float* pred, const float* target, int target_stride, const float* weight, int64_t n, int box_dim,
+                      int kind, float* loss, float* iou, float* dpred, hipStream_t stream);
 
 /* Epilogue of Fcaf3DNeckWithHead.forward_single (fcaf3d_neck_with_head.py:256-279) on the output y (n, ld <= 64) of the
  * fused 1x1 head GEMM, columns [centerness | reg (n_reg = 6 or 8) | cls (n_cls) | padding]:

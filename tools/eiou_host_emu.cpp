@@ -1,0 +1,77 @@
+// Host emulation of the kernel of fcaf3d_amd/csrc_post/eiou.hip: one std::thread per GPU thread of a workgroup, a std::barrier for
+// __syncthreads, a barrier-backed stand-in for the wave ballot (every thread of the workgroup reaches each ballot, as in the kernel),
+// workgroups one after the other, the grid fc_eiou3d_fwd_bwd launches.  tests/test_eiou_cpu.py cuts the kernel's text (eiou.hip from
+// its EIOU_* constants to the end of its anonymous namespace: constants, grid helper, geometry, kernel — nothing is restated here)
+// into kernels.inc and builds this file with clang++ -std=c++20 -fsanitize=address,undefined: the listing of the active rows, the
+// coalesced zero pass, every index and every bound are checked without a GPU, and the arithmetic against the float64 fixture (the
+// host's sinf / cosf are not the device's to the bit).  Every buffer has exactly the size the C ABI asks for; the outputs start as a
+// NaN pattern so that a word the kernel does not write shows.
+//
+//   eiou_host_emu IN OUT      IN: int64[5] n box_dim target_stride kind has_weight, then pred f32 (n, box_dim), target f32
+//                             (n, target_stride), weight f32 (n) if has_weight
+//                             OUT: loss f32 (n), iou f32 (n), dpred f32 (n, box_dim)
+#include <barrier>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+#define __device__
+#define __global__
+#define __shared__ static
+#define __restrict__
+#define __launch_bounds__(x)
+#include "fcaf3d_hip.h"  // FC_EIOU_GIOU, FC_EIOU_DIOU
+struct D3 { unsigned x, y, z; };
+static thread_local D3 threadIdx;
+static D3 blockIdx, gridDim;
+static std::barrier<>* g_bar;
+static void __syncthreads() { g_bar->arrive_and_wait(); }
+static unsigned char g_vote[1024];
+static unsigned long long __ballot(bool p) {
+  g_vote[threadIdx.x] = p;
+  g_bar->arrive_and_wait();
+  unsigned long long m = 0;
+  for (unsigned l = 0; l < 64; ++l) m |= (unsigned long long)g_vote[(threadIdx.x & ~63u) + l] << l;
+  g_bar->arrive_and_wait();
+  return m;
+}
+static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+#pragma clang fp contract(off)
+#include "kernels.inc"
+static_assert(EIOU_THREADS <= 1024, "g_vote");
+
+template <class F> static void launch(unsigned gx, F f) {
+  gridDim = {gx, 1, 1};
+  for (unsigned bx = 0; bx < gx; ++bx) {
+    blockIdx = {bx, 0, 0};
+    std::barrier<> bar(EIOU_THREADS);
+    g_bar = &bar;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < EIOU_THREADS; ++t) th.emplace_back([&, t] { threadIdx = {t, 0, 0}; f(); });
+    for (auto& x : th) x.join();
+  }
+}
+template <class T> static std::vector<T> rd(FILE* f, size_t n) { std::vector<T> v(n); if (n && fread(v.data(), sizeof(T), n, f) != n) abort(); return v; }
+
+int main(int argc, char** argv) {
+  if (argc != 3) return 2;
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  auto h = rd<int64_t>(f, 5);
+  const int64_t n = h[0], bd = h[1], ts = h[2], kind = h[3], has_w = h[4];
+  if (n < 1 || (bd != 6 && bd != 7) || ts < bd) return 2;
+  auto pred = rd<float>(f, n * bd); auto target = rd<float>(f, n * ts);
+  auto weight = rd<float>(f, has_w ? n : 0);
+  fclose(f);
+  const float* w = has_w ? weight.data() : nullptr;
+  std::vector<float> loss(n, NAN), iou(n, NAN), dpred(n * bd, NAN);
+  if (bd == 7) launch(eiou_blocks(n), [&] { k_eiou3d<7>(pred.data(), target.data(), (int)ts, w, n, (int)kind, loss.data(), iou.data(), dpred.data()); });
+  else launch(eiou_blocks(n), [&] { k_eiou3d<6>(pred.data(), target.data(), (int)ts, w, n, (int)kind, loss.data(), iou.data(), dpred.data()); });
+  FILE* o = fopen(argv[2], "wb");
+  fwrite(loss.data(), 4, n, o); fwrite(iou.data(), 4, n, o); fwrite(dpred.data(), 4, n * bd, o);
+  fclose(o);
+  return 0;
+}
