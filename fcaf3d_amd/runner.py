@@ -14,6 +14,7 @@ torch.optim.AdamW + clip_grad_norm_, the calls the reference makes.
 """
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -111,25 +112,44 @@ def build_optimizer(model, cfg, flat=None):
 
 
 class StepLrUpdater:
-    """mmcv StepLrUpdaterHook with by_epoch=True: lr = base_lr * gamma ** (number of `step` entries <= epoch)."""
+    """mmcv StepLrUpdaterHook with by_epoch=True: lr = base_lr * gamma ** (number of `step` entries <= epoch).
+    warmup='linear' (mmcv LrUpdaterHook, warmup_by_epoch=False): before iteration `it` < warmup_iters (global, counted from 0) the
+    rate is regular_lr * (1 - (1 - it / warmup_iters) * (1 - warmup_ratio)); from warmup_iters on, the epoch's regular rate.  The
+    caller hands the iteration over with `set_iter` before every step (runner.fit does)."""
 
-    def __init__(self, optimizer, step, gamma=0.1, min_lr=None, warmup=None, **_ignored):
-        assert warmup is None, 'the FCAF3D configs train without warm-up'
+    def __init__(self, optimizer, step, gamma=0.1, min_lr=None, warmup=None, warmup_iters=0, warmup_ratio=0.1, warmup_by_epoch=False,
+                 **_ignored):
+        if warmup not in (None, 'linear'):
+            raise KeyError(f"lr warmup {warmup!r} is not implemented (None or 'linear')")
+        assert not warmup_by_epoch, 'warm-up is counted in iterations'
+        if warmup is not None:
+            assert warmup_iters > 0 and 0 < warmup_ratio <= 1.0
+        self.warmup, self.warmup_iters, self.warmup_ratio = warmup, int(warmup_iters), float(warmup_ratio)
         self.optimizer = optimizer
         self.steps = [step] if isinstance(step, int) else sorted(step)
         self.gamma, self.min_lr = gamma, min_lr
         self.base_lrs = [g['lr'] for g in optimizer.param_groups]
         self.epoch = 0
 
-    def lr_at(self, base_lr, epoch):
+    def lr_at(self, base_lr, epoch, it=None):
         exp = sum(1 for s in self.steps if epoch >= s)
         lr = base_lr * self.gamma ** exp
-        return max(lr, self.min_lr) if self.min_lr is not None else lr
+        lr = max(lr, self.min_lr) if self.min_lr is not None else lr
+        if self.warmup is not None and it is not None and it < self.warmup_iters:
+            lr = lr * (1 - (1 - it / self.warmup_iters) * (1 - self.warmup_ratio))
+        return lr
 
     def set_epoch(self, epoch):
         self.epoch = epoch
         for g, base in zip(self.optimizer.param_groups, self.base_lrs):
             g['lr'] = self.lr_at(base, epoch)
+
+    def set_iter(self, it):
+        """before global iteration `it`: the warm-up rate while it lasts (mmcv before_train_iter); a no-op without warm-up"""
+        if self.warmup is None or it > self.warmup_iters:
+            return
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g['lr'] = self.lr_at(base, self.epoch, it)
 
     def epoch_end(self):
         self.set_epoch(self.epoch + 1)
@@ -382,3 +402,151 @@ def evaluate(model, batches, gt_annos, metric=(0.25, 0.5), label2cat=None, in_fl
             stale = getattr(model, '_stale_images', None)     # what the detector's own train() does besides the flags
             if stale is not None:
                 stale()
+
+
+# ---- the EpochBasedRunner recipe of the configs ---------------------------------------------------------------------------------------------
+def _rank():
+    return torch.distributed.get_rank() if D.is_dist() else 0
+
+
+class _Log:
+    """mmcv's TextLoggerHook JSON lines: the losses and the gradient norm are summed ON THE DEVICE step by step and read back once per
+    `interval` steps (one copy: the host never waits for a step it has just enqueued, so the run-ahead bound keeps working)."""
+
+    def __init__(self, path, interval):
+        self.path, self.interval = path, max(int(interval), 1)
+        self.records, self.acc, self.keys, self.n, self.t_step, self.t_data = [], None, None, 0, 0.0, 0.0
+
+    def add(self, loss, losses, grad_norm, t_step, t_data):
+        items = [(k, v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.dim() == 0] + [('loss', loss.detach())]
+        if grad_norm is not None:
+            items.append(('grad_norm', grad_norm.detach() if torch.is_tensor(grad_norm) else torch.as_tensor(float(grad_norm))))
+        keys, vals = [k for k, _ in items], [v.to(loss.device) for _, v in items]
+        row = torch.stack([v.float().reshape(()) for v in vals])
+        self.acc = row if self.acc is None else self.acc + row
+        self.keys, self.n, self.t_step, self.t_data = keys, self.n + 1, self.t_step + t_step, self.t_data + t_data
+
+    def flush(self, mode, epoch, it, lr):
+        if not self.n:
+            return None
+        vals = (self.acc / self.n).tolist()              # the interval's ONE read-back
+        rec = dict(mode=mode, epoch=epoch, iter=it, lr=lr)
+        rec.update({k: float(v) for k, v in zip(self.keys, vals)})
+        rec.update(time=self.t_step / self.n, data_time=self.t_data / self.n)
+        self.acc, self.n, self.t_step, self.t_data = None, 0, 0.0, 0.0
+        return self.write(rec)
+
+    def write(self, rec):
+        import json
+        self.records.append(rec)
+        if self.path is not None:
+            with open(self.path, 'a') as f:
+                f.write(json.dumps(rec) + '\n')
+        return rec
+
+
+def _save(model, tr, work_dir, epoch, it, seed, cfg_ck):
+    """mmcv CheckpointHook: epoch_{n}.pth (meta: epoch, iter, seed; optimizer state), latest.pth, and at most max_keep_ckpts files"""
+    import shutil
+    from .checkpoint import save_checkpoint
+    path = os.path.join(work_dir, f'epoch_{epoch}.pth')
+    save_checkpoint(model, path, optimizer=tr.optimizer, meta=dict(epoch=epoch, iter=it, seed=seed))
+    shutil.copyfile(path, os.path.join(work_dir, 'latest.pth'))
+    keep, interval = cfg_ck.get('max_keep_ckpts', -1), max(int(cfg_ck.get('interval', 1)), 1)
+    if keep and keep > 0:
+        for e in range(epoch - keep * interval, 0, -interval):
+            old = os.path.join(work_dir, f'epoch_{e}.pth')
+            if not os.path.exists(old):
+                break
+            os.remove(old)
+    return path
+
+
+def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=None, seed=0, device=None, max_gb=64.0, on_batch=None,
+        step=None):
+    """What the reference's tools/train.py does through mmdet3d/apis/train.py train_model: mmcv's EpochBasedRunner with its
+    optimizer, LR, checkpoint, evaluation and text-logger hooks, for `cfg.runner.max_epochs` epochs.
+
+      epoch e:  lr.set_epoch(e) -> every batch of the loader through TrainStep(batch, next_batch) -> epoch_end()
+      checkpoint_config  dict(interval=1, max_keep_ckpts=-1): work_dir/epoch_{n}.pth + latest.pth, older files removed
+      evaluation         dict(interval=n): runner.evaluate over the validation loader (fixed draws per scene), logged as mode 'val'
+      log_config         dict(interval=n): one JSON line per n steps in work_dir/<time>.log.json (mode, epoch, iter, lr, losses,
+                         grad_norm, time, data_time), read back from the device once per line
+      resume_from        a checkpoint written here: model, optimizer, epoch and iteration continue where it stopped; the batches of
+                         the remaining epochs are the straight run's (data.DeviceLoader draws by (seed, epoch, index))
+
+    train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`).  Under
+    torch.distributed every rank calls fit: the loaders shard, rank 0 alone writes files, evaluate gathers over the group.
+    on_batch(epoch, iteration, batch): called before every step (tests, progress bars).  step: a TrainStep to reuse (default:
+    TrainStep.from_config(model, cfg)).  Returns the log records (dicts, train and val, in order)."""
+    import time
+    from . import data as DT
+    rank, world = _rank(), D.world_size()
+    if device is None:
+        device = next(model.parameters()).device
+    if train_loader is None:
+        ds = DT.build_dataset(cfg.data.train)
+        train_loader = DT.DeviceLoader(DT.ResidentScenes(ds, device, max_gb), ds.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
+    ev = cfg.get('evaluation') or {}
+    ev_interval = int(ev.get('interval', 0) or 0)
+    if val_loader is None and ev_interval > 0 and cfg.get('data', {}).get('val') is not None:
+        vs = DT.build_dataset(cfg.data.val)
+        val_loader = DT.DeviceLoader(DT.ResidentScenes(vs, device, max_gb), vs.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
+    if world > 1:
+        for t in list(model.parameters()) + list(model.buffers()):
+            torch.distributed.broadcast(t.data, 0)            # every rank starts from rank 0's weights, as DDP's constructor does
+    tr = step if step is not None else TrainStep.from_config(model, cfg)
+    if world > 1 and step is not None:
+        tr.invalidate_images()                                # the broadcast wrote the weights through .data behind an existing TrainStep
+    start_epoch, it = 0, 0
+    if resume_from is not None:
+        from .checkpoint import load_checkpoint
+        ck = load_checkpoint(model, resume_from, map_location=device, strict=True)
+        start_epoch, it = int(ck['meta']['epoch']), int(ck['meta']['iter'])
+        tr.load_state_dict(dict(optimizer=ck['optimizer'], epoch=start_epoch))
+    log_path = None
+    if rank == 0:
+        os.makedirs(work_dir, exist_ok=True)
+        log_path = os.path.join(work_dir, time.strftime('%Y%m%d_%H%M%S') + '.log.json')
+    log = _Log(log_path, (cfg.get('log_config') or {}).get('interval', 50))
+    ck_cfg = cfg.get('checkpoint_config') or {}
+    max_epochs = int(cfg.runner['max_epochs'])
+    model.train()
+    for epoch in range(start_epoch, max_epochs):
+        if tr.lr is not None:
+            tr.lr.set_epoch(epoch)
+        train_loader.set_epoch(epoch)
+        t_data0 = time.perf_counter()
+        batches = train_loader.batches(epoch)
+        t_data = (time.perf_counter() - t_data0) / max(len(batches), 1)
+        for k, batch in enumerate(batches):
+            if tr.lr is not None:
+                tr.lr.set_iter(it)
+            if on_batch is not None:
+                on_batch(epoch, it, batch)
+            t0 = time.perf_counter()
+            loss, losses = tr(batch, batches[k + 1] if k + 1 < len(batches) else None)
+            it += 1
+            log.add(loss, losses, tr.last_grad_norm, time.perf_counter() - t0, t_data)
+            if (k + 1) % log.interval == 0:
+                log.flush('train', epoch + 1, k + 1, tr.optimizer.param_groups[0]['lr'])
+        log.flush('train', epoch + 1, len(batches), tr.optimizer.param_groups[0]['lr'])
+        tr.epoch_end()
+        if rank == 0 and ck_cfg.get('interval', 1) > 0 and (epoch + 1) % int(ck_cfg.get('interval', 1)) == 0:
+            _save(model, tr, work_dir, epoch + 1, it, seed, ck_cfg)
+        if val_loader is not None and ev_interval > 0 and (epoch + 1) % ev_interval == 0:
+            res = validate(model, val_loader, metric=tuple(ev.get('iou_thr', (0.25, 0.5))))
+            res = {k: float(v) if isinstance(v, (int, float, np.generic)) else v for k, v in res.items()}
+            log.write(dict(mode='val', epoch=epoch + 1, iter=len(batches), lr=tr.optimizer.param_groups[0]['lr'], **res))
+    return log.records
+
+
+def validate(model, val_loader, metric=(0.25, 0.5), label2cat=None):
+    """runner.evaluate over a validation data.DeviceLoader: this rank's scenes (rank r: [r::world_size]), the ranks' tables gathered"""
+    rs = val_loader.resident
+    idx = val_loader.indices(0)
+    annos = rs.dataset.gt_annos() if hasattr(rs.dataset, 'gt_annos') else None
+    assert annos is not None, 'validation needs a plain dataset (ScanNetDataset / SUNRGBDDataset / S3DISDataset)'
+    group = torch.distributed.group.WORLD if D.world_size() > 1 else None
+    return evaluate(model, ((b['points'], b['img_metas']) for b in val_loader.batches(0)), [annos[int(i)] for i in idx], metric=metric,
+                    label2cat=label2cat, scene_ids=[int(i) for i in idx], group=group)

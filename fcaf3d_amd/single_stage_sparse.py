@@ -45,6 +45,11 @@ class SingleStageSparse3DDetector(nn.Module):
         coords = torch.empty((total, 4), dtype=torch.int32, device=dev)
         feats = torch.empty((total, nfeat), dtype=torch.float32, device=dev)
         off = 0
+        if hasattr(points, 'voxelize_batch'):
+            # a batch that collates itself (data.DeviceBatch): every scene sampled, augmented and voxelised from the resident arena
+            # in ONE launch (fc_batch_augment_voxelize)
+            points.voxelize_batch(self.voxel_size, 255.0, coords, feats)
+            points = ()                                    # nothing is left for the per-scene loop
         for b, p in enumerate(points):
             n = p.shape[0]
             if hasattr(p, 'voxelize_into'):

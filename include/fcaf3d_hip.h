@@ -36,9 +36,10 @@ extern "C" {
  * fc_bn_train_add_fwd added: the stem's tail and the neck's sparse sums without their intermediates), -> 10 (fc_conv_fwd_route /
  * fc_conv_wgrad_route added: the launch a convolution call becomes, as data), -> 11 (fc_bn_train_fwd_route / fc_bn_train_bwd_route
  * added: the launches a normalisation call becomes, as data), -> 12 (fc_eval_match / fc_eval_match_ws_bytes added: the matching
- * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss).  A caller built
- * against another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 13
+ * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss), -> 14
+ * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch).  A caller built against
+ * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
+#define FC_ABI_VERSION 14
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -61,6 +62,24 @@ int fc_voxelize(const float* points, int64_t n, int pt_stride, int batch_idx, fl
 int fc_augment_voxelize(const float* points, int64_t n_src, int pt_stride, const int* sample_idx, int64_t n_out,
                         const float* xform_host, int batch_idx, float voxel_size, float feat_div, int nfeat, int* coords,
                         float* feats, float* points_out, hipStream_t stream);
+
+/* The same train pipeline for ALL B scenes of a batch in one launch, with the sampling drawn in the kernel: IndoorPointSample
+ * (mmdet3d/datasets/pipelines/transforms_3d.py:821-895), GlobalAlignment (:409-490), RandomFlip3D (:59-170), GlobalRotScaleTrans
+ * (:493-645) and the collate of extract_feat (mmdet3d/models/detectors/single_stage_sparse.py:34-36), from a resident arena of raw points
+ * (arena_rows, pt_stride) fp32 that holds many scenes back to back.  desc: DEVICE table of B <= 256 scenes, FC_BATCH_DESC_WORDS
+ * int64 words each: [0] first arena row, [1] n_src, [2] n_out, [3] first output row, [4] 64-bit sample seed, [5] first entry in
+ * sample_idx, [6..17] the 24 floats of fc_augment_voxelize's xform_host.  Scene s writes rows [out_off, out_off + n_out) of
+ * coords (batch index s) / feats / sample_out / points_out (each out_rows rows; rows outside every scene's range are not
+ * touched).  Row j of a scene reads source row perm_seed(j), a keyed bijection of [0, n_src) (four-round Feistel network with
+ * cycle walking: n_out distinct rows), or with n_src < n_out a keyed hash of j reduced to [0, n_src) (with replacement), or —
+ * sample_idx != NULL (n_idx ints) — sample_idx[idx_off + j]; csrc_post/batch.hip states the integer arithmetic.  The arithmetic
+ * behind the gather is fc_augment_voxelize's: coords / feats are bit-equal to B calls of it with the same rows.  total_out =
+ * the sum of n_out as the HOST knows it (sizes the grid; 0, or B == 0: nothing is launched).  sample_out (nullable): the rows
+ * chosen; points_out (nullable): the augmented cloud.  A descriptor whose ranges leave the arrays writes nothing. */
+#define FC_BATCH_DESC_WORDS 18
+int fc_batch_augment_voxelize(const float* arena, int64_t arena_rows, int pt_stride, const int64_t* desc, int B, int64_t total_out,
+                              int64_t out_rows, const int* sample_idx, int64_t n_idx, float voxel_size, float feat_div, int nfeat,
+                              int* coords, float* feats, int* sample_out, float* points_out, hipStream_t stream);
 
 /* Z-order key per voxel coordinate [b | x,y,z bit-interleaved]; sorting the collated points by it before
  * fc_hash_unique turns "order of first occurrence" into a space-filling-curve order on every pyramid level.
