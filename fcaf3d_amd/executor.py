@@ -32,15 +32,12 @@ import torch
 from . import _lib as L
 from . import functional as Fn
 from . import nn as MEnn
+from .weight_images import ImageSet
 
 ENABLED = os.environ.get('FC_EXEC', '1') != '0'
 # bench.py's live roofline measurement: a list -> every step bound while it is set has its convolution operators bracketed by
 # HIP events inside fc_exec (csrc/exec.hip, cfg[2]) and appends {pairs per kernel map (device scalars), operators per direction}
 PROBE = None
-# TrainStep (runner.py) sets this to the program whose weight images it has just rebuilt, for the duration of its step: only then
-# (or for a detector that declares `static_weights` in eval mode) does a forward pass trust the images of the previous call.  Anyone
-# else who steps the weights (an optimizer of their own, EMA, surgery) gets fresh images at every call, as on the per-operator path.
-TRUSTED = None
 # tests: keep the bound state of the last forward pass on the detector (`det._last_exec = (program, state)`) so that the recorded
 # activations can be inspected (NetProgram.decisions).  A program built while it is set also stores the stem's normalised output,
 # which a plain step never materialises (r7): part of the program cache key
@@ -221,21 +218,10 @@ class NetProgram:
         if holder is None or holder.sig != self._sig:
             holder = self.det.__dict__['_exec_weights'] = _Weights(self.det, self.dev, self._sig)
         self.w = holder
-        self.packed, self.gent_w, self.gents, self.images, self.ncol = holder.packed, holder.gent_w, holder.gents, holder.images, holder.ncol
-
-    @property
-    def weights_fresh(self):
-        return self.w.fresh
-
-    @weights_fresh.setter
-    def weights_fresh(self, v):
-        self.w.fresh = v
-
-    def refresh_weights(self):
-        self.w.refresh()
+        self.packed, self.gent_w, self.gents, self.ncol = holder.packed, holder.gent_w, holder.gents, holder.ncol
 
     def IMG(self, w, transposed):
-        v = self.w.img_of[w.data_ptr()]
+        v = self.w.images.table.get((w.data_ptr(), 1 if w.dim() == 2 else w.shape[0], w.shape[-2], w.shape[-1]))
         assert v is not None and v[1 if transposed else 0] is not None, 'no split-bf16 image for this kernel shape'
         return self.S(v[1 if transposed else 0])
 
@@ -417,12 +403,9 @@ class NetProgram:
 
     def forward(self, st):
         """-> (cent_all, bbox_all, cls_all, cmax_all) for all head locations (levels finest first), autograd-connected in training"""
-        trusted = (TRUSTED is not None and TRUSTED.w is self.w) or (not self.training and getattr(self.det, 'static_weights', False))
-        if not (self.weights_fresh and trusted):
-            self.refresh_weights()
-        ev = self.images.event
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)     # images may have been built on another stream (runner: after the optimizer step)
+        # the previous call's images are believed only under runner.TrainStep's lease or, in eval mode, a detector's `static_weights`
+        self.w.ensure(trusted=ImageSet.held is self.w or (not self.training and getattr(self.det, 'static_weights', False)))
+        self.w.wait()                                      # they may have been built on another stream (runner: after the optimizer step)
         if self.training:
             return _NetFn.apply(self._anchor, self, st)
         return self._forward(st)
@@ -996,10 +979,10 @@ class _Emitter:
             p.patch(Bk[0], bytes=self.AMAX_SLOT_BYTES * (self.amax_used - n_fwd_slots))
 
 
-class _Weights:
-    """the executor's view of a detector's weights: pre-split images of every convolution kernel (functional.WeightImages), the
+class _Weights(ImageSet):
+    """the executor's view of a detector's weights: pre-split images of every convolution kernel (weight_images.ImageSet), the
     three 1x1 head kernels packed side by side (zero-padded to 64 columns), the generative transposed convolutions' kernels in
-    their GEMM form (Cin, 8 Cout) — persistent buffers, rebuilt by `refresh` (5-6 launches on the current stream)"""
+    their GEMM form (Cin, 8 Cout) — persistent buffers, rebuilt with the images (5-6 launches on the current stream)"""
 
     def __init__(self, det, dev, sig):
         nh = det.neck_with_head
@@ -1012,21 +995,17 @@ class _Weights:
         self.packed = torch.zeros((1, C, 64), dtype=torch.float32, device=dev)       # [centerness | reg | cls | 0...]
         self.gent_w = [torch.empty((1, m.in_channels, 8 * m.out_channels), dtype=torch.float32, device=dev) for m in self.gents]
         ws = [m.kernel for m in convs] + [self.packed] + self.gent_w
-        self.images = Fn.WeightImages(ws)
-        self.img_of = {}
-        for w in ws:
-            K = 1 if w.dim() == 2 else w.shape[0]
-            self.img_of[w.data_ptr()] = self.images.table.get((w.data_ptr(), K, w.shape[-2], w.shape[-1]))
-        self.fresh = False
+        super().__init__([m.kernel for m in convs + list(head) + self.gents], weights=ws)
+
+    def lookup(self, weight, transposed):
+        return None                 # programs read these images natively; a per-operator convolution of such a step builds its own
 
     @torch.no_grad()
-    def refresh(self):
+    def prepare(self):
         nh = self.det.neck_with_head
         torch.cat((nh.centerness_conv.kernel, nh.reg_conv.kernel, nh.cls_conv.kernel), dim=1, out=self.packed[0][:, :self.ncol])
         for m, w in zip(self.gents, self.gent_w):
             w.view(m.in_channels, 8, m.out_channels).copy_(m.kernel.permute(1, 0, 2))
-        self.images.build()
-        self.fresh = True
 
 
 class _NetFn(torch.autograd.Function):
@@ -1057,15 +1036,12 @@ def program_for(det, training, tail0=False):
     keep = bool(KEEP_STATE)                    # the recorder flips it at run time: a program built without the stem's normalised output
                                                # must never be handed to `decisions`
     fuse = bool(Fn.BN_FUSE)                    # changes the emitted program (statistics tables, producer words): part of the cache key
-    # ... and so does the operand split (r6): the three-product route's program carries amax slots, hint words and clear operators,
-    # and the weight images are mode-dependent
+    # ... and so does the operand split (r6): the three-product route's program carries amax slots, hint words and clear operators
+    # (the weight images, shared by the programs, carry the mode in their own key)
     mode = Fn.split_mode() if Fn.X6 else -1
     cache = det.__dict__.setdefault('_programs', {})
     sig = NetProgram.signature(det)
     prog = cache.get(key + (fuse, mode, keep))
     if prog is None or prog._sig != sig:
         prog = cache[key + (fuse, mode, keep)] = NetProgram(det, *key, keep_state=keep)
-    if getattr(prog.w, 'split_mode', mode) != mode:      # the shared images were built in the other mode
-        prog.w.fresh = False
-    prog.w.split_mode = mode
     return prog

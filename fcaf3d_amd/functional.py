@@ -5,6 +5,7 @@ import os
 import torch
 
 from . import _lib as L
+from .weight_images import ImageSet, WeightImages  # noqa: F401  (WeightImages: its home; importable from here as before)
 
 # bits of the convolution `flags` word: the one Python mirror of include/fcaf3d_hip.h FC_CONV_* (tests/test_cabi.py compares them)
 CONV_FMA = 1 << 0                        # the generic FMA kernels (parity cross-check)
@@ -131,14 +132,14 @@ def split_mode():
 
 
 def set_split_mode(mode):
-    """switch the operand split (0 / 2).  Weight images are mode-dependent: whoever holds prebuilt ones (runner.TrainStep:
-    `invalidate_images()`, an executor program: `weights_fresh = False`) must rebuild them before the next pass; the per-call images of
-    the module path follow by themselves."""
+    """switch the operand split (0 / 2).  Weight images are mode-dependent: the mode is part of the key a `weight_images.ImageSet`
+    was built under, so prebuilt ones are rebuilt before the next pass; the per-call images of the module path follow by themselves."""
     L.call('fc_set_split_mode', int(mode))
 
 
 def set_bf16_fast(on):
-    """the flagged NON-PARITY bf16 fast mode (csrc/conv.hip fc_set_bf16_fast); it reads six-product images: rebuild prebuilt ones"""
+    """the flagged NON-PARITY bf16 fast mode (csrc/conv.hip fc_set_bf16_fast); it reads six-product images: `split_mode()` reads 0
+    while it is on, so the key of a `weight_images.ImageSet` built in the other mode no longer matches"""
     L.call('fc_set_bf16_fast', 1 if on else 0)
 
 
@@ -147,24 +148,15 @@ def _x6_image(weight, transposed):
     for the backward-data launch on the same kernel (transposed=True: reduction Cout, columns Cin).  Built at every call:
     a cache across calls would have to know when the weights changed, and torch's fused optimizers update parameters
     without touching their version counters (measured: torch.optim.AdamW(fused=True) leaves `_version` at 0).  A training
-    loop that owns the optimizer step can hand over images it built itself for exactly one step (`PREBUILT`)."""
+    loop that owns the optimizer step hands over its own for one step: the set whose `ImageSet.lease()` is held is asked first."""
+    pre = ImageSet.held.lookup(weight, transposed) if ImageSet.held is not None else None
+    if pre is not None:
+        return pre
     K, Cin, Cout = weight.shape
-    if PREBUILT:
-        pre = PREBUILT.get((weight.data_ptr(), K, Cin, Cout))
-        if pre is not None and pre[transposed] is not None:
-            global PREBUILT_EVENT
-            if PREBUILT_EVENT is not None:         # first consumer of the step: the images were built on another stream
-                torch.cuda.current_stream().wait_event(PREBUILT_EVENT)
-                PREBUILT_EVENT = None
-            return pre[transposed]
     R, C = (Cout, Cin) if transposed else (Cin, Cout)
     img = torch.empty(L.query('fc_x6_weight_image_bytes', K, R, C), dtype=torch.uint8, device=weight.device)
     L.call('fc_x6_weight_image', L.ptr(weight), L.ptr(img), K, R, C, 1 if transposed else 0, L.stream())
     return img
-
-
-PREBUILT = {}          # (data_ptr, K, Cin, Cout) of a kernel -> (forward image, backward-data image): WeightImages.table, set by the
-PREBUILT_EVENT = None   # training loop for the duration of one step; the event the first consumer waits for
 
 
 def _stats_table(n_out, K, Cin, Cout, flags, pairs, device):
@@ -613,60 +605,3 @@ class _HeadSplit(torch.autograd.Function):
 
 def head_split(y, bias, scale, n_reg, n_cls):
     return _HeadSplit.apply(y, bias, scale, n_reg, n_cls)
-
-
-class WeightImages:
-    """Pre-split images (csrc/conv_x6.h) of every convolution kernel of a model, forward and backward-data, built by ONE
-    launch — for a training loop that knows when the weights change (runner.TrainStep builds them right after the optimizer
-    step, on the weight-gradient stream, and hands them to the next step through `PREBUILT`).  Kernels that reach
-    `sparse_conv` as a fresh tensor (the transposed convolution's permuted copy) are not covered and build their own."""
-
-    def __init__(self, weights):
-        ents, off = [], 0
-        self.table = {}
-        dev = None
-        for w in weights:
-            if w.dim() == 2:                       # 1 x 1 convolution: (Cin, Cout), used as (1, Cin, Cout)
-                K, (Cin, Cout) = 1, w.shape
-            else:
-                K, Cin, Cout = w.shape
-            dev = w.device
-            pair = [None, None]
-            for tr, (R, C) in ((0, (Cin, Cout)), (1, (Cout, Cin))):
-                if R % 32 or C % 64 or not w.is_contiguous():
-                    continue
-                nbytes = L.query('fc_x6_weight_image_bytes', K, R, C)
-                pair[tr] = (off, nbytes, K, R, C)
-                off += (nbytes + 255) // 256 * 256
-            if pair[0] or pair[1]:
-                ents.append((w, pair))
-        self.n = 0
-        if not ents:
-            return
-        self.buf = torch.empty(off, dtype=torch.uint8, device=dev)
-        desc, blk = [], 0
-        for w, pair in ents:
-            views = []
-            for tr in (0, 1):
-                if pair[tr] is None:
-                    views.append(None)
-                    continue
-                o, nb, K, R, C = pair[tr]
-                v = self.buf[o:o + nb]
-                views.append(v)
-                # word 7 (h3 split): a backward-data image shares the amax slot of its forward image (the same weights): no second pass
-                desc += [w.data_ptr(), v.data_ptr(), K, R, C, tr, blk, views[0].data_ptr() if (tr == 1 and views[0] is not None) else 0]
-                blk += K * (R // 32) * (C // 64)
-            K = 1 if w.dim() == 2 else w.shape[0]
-            self.table[(w.data_ptr(), K, w.shape[-2], w.shape[-1])] = tuple(views)
-        self.n = len(desc) // 8
-        self.blocks = blk
-        self.desc = torch.tensor(desc, dtype=torch.int64).to(dev)
-        self.event = None
-
-    def build(self):
-        """enqueue the build on the CURRENT stream; records the event consumers on other streams wait for"""
-        if self.n:
-            L.call('fc_x6_weight_images', L.ptr(self.desc), self.n, self.blocks, L.stream())
-            self.event = torch.cuda.Event()
-            self.event.record()

@@ -12,14 +12,19 @@ LR hook's per-epoch update.  On the GPU the parameters, gradients and AdamW mome
 and clip + AdamW are three launches of csrc/optim.hip (`FlatAdamW`); CPU parameters (the host-logic tests) take
 torch.optim.AdamW + clip_grad_norm_, the calls the reference makes.
 """
+import contextlib
 import os
+import time
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import dist as D
+from . import executor
+from . import functional as Fn
 from .flat import FlatParams
+from .weight_images import ImageSet
 
 
 class FlatAdamW:
@@ -188,7 +193,6 @@ def reserve_device_memory(gigabytes, device=None, streams=None, chunk_gb=8):
     a quarter of what is free)."""
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     if streams is None:
-        from . import functional as Fn
         from . import sparse as SP
         streams = [(torch.cuda.current_stream(dev), 0.5), (SP.map_stream(dev), 0.25), (Fn.wgrad_stream(dev), 0.25)]
     free, _ = torch.cuda.mem_get_info(dev)
@@ -228,21 +232,17 @@ class TrainStep:
         self.lr = build_lr_updater(self.optimizer, lr_config) if lr_config else None
         self.averager = D.GradientAverager(self.params, bucket_mb=bucket_mb, flat=self.flat)
         self.last_grad_norm = None
-        # host seconds per phase, accumulated over the calls: [run-ahead bound + prefetch submit, forward_train enqueue, backward enqueue,
+        # host seconds per phase, accumulated over the calls: [run-ahead bound + prefetch submit + zero_grad, forward_train enqueue, backward enqueue,
         # averager + clip + AdamW + weight images] (bench.py config.host.phases_ms: which phase grows when the host is slow)
         self.phase_s = [0.0, 0.0, 0.0, 0.0]
-        # split-bf16 convolutions read pre-split weight images: with the flat optimizer this loop is the only writer of the
-        # weights, so it builds all of them in one launch right after its step (on the weight-gradient stream, under the
-        # next step's voxelisation and stem) instead of ~100 per-layer launches on the critical path of the next step.
-        # Whoever else writes the parameters (load_state_dict, ...) does so through torch and moves their version counters
-        # (the flat optimizer writes through raw pointers and does not); then the images are rebuilt before use.
-        from . import functional as Fn
+        # split-bf16 convolutions read pre-split weight images (weight_images.ImageSet): with the flat optimizer this loop is the only
+        # writer of the weights, so it builds them all in one launch right after its step (weight-gradient stream, under the next step's
+        # voxelisation and stem) instead of ~100 per-layer launches there, and leases them to its own pass.  This set serves the module path.
         self.images = None
         if self.flat is not None and Fn.X6:
             from .nn import MinkowskiConvolution
-            ws = [m.kernel for m in model.modules() if isinstance(m, MinkowskiConvolution) and m.kernel.requires_grad]
-            self.images = Fn.WeightImages(ws)
-            self._image_ws, self.images_version = ws, None
+            self.images = ImageSet(m.kernel for m in model.modules() if isinstance(m, MinkowskiConvolution) and m.kernel.requires_grad)
+        self._step_events = []
 
     @classmethod
     def from_config(cls, model, cfg, **kw):
@@ -253,98 +253,71 @@ class TrainStep:
         `dist.broadcast(p.data)`, EMA / weight surgery through `.data`): the next step rebuilds the pre-split weight images
         (the module path's and the native executor's) before it uses them.  Writes through torch ops on the parameters
         themselves (load_state_dict, `with no_grad(): p.copy_()`) are detected by the version counters."""
-        for pr in getattr(self.model, '_programs', {}).values():
-            pr.weights_fresh = False
-        self.images_version = None
-
-    def _build_images(self, side_stream):
-        from . import functional as Fn
-        if side_stream:
-            side, main = Fn.wgrad_stream(self.flat.data.device), torch.cuda.current_stream()
-            side.wait_stream(main)                   # the optimizer step (and every reader of the old images) is enqueued on main
-            with torch.cuda.stream(side):
-                self.images.build()
-        else:
-            self.images.build()
-        self.images_version = sum(w._version for w in self._image_ws)
-
-    def _program(self):
-        """the model's native-executor program for a training step, if this step will go through it (executor.py)"""
-        from . import executor
-        if self.flat is None or not hasattr(self.model, 'backbone') or not self.model.training:
-            return None
-        return executor.program_for(self.model, True)
+        for s in (self.images, getattr(self.model, '_exec_weights', None)):
+            if s is not None:
+                s.invalidate()
 
     def __call__(self, batch, next_batch=None):
         """next_batch: the batch of the FOLLOWING call, if the caller has it (a data loader's prefetched item): its coordinate
         phase starts now on a worker thread (SingleStageSparse3DDetector.prefetch) and overlaps this step"""
-        from . import functional as Fn
-        import time
-        ph = self.phase_s
         t0 = time.perf_counter()
-        self._bound_run_ahead()
-        if next_batch is not None and hasattr(self.model, 'prefetch'):
-            self.model.prefetch(next_batch['points'], gt=True)
+        images = self.open(next_batch)
         t1 = time.perf_counter()
-        ph[0] += t1 - t0
-        self.optimizer.zero_grad(set_to_none=True)
-        Fn._flat_pass_done()                         # a backward pass that raised never ran its final callback: start clean
-        prog = self._program()
-        if prog is not None:
-            # the executor reads its own weight images (incl. the packed head kernel and the generative kernels' GEMM form); they
-            # are refreshed right after the optimizer step below, or here if something else has written the weights since
-            ver = sum(w._version for w in self._image_ws) if self.images is not None else None
-            if not prog.weights_fresh or getattr(self, '_prog_version', None) != ver:
-                prog.refresh_weights()
-                self._prog_version = ver
-        elif self.images is not None and self.images.n:
-            if self.images_version != sum(w._version for w in self._image_ws):      # first step, or somebody wrote the weights through torch
-                self._build_images(side_stream=False)
-            Fn.PREBUILT, Fn.PREBUILT_EVENT = self.images.table, self.images.event
-        from . import executor
-        executor.TRUSTED = prog                      # this step's images were rebuilt after the last write of the weights
-        try:
+        with self.passing(images):
             losses = self.model(return_loss=True, **batch)
             loss = parse_losses(losses)
             t2 = time.perf_counter()
-            ph[1] += t2 - t1
             loss.backward()
             t3 = time.perf_counter()
-            ph[2] += t3 - t2
-        finally:
-            Fn.PREBUILT, Fn.PREBUILT_EVENT = {}, None
-            executor.TRUSTED = None
         self.averager.finish()
-        if isinstance(self.optimizer, FlatAdamW):
-            # after finish() under data parallelism every gradient already sits (averaged) in the flat buffer
-            self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets))
-            for pr in getattr(self.model, '_programs', {}).values():
-                pr.weights_fresh = False
-            if prog is not None:
-                side, main = Fn.wgrad_stream(self.flat.data.device), torch.cuda.current_stream()
-                side.wait_stream(main)                   # the optimizer step (and every reader of the old images) is enqueued on main
-                with torch.cuda.stream(side):
-                    prog.refresh_weights()
-                self.images_version = None               # the module path's images are stale now; rebuilt if a step takes that path
-            elif self.images is not None and self.images.n:
-                self._build_images(side_stream=True)
-            ph[3] += time.perf_counter() - t3
-            return loss, losses
-        if self.max_norm is not None:
-            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.params, self.max_norm, norm_type=self.norm_type)
-        self.optimizer.step()
+        self.close(images)
+        for k, dt in enumerate((t1 - t0, t2 - t1, t3 - t2, time.perf_counter() - t3)):
+            self.phase_s[k] += dt
         return loss, losses
+
+    def open(self, next_batch=None):      # open / passing / close: the pieces of a step (tools/hostprof.py puts its marks between them)
+        """before the pass: bound the run-ahead, start the next batch's coordinate phase, drop the gradients -> the image set this
+        step runs under: the executor's if it will go through a program (executor.py), else this loop's own (or None)"""
+        self._bound_run_ahead()
+        if next_batch is not None and hasattr(self.model, 'prefetch'):
+            self.model.prefetch(next_batch['points'], gt=True)
+        self.optimizer.zero_grad(set_to_none=True)
+        Fn._flat_pass_done()                         # a backward pass that raised never ran its final callback: start clean
+        if self.flat is not None and hasattr(self.model, 'backbone') and self.model.training:
+            prog = executor.program_for(self.model, True)
+            if prog is not None:
+                return prog.w
+        return self.images
+
+    @contextlib.contextmanager
+    def passing(self, images):
+        """the forward + backward pass runs inside, under the lease of this step's images (rebuilt first unless they are current)"""
+        with images.lease() if images is not None else contextlib.nullcontext():
+            if images is not None:
+                images.ensure(trusted=True)
+            yield
+
+    def close(self, images):
+        """after the pass and the averager: clip + optimizer step, then the images of the stepped weights (weight-gradient stream)"""
+        if isinstance(self.optimizer, FlatAdamW):    # (after finish() under data parallelism the averaged gradients sit in the flat buffer)
+            self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets))
+        else:
+            if self.max_norm is not None:
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.params, self.max_norm, norm_type=self.norm_type)
+            self.optimizer.step()
+        self.invalidate_images()                     # the step wrote through raw pointers (torch's fused ones too): no version counter moved
+        if images is not None:
+            images.rebuild_after_step(torch.cuda.current_stream(), Fn.wgrad_stream(self.flat.data.device))
 
     def _bound_run_ahead(self, depth=int(os.environ.get('FC_RUN_AHEAD', '2'))):
         """the host may enqueue at most `depth` steps ahead of the GPU: with the coordinate phase off the main thread nothing else
         in a step waits for the device, and every step in flight holds its arenas"""
         if not self.params or not self.params[0].is_cuda:
             return
-        evs = self.__dict__.setdefault('_step_events', [])
+        evs = self._step_events
         if len(evs) >= depth:
             e0 = evs.pop(0)
             if not e0.query():
-                import time
                 t0 = time.perf_counter()
                 e0.synchronize()
                 L.HOST_WAIT[0] += time.perf_counter() - t0
@@ -399,9 +372,7 @@ def evaluate(model, batches, gt_annos, metric=(0.25, 0.5), label2cat=None, in_fl
         if any(m.training != t for m, t in modes):
             for m, t in modes:
                 m.training = t
-            stale = getattr(model, '_stale_images', None)     # what the detector's own train() does besides the flags
-            if stale is not None:
-                stale()
+            model.invalidate_images()                          # what the detector's own train() does besides the flags
 
 
 # ---- the EpochBasedRunner recipe of the configs ---------------------------------------------------------------------------------------------
@@ -479,7 +450,6 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     torch.distributed every rank calls fit: the loaders shard, rank 0 alone writes files, evaluate gathers over the group.
     on_batch(epoch, iteration, batch): called before every step (tests, progress bars).  step: a TrainStep to reuse (default:
     TrainStep.from_config(model, cfg)).  Returns the log records (dicts, train and val, in order)."""
-    import time
     from . import data as DT
     rank, world = _rank(), D.world_size()
     if device is None:

@@ -222,16 +222,17 @@ class SingleStageSparse3DDetector(nn.Module):
     # across calls instead of rebuilding them at every forward pass.  Switching train() / eval(), load_state_dict and .to() drop them.
     static_weights = False
 
-    def _stale_images(self):
-        for pr in self.__dict__.get('_programs', {}).values():
-            pr.weights_fresh = False
+    def invalidate_images(self):
+        """the executor's weight images (one set per detector, weight_images.ImageSet) are rebuilt before their next use"""
+        if '_exec_weights' in self.__dict__:
+            self._exec_weights.invalidate()
 
     def train(self, mode=True):
-        self._stale_images()
+        self.invalidate_images()
         return super().train(mode)
 
     def load_state_dict(self, *a, **kw):
-        self._stale_images()
+        self.invalidate_images()
         return super().load_state_dict(*a, **kw)
 
     def _apply(self, fn, *a, **kw):

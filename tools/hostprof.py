@@ -34,7 +34,6 @@ def pop_flag(name, default):
 
 def run_one(args, B, dev, do_cprofile, steps=8):
     import fcaf3d_amd._lib as L
-    import fcaf3d_amd.executor as EX
     import fcaf3d_amd.functional as Fn
     from fcaf3d_amd.runner import TrainStep, parse_losses
     args.batch = B
@@ -61,40 +60,18 @@ def run_one(args, B, dev, do_cprofile, steps=8):
                     torch.cuda.synchronize()
                 marks.append(time.perf_counter())
         mark()
-        tr._bound_run_ahead()
-        if LOOKAHEAD:
-            model.prefetch(batches[(i + 1) % 2]['points'], gt=True)
-        tr.optimizer.zero_grad(set_to_none=True)
-        prog = tr._program()
-        if prog is not None:
-            if not prog.weights_fresh:
-                prog.refresh_weights()
-        elif tr.images is not None and tr.images.n:
-            if tr.images_version != sum(w._version for w in tr._image_ws):
-                tr._build_images(side_stream=False)
-            Fn.PREBUILT, Fn.PREBUILT_EVENT = tr.images.table, tr.images.event
-        EX.TRUSTED = prog
-        x = model.extract_feat(b['points'], b['img_metas'], (b['gt_bboxes_3d'], b['gt_labels_3d']))
-        x = [list(v) for v in x]
-        mark()
-        losses = model.neck_with_head.loss(*x, b['gt_bboxes_3d'], b['gt_labels_3d'], b['img_metas'])
-        loss = parse_losses(losses)
-        mark()
-        loss.backward()
-        Fn.PREBUILT, Fn.PREBUILT_EVENT = {}, None
-        EX.TRUSTED = None
+        images = tr.open(batches[(i + 1) % 2] if LOOKAHEAD else None)
+        with tr.passing(images):
+            x = model.extract_feat(b['points'], b['img_metas'], (b['gt_bboxes_3d'], b['gt_labels_3d']))
+            x = [list(v) for v in x]
+            mark()
+            losses = model.neck_with_head.loss(*x, b['gt_bboxes_3d'], b['gt_labels_3d'], b['img_metas'])
+            loss = parse_losses(losses)
+            mark()
+            loss.backward()
         tr.averager.finish()
         mark()
-        tr.optimizer.step(tr.max_norm)
-        for pr in getattr(model, '_programs', {}).values():
-            pr.weights_fresh = False
-        if prog is not None:
-            side, main = Fn.wgrad_stream(dev), torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                prog.refresh_weights()
-        elif tr.images is not None and tr.images.n:
-            tr._build_images(side_stream=True)
+        tr.close(images)
         mark()
 
     names = ['forward (extract_feat)', 'loss', 'backward', 'clip + AdamW + images']
