@@ -11,6 +11,9 @@
 //
 // Replaces MinkowskiEngine's ConvolutionForward/Backward (and ConvolutionTranspose, 1x1 mm) called
 // from me_resnet.py:19-21,56-62, BasicBlock, fcaf3d_neck_with_head.py:52,60-69,83-85,257-263.
+//
+// This file: the process switches, the amax pass, the fixed-order sums, launch_conv / launch_wgrad and the entry points.  The kernels:
+// conv_f32.h / wgrad_f32.h (fp32), conv_stem.h, conv_x6.h / wgrad_x6.h / conv_h3r.h (split operands); what they share: conv_tile.h.
 #include "fc_common.h"
 #include "../../include/fcaf3d_hip.h"
 #ifdef FC_TRACE
@@ -75,6 +78,10 @@ extern "C" int fc_debug_set_h3r(int mode) {
 }
 
 #include <mutex>
+#include "conv_tile.h"
+#include "conv_f32.h"
+#include "wgrad_f32.h"
+#include "conv_stem.h"
 #include "conv_x6.h"
 #include "wgrad_x6.h"
 #include "conv_h3r.h"
@@ -172,717 +179,6 @@ extern "C" int fc_conv_amax_hint(const unsigned* amax_in, const unsigned* amax_g
   t_amax_hint[0] = amax_in;
   t_amax_hint[1] = amax_gout;
   return FC_OK;
-}
-
-#define BK 32            // reduction slab (input channels per stage / rows per stage for wgrad)
-#define LDA (BK + 4)     // A row stride in floats: 16B-aligned rows, conflict-free ds_read_b128 (9r mod 16)
-
-// ------------------------------------------------------------------------------------------------
-// Pipeline per workgroup: (1) which kernel offsets have any neighbour among the tile's rows (offsets without one are
-// skipped outright), OR-reduced over the tile's rows; (2) walk the surviving (offset,
-// Cin-slab) stages with the NEXT stage's gathers + weight loads issued into registers before the current stage's MFMAs
-// run (single LDS buffer, global-load latency hidden behind the matrix pipe).
-// gridDim.z > 1 = split over kernel offsets (offset k handled by split k % gridDim.z) for layers whose
-// row count cannot fill the chip; partial tiles go to `out` + z*n_out*Cout and are summed by k_sum_parts.
-// WM = waves along the rows (2: 2 x 2 waves; 4: 4 x 1 — the 256 x 64 tile for 64-wide outputs: every wave still owns a
-// 64 x 64 quadrant, i.e. the operand re-use of the 128 x 128 tile, where a 128 x 64 tile halves it).
-// WT: the weights are given TRANSPOSED, W[k] as (Cout, Cin) row-major — the backward-data pass reads the layer's own
-// (K, Cin, Cout) kernel as the (Cout -> Cin) operator it needs, no per-step transpose launch.  Only the staging differs:
-// a thread loads 4 reduction-consecutive floats of one output column and stores them as 4 ds_write_b32 (conflict-free:
-// consecutive lanes = consecutive columns); the LDS image, the fragment reads and the results are the same.
-template <int BM, int BN, int BKT, bool HAS_NBR, int WM = 2, bool WT = false>
-__global__ __launch_bounds__(256, (BM == 128 && BN == 128 && BKT == 32) ? 4 : (WM == 4 ? 3 : 2)) void k_conv_mfma(const float* __restrict__ in, const float* __restrict__ W,
-                                                   const int* __restrict__ nbr,
-                                                   const int* __restrict__ out_index, const int* __restrict__ cnt,
-                                                   float* __restrict__ out, int64_t n_out, int K, int Cin, int Cout) {
-  constexpr int WN = 4 / WM;
-  constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);      // 32x32 MFMA tiles per wave
-  constexpr int RW = BM / WM, CW = BN / WN;      // rows / columns of a wave's part of the tile
-  constexpr int LDAT = BKT + 4;                  // (BKT+4)/4 odd -> conflict-free ds_read_b128 of the A fragments
-  constexpr int A4 = BKT / 4;                    // float4 per gathered row slab
-  constexpr int APASS = 256 / A4;                // rows staged per pass
-  constexpr int AR = BM / APASS;                 // float4 gathers per thread per stage
-  constexpr int BR = BKT * BN / 1024;            // float4 weight loads per thread per stage
-  __shared__ __attribute__((aligned(16))) float As[BM * LDAT];
-  __shared__ __attribute__((aligned(16))) float Bs[BKT * BN];
-  __shared__ unsigned int kmask_s;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = WM == 4 ? wave : wave >> 1, wc = WM == 4 ? 0 : wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  int64_t bx = blockIdx.x;
-  const int n0 = blockIdx.y * BN;
-  int S = gridDim.z, z = blockIdx.z;
-  TR_DECL;
-  TR(0);
-  int tr_units = 0;
-  (void)tr_units;
-  if (cnt) {
-    // pair mode (fc_conv_fwd_pairs): `nbr` row z lists the input rows of offset z's cnt[z] pairs and the tile computes
-    // those compacted rows only: T_z[j] = in[pair_in[z][j]] @ W[z], written to slab z of the workspace.  From here on
-    // it is a one-offset convolution over cnt[z] rows.  Two grid shapes: (row tiles, column tiles, K) with the workgroups
-    // beyond cnt[z] exiting at once, or — gridDim.z == 1, the caller knows sum_k ceil(cnt[k] / BM) — a LINEAR list of the
-    // live tiles only, offset-major (r2: the dead workgroups of the 3-D grid skew the round-robin placement, a few
-    // shader engines overflow and their last workgroups start a whole round late: 115 -> 88 us on the 3.5k-row level).
-    if (gridDim.z == 1 && K > 1) {
-      int k = 0;
-      for (; k < K - 1; ++k) {
-        const int64_t t = ((int64_t)cnt[k] + BM - 1) / BM;
-        if (bx < t) break;
-        bx -= t;
-      }
-      z = k;
-    }
-    const int64_t stride = n_out;
-    n_out = cnt[z];
-    if (bx * BM >= n_out) return;
-    nbr += (int64_t)z * stride;
-    W += (int64_t)z * Cin * Cout;
-    out += (int64_t)z * stride * Cout;
-    K = 1; S = 1; z = 0;
-  }
-  const int64_t m0 = bx * BM;
-  const int a_c4 = tid % A4, a_r = tid / A4;     // A staging: A4 float4 per row, APASS rows per pass
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // ---- (1) which of this split's offsets have a neighbour anywhere in the tile ---------------------
-  unsigned int kmask;
-  {
-    if (tid == 0) kmask_s = 0u;
-    __syncthreads();
-    if (tid < BM) {
-      unsigned int mk = 0u;
-      int64_t row = m0 + tid;
-      if (row < n_out) {
-        if (HAS_NBR) {
-          for (int k = z; k < K; k += S)
-            if (nbr[(int64_t)k * n_out + row] >= 0) mk |= 1u << k;
-        } else {
-          mk = 1u;
-        }
-      }
-      // wave-level OR, one LDS atomic per wave
-      for (int off = 32; off > 0; off >>= 1) mk |= __shfl_xor(mk, off, 64);
-      if (lane == 0 && mk) atomicOr(&kmask_s, mk);
-    }
-    __syncthreads();
-    kmask = kmask_s;
-  }
-  TR(1);
-
-  // ---- (2) software-pipelined stage loop -------------------------------------------------------------
-  if (kmask) {
-    int k = __ffs(kmask) - 1;
-    kmask &= kmask - 1;
-    int c0 = 0;
-    f32x4 av[AR], bv[BR];
-    // Prefetch of one stage, written branch-free so that the compiler issues it as batches (the AR neighbour
-    // indices, the weights, then the AR gathers) instead of AR serialised index->wait->gather chains with the data
-    // waited for on the spot (r1 ISA reading).  An absent neighbour gathers from a row of zeros (pointer select
-    // BEFORE the load), so nothing touches the loaded registers until the next stage's LDS store.
-    auto load_stage = [&](int kk, int cc) {
-      const float* Wk = W + (int64_t)kk * Cin * Cout;
-      int v[AR];
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        int64_t row = m0 + a_r + APASS * i;
-        int64_t rc = row < n_out ? row : n_out - 1;
-        int t = HAS_NBR ? nbr[(int64_t)kk * n_out + rc] : (int)rc;    // compile-time: no null test between the loads
-        v[i] = row < n_out ? t : -1;
-      }
-#pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        int lin = tid + 256 * i;
-        if (WT) {
-          bv[i] = *reinterpret_cast<const f32x4*>(Wk + (int64_t)(n0 + lin % BN) * Cin + cc + (lin / BN) * 4);
-        } else {
-          int kr = lin / (BN / 4), c4 = lin % (BN / 4);
-          bv[i] = *reinterpret_cast<const f32x4*>(Wk + (int64_t)(cc + kr) * Cout + n0 + c4 * 4);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const float* src = v[i] < 0 ? g_zero_row + a_c4 * 4 : in + (int64_t)v[i] * Cin + cc + a_c4 * 4;
-        av[i] = *reinterpret_cast<const f32x4*>(src);
-      }
-    };
-    load_stage(k, c0);
-    const bool prio = g_fc_prio >= 0;             // see g_fc_prio
-    while (true) {
-#ifdef FC_TRACE
-      if (tr_units == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TR(2); }
-      tr_units += BKT / 8;
-#endif
-      __syncthreads();                           // previous stage fully consumed
-#pragma unroll
-      for (int i = 0; i < AR; ++i)
-        *reinterpret_cast<f32x4*>(&As[(a_r + APASS * i) * LDAT + a_c4 * 4]) = av[i];
-#pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        int lin = tid + 256 * i;
-        if (WT) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) Bs[((lin / BN) * 4 + e) * BN + lin % BN] = bv[i][e];
-        } else {
-          int kr = lin / (BN / 4), c4 = lin % (BN / 4);
-          *reinterpret_cast<f32x4*>(&Bs[kr * BN + c4 * 4]) = bv[i];
-        }
-      }
-      __syncthreads();
-      // issue the next stage's global loads before computing this one
-      int nk = k, nc0 = c0 + BKT;
-      if (nc0 >= Cin) {
-        nc0 = 0;
-        nk = kmask ? __ffs(kmask) - 1 : -1;
-        kmask &= kmask - 1;
-      }
-      // unconditional (the last iteration re-reads its own stage): a conditionally assigned float4 array is not
-      // promoted to registers by the compiler and lands in scratch
-      load_stage(nk >= 0 ? nk : k, nk >= 0 ? nc0 : c0);
-      if (prio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int q = 0; q < BKT / 8; ++q) {
-        f32x4 a[TM];
-        float b[TN][4];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          a[i] = *reinterpret_cast<const f32x4*>(&As[(wr * RW + i * 32 + r) * LDAT + 8 * q + 4 * h]);
-        // sub-tile j of the wave owns the INTERLEAVED columns TN*r + j of its half of the tile: one ds_read_b64 per
-        // (k, lane) instead of two ds_read_b32 (conflict-free: 32 lanes x 8 B = 64 banks), and 8-byte output stores
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (TN == 2) {
-            const f32x2 bb = *reinterpret_cast<const f32x2*>(&Bs[(8 * q + 4 * h + e) * BN + wc * CW + 2 * r]);
-            b[0][e] = bb[0];
-            b[TN - 1][e] = bb[1];
-          } else {
-            b[0][e] = Bs[(8 * q + 4 * h + e) * BN + wc * CW + r];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            float ae = a[i][e];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae, b[j][e], acc[i][j], 0, 0, 0);
-          }
-        }
-      }
-      if (prio) __builtin_amdgcn_s_setprio(0);
-      if (nk < 0) break;
-      k = nk;
-      c0 = nc0;
-    }
-  }
-  // epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-  TR(3);
-  float* dst = out + (int64_t)z * n_out * Cout + n0 + wc * CW + TN * r;
-  int orow[TM][16];                              // looked up in one batch ahead of the stores
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int64_t row = m0 + wr * RW + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      int o = -1;
-      if (row < n_out) o = out_index ? out_index[row] : (int)row;      // rows are processed in mask-sorted order
-      orow[i][e] = o;
-    }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      if (orow[i][e] >= 0) {
-        if (TN == 2) {
-          f32x2 v = {acc[i][0][e], acc[i][TN - 1][e]};
-          *reinterpret_cast<f32x2*>(dst + (int64_t)orow[i][e] * Cout) = v;
-        } else {
-          dst[(int64_t)orow[i][e] * Cout] = acc[i][0][e];
-        }
-      }
-    }
-  TR(5);
-  TR_FLUSH(tr_units);
-}
-
-// Deeper-pipelined variant of k_conv_mfma (same tiles, same LDS layout, same results) at 3 waves per SIMD (168 VGPRs):
-//  * the neighbour rows of the NEXT kernel offset are requested one offset ahead (vnxt), so that a stage's gathers are
-//    issued at once instead of behind an exposed index round trip (r2 ISA reading of k_conv_mfma: index loads ->
-//    s_waitcnt vmcnt(0) -> gathers in front of every stage's MFMA block; the 128-VGPR budget of 4 waves/SIMD had no
-//    room for the look-ahead — r1 dead end);
-//  * the MFMA fragments of 8-channel step q+1 are read from LDS while step q multiplies (double-buffered fragment
-//    registers) instead of read -> s_waitcnt lgkmcnt(0) -> multiply.
-template <int BM, int BN, int BKT, bool HAS_NBR, int WM = 2, bool WT = false>
-__global__ __launch_bounds__(256, 3) void k_conv_mfma_p(const float* __restrict__ in, const float* __restrict__ W,
-                                                   const int* __restrict__ nbr,
-                                                   const int* __restrict__ out_index, const int* __restrict__ cnt,
-                                                   float* __restrict__ out, int64_t n_out, int K, int Cin, int Cout) {
-  constexpr int WN = 4 / WM;
-  constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);      // 32x32 MFMA tiles per wave
-  constexpr int RW = BM / WM, CW = BN / WN;      // rows / columns of a wave's part of the tile
-  constexpr int LDAT = BKT + 4;                  // (BKT+4)/4 odd -> conflict-free ds_read_b128 of the A fragments
-  constexpr int A4 = BKT / 4;                    // float4 per gathered row slab
-  constexpr int APASS = 256 / A4;                // rows staged per pass
-  constexpr int AR = BM / APASS;                 // float4 gathers per thread per stage
-  constexpr int BR = BKT * BN / 1024;            // float4 weight loads per thread per stage
-  __shared__ __attribute__((aligned(16))) float As[BM * LDAT];
-  __shared__ __attribute__((aligned(16))) float Bs[BKT * BN];
-  __shared__ unsigned int kmask_s;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = WM == 4 ? wave : wave >> 1, wc = WM == 4 ? 0 : wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  int64_t bx = blockIdx.x;
-  const int n0 = blockIdx.y * BN;
-  int S = gridDim.z, z = blockIdx.z;
-  TR_DECL;
-  TR(0);
-  int tr_units = 0;
-  (void)tr_units;
-  if (cnt) {
-    // pair mode (fc_conv_fwd_pairs): `nbr` row z lists the input rows of offset z's cnt[z] pairs and the tile computes
-    // those compacted rows only: T_z[j] = in[pair_in[z][j]] @ W[z], written to slab z of the workspace.  From here on
-    // it is a one-offset convolution over cnt[z] rows.  Two grid shapes: (row tiles, column tiles, K) with the workgroups
-    // beyond cnt[z] exiting at once, or — gridDim.z == 1, the caller knows sum_k ceil(cnt[k] / BM) — a LINEAR list of the
-    // live tiles only, offset-major (r2: the dead workgroups of the 3-D grid skew the round-robin placement, a few
-    // shader engines overflow and their last workgroups start a whole round late: 115 -> 88 us on the 3.5k-row level).
-    if (gridDim.z == 1 && K > 1) {
-      int k = 0;
-      for (; k < K - 1; ++k) {
-        const int64_t t = ((int64_t)cnt[k] + BM - 1) / BM;
-        if (bx < t) break;
-        bx -= t;
-      }
-      z = k;
-    }
-    const int64_t stride = n_out;
-    n_out = cnt[z];
-    if (bx * BM >= n_out) return;
-    nbr += (int64_t)z * stride;
-    W += (int64_t)z * Cin * Cout;
-    out += (int64_t)z * stride * Cout;
-    K = 1; S = 1; z = 0;
-  }
-  const int64_t m0 = bx * BM;
-  const int a_c4 = tid % A4, a_r = tid / A4;     // A staging: A4 float4 per row, APASS rows per pass
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // ---- (1) which of this split's offsets have a neighbour anywhere in the tile ---------------------
-  unsigned int kmask;
-  {
-    if (tid == 0) kmask_s = 0u;
-    __syncthreads();
-    if (tid < BM) {
-      unsigned int mk = 0u;
-      int64_t row = m0 + tid;
-      if (row < n_out) {
-        if (HAS_NBR) {
-          for (int k = z; k < K; k += S)
-            if (nbr[(int64_t)k * n_out + row] >= 0) mk |= 1u << k;
-        } else {
-          mk = 1u;
-        }
-      }
-      // wave-level OR, one LDS atomic per wave
-      for (int off = 32; off > 0; off >>= 1) mk |= __shfl_xor(mk, off, 64);
-      if (lane == 0 && mk) atomicOr(&kmask_s, mk);
-    }
-    __syncthreads();
-    kmask = kmask_s;
-  }
-  TR(1);
-
-  // ---- (2) software-pipelined stage loop -------------------------------------------------------------
-  if (kmask) {
-    const int nst = __popc(kmask) * (Cin / BKT);         // stages of this tile
-    unsigned int rem = kmask;
-    int lk = __ffs(rem) - 1;                              // load cursor: offset / channel slab of the stage requested next
-    rem &= rem - 1;
-    int lnk = rem ? __ffs(rem) - 1 : lk;                  // ... and the offset after it (its rows are already on their way)
-    if (rem) rem &= rem - 1;
-    int lc0 = 0;
-    bool sw = false;                                      // the cursor has left lk: switch to lnk at the next request
-    f32x4 av[AR], bv[BR];
-    int vcur[AR], vnxt[AR];
-    int64_t arow[AR];
-    bool aok[AR];
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int64_t row = m0 + a_r + APASS * i;
-      aok[i] = row < n_out;
-      arow[i] = aok[i] ? row : n_out - 1;
-    }
-    // raw table entries only: nothing touches a requested index until the stage that uses it
-    auto fetch_idx = [&](int kk, int (&v)[AR]) {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) v[i] = HAS_NBR ? nbr[(int64_t)kk * n_out + arow[i]] : (int)arow[i];
-    };
-    fetch_idx(lk, vcur);
-    fetch_idx(lnk, vnxt);
-    auto load_stage = [&]() {
-      if (sw) {                                           // first slab of a new offset: its rows were requested an offset ago
-        sw = false;
-        lk = lnk;
-#pragma unroll
-        for (int i = 0; i < AR; ++i) vcur[i] = vnxt[i];
-        if (rem) {
-          lnk = __ffs(rem) - 1;
-          rem &= rem - 1;
-        }
-        fetch_idx(lnk, vnxt);
-      }
-      const float* Wk = W + (int64_t)lk * Cin * Cout;
-#pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        int lin = tid + 256 * i;
-        if (WT) {
-          bv[i] = *reinterpret_cast<const f32x4*>(Wk + (int64_t)(n0 + lin % BN) * Cin + lc0 + (lin / BN) * 4);
-        } else {
-          int kr = lin / (BN / 4), c4 = lin % (BN / 4);
-          bv[i] = *reinterpret_cast<const f32x4*>(Wk + (int64_t)(lc0 + kr) * Cout + n0 + c4 * 4);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const float* src = (vcur[i] < 0 || !aok[i]) ? g_zero_row + a_c4 * 4 : in + (int64_t)vcur[i] * Cin + lc0 + a_c4 * 4;
-        av[i] = *reinterpret_cast<const f32x4*>(src);
-      }
-    };
-    load_stage();
-    const bool prio = g_fc_prio >= 0;
-    for (int st = 0; st < nst; ++st) {
-#ifdef FC_TRACE
-      if (tr_units == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TR(2); }
-      tr_units += BKT / 8;
-#endif
-      __syncthreads();                           // previous stage fully consumed
-#pragma unroll
-      for (int i = 0; i < AR; ++i)
-        *reinterpret_cast<f32x4*>(&As[(a_r + APASS * i) * LDAT + a_c4 * 4]) = av[i];
-#pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        int lin = tid + 256 * i;
-        if (WT) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) Bs[((lin / BN) * 4 + e) * BN + lin % BN] = bv[i][e];
-        } else {
-          int kr = lin / (BN / 4), c4 = lin % (BN / 4);
-          *reinterpret_cast<f32x4*>(&Bs[kr * BN + c4 * 4]) = bv[i];
-        }
-      }
-      __syncthreads();
-      // request the next stage before multiplying this one (the last iteration re-reads its own stage: a conditionally
-      // assigned staging array lands in scratch)
-      if (st + 1 < nst) {
-        lc0 += BKT;
-        if (lc0 >= Cin) {
-          lc0 = 0;
-          sw = true;
-        }
-      }
-      load_stage();
-      f32x4 fa[2][TM];
-      float fb[2][TN][4];
-      auto read_frag = [&](int q, int u) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          fa[u][i] = *reinterpret_cast<const f32x4*>(&As[(wr * RW + i * 32 + r) * LDAT + 8 * q + 4 * h]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (TN == 2) {
-            const f32x2 bb = *reinterpret_cast<const f32x2*>(&Bs[(8 * q + 4 * h + e) * BN + wc * CW + 2 * r]);
-            fb[u][0][e] = bb[0];
-            fb[u][TN - 1][e] = bb[1];
-          } else {
-            fb[u][0][e] = Bs[(8 * q + 4 * h + e) * BN + wc * CW + r];
-          }
-        }
-      };
-      read_frag(0, 0);
-      if (prio) __builtin_amdgcn_s_setprio(1);
-      // (r2: sched_group_barrier pins that issue the LDS reads of step q+1 ahead of step q's MFMAs measured +-1 % on 50 of 58
-      // launch shapes and -10.5 % at the VGPR limit: the fragment reads are not what the loop waits for.)
-#pragma unroll
-      for (int q = 0; q < BKT / 8; ++q) {
-        if (q + 1 < BKT / 8) read_frag(q + 1, (q + 1) & 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            const float ae = fa[q & 1][i][e];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae, fb[q & 1][j][e], acc[i][j], 0, 0, 0);
-          }
-        }
-      }
-      if (prio) __builtin_amdgcn_s_setprio(0);
-    }
-  }
-  // epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-  TR(3);
-  float* dst = out + (int64_t)z * n_out * Cout + n0 + wc * CW + TN * r;
-  int orow[TM][16];                              // looked up in one batch ahead of the stores
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int64_t row = m0 + wr * RW + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      int o = -1;
-      if (row < n_out) o = out_index ? out_index[row] : (int)row;      // rows are processed in mask-sorted order
-      orow[i][e] = o;
-    }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      if (orow[i][e] >= 0) {
-        if (TN == 2) {
-          f32x2 v = {acc[i][0][e], acc[i][TN - 1][e]};
-          *reinterpret_cast<f32x2*>(dst + (int64_t)orow[i][e] * Cout) = v;
-        } else {
-          dst[(int64_t)orow[i][e] * Cout] = acc[i][0][e];
-        }
-      }
-    }
-  TR(5);
-  TR_FLUSH(tr_units);
-}
-
-// LDS-DMA variant (r2; VERDICT r1 item 1a — double-buffered LDS, one barrier per stage): the gathered rows and the weight slab go
-// from global memory STRAIGHT into LDS (`global_load_lds_dwordx4`, 1 KiB per wave instruction: 8 gathered rows x 128 B, or
-// 1 KiB of a weight slab), no staging registers and no ds_write pass, into one of TWO stage buffers; a stage is
-//     wait for my own DMAs -> barrier -> issue stage s+1's DMAs into the other buffer -> multiply stage s.
-// The DMA's LDS image is lane-linear (wave-uniform base + lane x 16 B: MI355X guide), so the A tile cannot be padded; its
-// rows are XOR-swizzled instead ON THE SOURCE SIDE: the lane that fills 16-byte slot p of row j fetches the row's slot
-// p ^ ((j >> 1) & 7), and the MFMA fragment read of slot c of row j addresses slot c ^ ((j >> 1) & 7) — conflict-free for
-// ds_read_b128's 16-lane groups.  Same tiles, prologue, epilogue, grid shapes and results as k_conv_mfma / _p.
-template <int BM, int BN, bool HAS_NBR, int WM = 2>
-__global__ __launch_bounds__(256, 2) void k_conv_glds(const float* __restrict__ in, const float* __restrict__ W,
-                                                      const int* __restrict__ nbr,
-                                                      const int* __restrict__ out_index, const int* __restrict__ cnt,
-                                                      float* __restrict__ out, int64_t n_out, int K, int Cin, int Cout) {
-  constexpr int BKT = 32;
-  constexpr int WN = 4 / WM;
-  constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
-  constexpr int RW = BM / WM, CW = BN / WN;
-  constexpr int AR = BM / 32;                    // row DMAs per thread per stage (8 rows per wave instruction)
-  constexpr int BR = BN / 32;                    // weight DMAs per thread per stage
-  constexpr int BRPI = 256 / BN;                 // weight-slab rows per wave instruction
-  constexpr int STAGE = BM * BKT + BKT * BN;     // floats per stage buffer
-  __shared__ __attribute__((aligned(1024))) float smem[2 * STAGE];         // ONE array (a second one costs vmcnt(0)s: guide §5)
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = WM == 4 ? wave : wave >> 1, wc = WM == 4 ? 0 : wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  int64_t bx = blockIdx.x;
-  const int n0 = blockIdx.y * BN;
-  int S = gridDim.z, z = blockIdx.z;
-  if (cnt) {                                     // pair mode: see k_conv_mfma_p
-    if (gridDim.z == 1 && K > 1) {
-      int k = 0;
-      for (; k < K - 1; ++k) {
-        const int64_t t = ((int64_t)cnt[k] + BM - 1) / BM;
-        if (bx < t) break;
-        bx -= t;
-      }
-      z = k;
-    }
-    const int64_t stride = n_out;
-    n_out = cnt[z];
-    if (bx * BM >= n_out) return;
-    nbr += (int64_t)z * stride;
-    W += (int64_t)z * Cin * Cout;
-    out += (int64_t)z * stride * Cout;
-    K = 1; S = 1; z = 0;
-  }
-  const int64_t m0 = bx * BM;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  unsigned int kmask;
-  {
-    // the tile-mask word lives in stage buffer 1: nothing is written there before every wave has passed stage 0's barrier
-    unsigned int* kmask_s = reinterpret_cast<unsigned int*>(&smem[STAGE]);
-    if (tid == 0) *kmask_s = 0u;
-    __syncthreads();
-    if (tid < BM) {
-      unsigned int mk = 0u;
-      int64_t row = m0 + tid;
-      if (row < n_out) {
-        if (HAS_NBR) {
-          for (int k = z; k < K; k += S)
-            if (nbr[(int64_t)k * n_out + row] >= 0) mk |= 1u << k;
-        } else {
-          mk = 1u;
-        }
-      }
-      for (int off = 32; off > 0; off >>= 1) mk |= __shfl_xor(mk, off, 64);
-      if (lane == 0 && mk) atomicOr(kmask_s, mk);
-    }
-    __syncthreads();
-    kmask = *kmask_s;
-  }
-
-  if (kmask) {
-    const int nst = __popc(kmask) * (Cin / BKT);
-    unsigned int rem = kmask;
-    int lk = __ffs(rem) - 1;
-    rem &= rem - 1;
-    int lnk = rem ? __ffs(rem) - 1 : lk;
-    if (rem) rem &= rem - 1;
-    int lc0 = 0;
-    bool sw = false;
-    // this lane's part of a row DMA: row (i*4 + wave)*8 + lane/8 of the tile, LDS slot lane%8, source slot swizzled
-    const int a_j = lane >> 3;
-    int vcur[AR], vnxt[AR], a_src4[AR];
-    int64_t arow[AR];
-    bool aok[AR];
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int lrow = (i * 4 + wave) * 8 + a_j;
-      const int64_t row = m0 + lrow;
-      aok[i] = row < n_out;
-      arow[i] = aok[i] ? row : n_out - 1;
-      a_src4[i] = (((lane & 7) ^ ((lrow >> 1) & 7))) * 4;
-    }
-    auto fetch_idx = [&](int kk, int (&v)[AR]) {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) v[i] = HAS_NBR ? nbr[(int64_t)kk * n_out + arow[i]] : (int)arow[i];
-    };
-    fetch_idx(lk, vcur);
-    fetch_idx(lnk, vnxt);
-    const int b_kr = lane / (BN / 4), b_c4 = lane % (BN / 4);
-    auto issue_stage = [&](int buf) {
-      if (sw) {
-        sw = false;
-        lk = lnk;
-#pragma unroll
-        for (int i = 0; i < AR; ++i) vcur[i] = vnxt[i];
-        if (rem) {
-          lnk = __ffs(rem) - 1;
-          rem &= rem - 1;
-        }
-        fetch_idx(lnk, vnxt);
-      }
-      float* As = smem + buf * STAGE;
-      float* Bs = As + BM * BKT;
-      const float* Wk = W + (int64_t)lk * Cin * Cout;
-      // every source address first (this consumes the index registers: hipcc waits vmcnt(0) at the first use of an ordinary
-      // load's result while a DMA is in flight — here nothing is, the loop-top wait has just drained the queue), then the
-      // DMAs back to back
-      const float* asrc[AR];
-      const float* bsrc[BR];
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const bool ok = vcur[i] >= 0 && aok[i];
-        const int64_t off = ok ? (int64_t)vcur[i] * Cin + lc0 : 0;
-        asrc[i] = (ok ? in : g_zero_row) + off + a_src4[i];
-      }
-#pragma unroll
-      for (int i = 0; i < BR; ++i) bsrc[i] = Wk + (int64_t)(lc0 + (i * 4 + wave) * BRPI + b_kr) * Cout + n0 + b_c4 * 4;
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < BR; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)bsrc[i],
-                                         (__attribute__((address_space(3))) void*)(Bs + (i * 4 + wave) * BRPI * BN), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < AR; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)asrc[i],
-                                         (__attribute__((address_space(3))) void*)(As + (i * 4 + wave) * 8 * BKT), 16, 0, 0);
-    };
-    issue_stage(0);
-    const int fsw = (r >> 1) & 7;                // the fragment rows' swizzle (tile row = 32-aligned base + r)
-    for (int st = 0; st < nst; ++st) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my DMAs of stage st have landed ...
-      __syncthreads();                                      // ... and everyone's; stage st-1 is fully consumed
-      if (st + 1 < nst) {
-        lc0 += BKT;
-        if (lc0 >= Cin) {
-          lc0 = 0;
-          sw = true;
-        }
-        issue_stage((st + 1) & 1);
-      }
-      const float* As = smem + (st & 1) * STAGE;
-      const float* Bs = As + BM * BKT;
-      f32x4 fa[2][TM];
-      float fb[2][TN][4];
-      auto read_frag = [&](int q, int u) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          fa[u][i] = *reinterpret_cast<const f32x4*>(&As[(wr * RW + i * 32 + r) * BKT + 4 * ((2 * q + h) ^ fsw)]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (TN == 2) {
-            const f32x2 bb = *reinterpret_cast<const f32x2*>(&Bs[(8 * q + 4 * h + e) * BN + wc * CW + 2 * r]);
-            fb[u][0][e] = bb[0];
-            fb[u][TN - 1][e] = bb[1];
-          } else {
-            fb[u][0][e] = Bs[(8 * q + 4 * h + e) * BN + wc * CW + r];
-          }
-        }
-      };
-      read_frag(0, 0);
-#pragma unroll
-      for (int q = 0; q < BKT / 8; ++q) {
-        if (q + 1 < BKT / 8) read_frag(q + 1, (q + 1) & 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            const float ae = fa[q & 1][i][e];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae, fb[q & 1][j][e], acc[i][j], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  float* dst = out + (int64_t)z * n_out * Cout + n0 + wc * CW + TN * r;
-  int orow[TM][16];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int64_t row = m0 + wr * RW + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      int o = -1;
-      if (row < n_out) o = out_index ? out_index[row] : (int)row;
-      orow[i][e] = o;
-    }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      if (orow[i][e] >= 0) {
-        if (TN == 2) {
-          f32x2 v = {acc[i][0][e], acc[i][TN - 1][e]};
-          *reinterpret_cast<f32x2*>(dst + (int64_t)orow[i][e] * Cout) = v;
-        } else {
-          dst[(int64_t)orow[i][e] * Cout] = acc[i][0][e];
-        }
-      }
-    }
 }
 
 // out[i] = sum_z part[z][i]   (fixed order; elems % 4 == 0)
@@ -1041,292 +337,6 @@ __global__ __launch_bounds__(256) void k_sum_pairs_stats(const float* __restrict
     }
   }
   stat_block_reduce(a1, a2, epi.stats, Cout, sm);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stem convolution (Cin = 3 colour channels -> 64, k3 s2; me_resnet.py:19-21): bound by the 148 MB output
-// write.  64 output rows per workgroup; the 27x3 gathered inputs of every row and the whole (81,64) kernel sit in
-// LDS, zero-padded to a reduction depth of 96, and each wave multiplies one 32x32 tile on the matrix cores.
-#define STEM_CIN 3
-#define STEM_COUT 64
-#define STEM_ROWS 64
-#define STEM_FWD_LDA 97
-#define STEM_COL_LD 84      // row stride of the saved gathered inputs: 27 x 3 = 81 floats, padded to 21 float4
-__global__ __launch_bounds__(256) void k_stem_fwd(const float* __restrict__ in, const float* __restrict__ W,
-                                                  const int* __restrict__ nbr, float* __restrict__ out,
-                                                  float* __restrict__ col, int64_t n_out, int K) {
-  // out[64 rows][64] = A[64][81 -> 96] x W[96][64] on the matrix cores: one 32x32 tile per wave, 48 MFMA steps.
-  extern __shared__ float sm[];
-  constexpr int SLD = STEM_FWD_LDA;          // odd row stride -> conflict-free column reads of A
-  const int KC = K * STEM_CIN;
-  float* in_s = sm;                          // [STEM_ROWS][SLD]   (columns >= KC are zero)
-  float* W_s = sm + STEM_ROWS * SLD;         // [96][64]           (rows >= KC are zero)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5, wr = wave >> 1, wc = wave & 1;
-  const int64_t m0 = (int64_t)blockIdx.x * STEM_ROWS;
-  for (int t = tid; t < STEM_ROWS * (SLD - KC); t += 256) {
-    int row = t / (SLD - KC), c = KC + t % (SLD - KC);
-    in_s[row * SLD + c] = 0.f;
-  }
-  for (int t = tid; t < STEM_ROWS * K; t += 256) {
-    int k = t / STEM_ROWS, row = t % STEM_ROWS;
-    int64_t o = m0 + row;
-    int64_t oc = o < n_out ? o : n_out - 1;
-    int i = nbr[(int64_t)k * n_out + oc];
-    if (o >= n_out) i = -1;
-    const float* src = i < 0 ? g_zero_row : in + (int64_t)i * 3;
-    float a = src[0], b = src[1], c = src[2];       // (r2: one 12-byte load instead of three dwords is no faster)
-    in_s[row * SLD + k * 3] = a; in_s[row * SLD + k * 3 + 1] = b; in_s[row * SLD + k * 3 + 2] = c;
-  }
-  for (int t = tid; t < 96 * 16; t += 256) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (t < KC * 16) v = reinterpret_cast<const f32x4*>(W)[t];
-    reinterpret_cast<f32x4*>(W_s)[t] = v;
-  }
-  __syncthreads();
-  if (col) {
-    // training: the gathered inputs of the tile go out as rows of `col` (n_out, 84) — the weight gradient then streams them
-    // instead of repeating 27 scattered 12-byte reads per output row (r2: 390 -> ~100 us; the forward pays one 195 MB write)
-    for (int t = tid; t < STEM_ROWS * (STEM_COL_LD / 4); t += 256) {
-      const int row = t / (STEM_COL_LD / 4), c = (t % (STEM_COL_LD / 4)) * 4;
-      const int64_t o = m0 + row;
-      if (o < n_out) {
-        const float* sp = in_s + row * SLD + c;
-        f32x4 v = {sp[0], sp[1], sp[2], sp[3]};
-        *reinterpret_cast<f32x4*>(col + o * STEM_COL_LD + c) = v;
-      }
-    }
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  const float* ap = in_s + (wr * 32 + r) * SLD + h;
-  const float* bp = W_s + h * 64 + wc * 32 + r;
-#pragma unroll 8
-  for (int sidx = 0; sidx < 48; ++sidx)
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * sidx], bp[2 * sidx * 64], acc, 0, 0, 0);
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    int64_t o = m0 + wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-    if (o < n_out) out[o * 64 + wc * 32 + r] = acc[e];
-  }
-}
-
-// stem wgrad on the matrix cores: part[block][j][co] = sum over the block's rows of A[row][j] * gout[row][co], with
-// A[row][j = 3k+c] = in[nbr[k][row]][c] staged in LDS (81 real columns padded to 96 = 3 MFMA tiles, gout 64 = 2 tiles).
-// Each of the 4 waves owns a quarter of every 64-row chunk as its reduction slice and all 6 tiles; the four partial
-// tiles are summed through LDS in wave order (deterministic) at the end.
-#define STEM_JP 96
-__global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ in, const float* __restrict__ gout,
-                                                    const int* __restrict__ nbr, float* __restrict__ part, int64_t n_out,
-                                                    int K, int64_t rows_per_block) {
-  extern __shared__ float sm[];
-  const int KC = K * STEM_CIN;
-  float* in_s = sm;                          // [STEM_ROWS][STEM_JP]   (columns >= KC stay zero)
-  float* g_s = sm + STEM_ROWS * STEM_JP;     // [STEM_ROWS][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r_end = r_begin + rows_per_block;
-  if (r_end > n_out) r_end = n_out;
-  for (int t = tid; t < STEM_ROWS * STEM_JP; t += 256) in_s[t] = 0.f;
-  f32x16 acc[3][2];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  // register-prefetch pipeline (as k_conv_mfma): the 27 x 3 gathered inputs and the gout rows of chunk t+1 are in flight
-  // while chunk t is multiplied (r2: without it the index -> gather chain of every 64-row chunk was exposed: 0.6 TB/s)
-  constexpr int NG = (STEM_ROWS * 27 + 255) / 256;          // gathers per thread per chunk (K <= 27)
-  float pa[NG][3];
-  f32x4 pg[4];
-  auto load_chunk = [&](int64_t rb) {
-    int idx[NG];
-#pragma unroll
-    for (int u = 0; u < NG; ++u) {
-      const int t = tid + 256 * u;
-      const int k = t / STEM_ROWS, row = t % STEM_ROWS;
-      const int64_t o = rb + row;
-      const int64_t oc = o < r_end ? o : r_end - 1;
-      const int kk = k < K ? k : K - 1;
-      int i = nbr[(int64_t)kk * n_out + oc];
-      idx[u] = (o < r_end && k < K) ? i : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int t = tid + 256 * u;
-      const int64_t o = rb + (t >> 4);
-      const float* gp = o < r_end ? gout + o * 64 + (t & 15) * 4 : g_zero_row;
-      pg[u] = *reinterpret_cast<const f32x4*>(gp);
-    }
-#pragma unroll
-    for (int u = 0; u < NG; ++u) {
-      const float* src = idx[u] < 0 ? g_zero_row : in + (int64_t)idx[u] * 3;
-      pa[u][0] = src[0]; pa[u][1] = src[1]; pa[u][2] = src[2];
-    }
-  };
-  if (r_begin < r_end) load_chunk(r_begin);
-  for (int64_t rb = r_begin; rb < r_end; rb += STEM_ROWS) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NG; ++u) {
-      const int t = tid + 256 * u;
-      const int k = t / STEM_ROWS, row = t % STEM_ROWS;
-      if (k < K) {
-        in_s[row * STEM_JP + k * 3] = pa[u][0]; in_s[row * STEM_JP + k * 3 + 1] = pa[u][1]; in_s[row * STEM_JP + k * 3 + 2] = pa[u][2];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) reinterpret_cast<f32x4*>(g_s)[tid + 256 * u] = pg[u];
-    __syncthreads();
-    load_chunk(rb + STEM_ROWS < r_end ? rb + STEM_ROWS : rb);          // unconditional (see k_conv_mfma)
-#pragma unroll
-    for (int sidx = 0; sidx < 8; ++sidx) {
-      const int row = wave * 16 + 2 * sidx + h;
-      float a[3], b[2];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a[i] = in_s[row * STEM_JP + i * 32 + r];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = g_s[row * 64 + j * 32 + r];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // cross-wave sum in wave order through LDS ([96][64] floats = 24 KB, reusing the staging area)
-  __syncthreads();
-  float* red = sm;
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            int jj = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, co = j * 32 + r;
-            float v = acc[i][j][e];
-            if (w > 0) v += red[jj * 64 + co];
-            red[jj * 64 + co] = v;
-          }
-    }
-    __syncthreads();
-  }
-  float* dst = part + (int64_t)blockIdx.x * KC * 64;
-  for (int t = tid; t < KC * 64; t += 256) dst[t] = red[t];
-}
-
-// The same reduction with the gathered inputs read back from `col` (k_stem_fwd) — no neighbour table, no gathers.
-__global__ __launch_bounds__(256) void k_stem_wgrad_col(const float* __restrict__ col, const float* __restrict__ gout,
-                                                        float* __restrict__ part, int64_t n_out, int K, int64_t rows_per_block) {
-  extern __shared__ float sm[];
-  const int KC = K * STEM_CIN;
-  float* in_s = sm;                          // [STEM_ROWS][STEM_JP]   (columns >= KC stay zero)
-  float* g_s = sm + STEM_ROWS * STEM_JP;     // [STEM_ROWS][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r_end = r_begin + rows_per_block;
-  if (r_end > n_out) r_end = n_out;
-  for (int t = tid; t < STEM_ROWS * STEM_JP; t += 256) in_s[t] = 0.f;
-  f32x16 acc[3][2];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  // the gathered inputs come as rows of `col` (saved by k_stem_fwd): two coalesced streams, prefetched one chunk ahead
-  constexpr int NC = (STEM_ROWS * (STEM_COL_LD / 4) + 255) / 256;      // float4 per thread per chunk
-  f32x4 pc[NC], pg[4];
-  auto load_chunk = [&](int64_t rb) {
-#pragma unroll
-    for (int u = 0; u < NC; ++u) {
-      const int t = tid + 256 * u;
-      const int row = t / (STEM_COL_LD / 4), c = (t % (STEM_COL_LD / 4)) * 4;
-      const int64_t o = rb + row;
-      const float* cp = (o < r_end && row < STEM_ROWS) ? col + o * STEM_COL_LD + c : g_zero_row;
-      pc[u] = *reinterpret_cast<const f32x4*>(cp);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int t = tid + 256 * u;
-      const int64_t o = rb + (t >> 4);
-      const float* gp = o < r_end ? gout + o * 64 + (t & 15) * 4 : g_zero_row;
-      pg[u] = *reinterpret_cast<const f32x4*>(gp);
-    }
-  };
-  if (r_begin < r_end) load_chunk(r_begin);
-  for (int64_t rb = r_begin; rb < r_end; rb += STEM_ROWS) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NC; ++u) {
-      const int t = tid + 256 * u;
-      const int row = t / (STEM_COL_LD / 4), c = (t % (STEM_COL_LD / 4)) * 4;
-      if (row < STEM_ROWS) *reinterpret_cast<f32x4*>(&in_s[row * STEM_JP + c]) = pc[u];      // columns 84..95 stay zero
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) reinterpret_cast<f32x4*>(g_s)[tid + 256 * u] = pg[u];
-    __syncthreads();
-    load_chunk(rb + STEM_ROWS < r_end ? rb + STEM_ROWS : rb);          // unconditional (see k_conv_mfma)
-#pragma unroll
-    for (int sidx = 0; sidx < 8; ++sidx) {
-      const int row = wave * 16 + 2 * sidx + h;
-      float a[3], b[2];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a[i] = in_s[row * STEM_JP + i * 32 + r];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = g_s[row * 64 + j * 32 + r];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // cross-wave sum in wave order through LDS ([96][64] floats = 24 KB, reusing the staging area)
-  __syncthreads();
-  float* red = sm;
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            int jj = i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h, co = j * 32 + r;
-            float v = acc[i][j][e];
-            if (w > 0) v += red[jj * 64 + co];
-            red[jj * 64 + co] = v;
-          }
-    }
-    __syncthreads();
-  }
-  float* dst = part + (int64_t)blockIdx.x * KC * 64;
-  for (int t = tid; t < KC * 64; t += 256) dst[t] = red[t];
-}
-
-// generic fallback (any Cin/Cout): one thread per (row, cout).  Used for the Cin=3 stem and as the
-// cross-check path of the parity tests (FC_CONV_FMA).
-__global__ void k_conv_fma(const float* __restrict__ in, const float* __restrict__ W, const int* __restrict__ nbr,
-                           float* __restrict__ out, int64_t n_out, int K, int Cin, int Cout, int wt) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_out * Cout) return;
-  int64_t o = t / Cout;
-  int co = (int)(t % Cout);
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) {
-    int i = nbr ? nbr[(int64_t)k * n_out + o] : (int)o;
-    if (i < 0) continue;
-    const float* x = in + (int64_t)i * Cin;
-    const float* w = W + (int64_t)k * Cin * Cout + (wt ? (int64_t)co * Cin : co);
-    const int64_t ws = wt ? 1 : Cout;             // wt: W[k] stored (Cout, Cin)
-    for (int ci = 0; ci < Cin; ++ci) acc = fmaf(x[ci], w[ci * ws], acc);
-  }
-  out[t] = acc;
 }
 
 static_assert(STEM_CIN == 3 && STEM_COUT == 64 && BK == 32, "conv_route.h spells these shapes out");
@@ -1567,399 +577,7 @@ int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, hipStr
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------
-// wgrad:  gW[k][ci][co] = sum_o in[nbr[k][o]][ci] * gout[o][co]
-// GEMM with M = Cin, N = Cout and the reduction over output rows, split over `S` row ranges whose
-// partial products are written to the workspace and summed by k_wgrad_reduce in a fixed order
-// (deterministic, no atomics).
-// PAIRS: `nbr` / `row_index` are the exact pair lists of fc_kernel_map_pairs (input row, output row; `cnt[k]` valid
-// entries per offset) and the reduction runs over the pairs only, split evenly over gridDim.x on the device.
-template <int BMc, int BNc, bool HAS_NBR, int BKR, bool PAIRS>
-__global__ __launch_bounds__(256, 2) void k_wgrad_mfma(const float* __restrict__ in, const float* __restrict__ gout,
-                                                    const int* __restrict__ nbr, const int* __restrict__ row_index,
-                                                    const int* __restrict__ cnt,
-                                                    float* __restrict__ part, int64_t n_out, int K, int Cin, int Cout,
-                                                    int64_t rows_per_split) {
-  constexpr int TM = BMc / 64, TN = BNc / 64;
-  constexpr int AR = BMc * BKR / 1024, GR = BNc * BKR / 1024;    // float4 loads per thread per stage (BKR rows)
-  __shared__ __attribute__((aligned(16))) float As[BKR * BMc];
-  __shared__ __attribute__((aligned(16))) float Gs[BKR * BNc];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  const int tiles_n = Cout / BNc, tiles_m = Cin / BMc;
-  int y = blockIdx.y;
-  const int tn = y % tiles_n; y /= tiles_n;
-  const int tm = y % tiles_m; y /= tiles_m;
-  const int k = y;
-  const int ci0 = tm * BMc, co0 = tn * BNc;
-  int64_t total = n_out;
-  if (PAIRS) {
-    total = cnt[k];
-    rows_per_split = ((total + gridDim.x - 1) / gridDim.x + BKR - 1) / BKR * BKR;
-  }
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_split;
-  int64_t r_end = r_begin + rows_per_split;
-  if (r_end > total) r_end = total;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // register-prefetch pipeline: the gathers + gout rows of chunk t+1 are in flight while chunk t is multiplied.
-  // (Measured r1: processing wgrad rows in occupancy-mask order with per-chunk skipping LOSES 15-35 % — gout rows stop
-  //  being sequential and the skip test costs a barrier per chunk — so wgrad always walks rows in natural order
-  //  and row_index must be NULL.)
-  f32x4 av[AR], gv[GR];
-  auto load_chunk = [&](int64_t rb) {        // branch-free, batched (see k_conv_mfma): indices, gout rows, gathers
-    int src[AR];
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      int lin = tid + 256 * i;
-      int rr = lin / (BMc / 4);
-      int64_t row = rb + rr;
-      int64_t rc = row < r_end ? row : r_end - 1;
-      int t = HAS_NBR ? nbr[(int64_t)k * n_out + rc] : (int)rc;      // compile-time: no null test between the loads
-      src[i] = row < r_end ? t : -1;
-    }
-#pragma unroll
-    for (int i = 0; i < GR; ++i) {
-      int lin = tid + 256 * i;
-      int rr = lin / (BNc / 4), c4 = lin % (BNc / 4);
-      int64_t row = rb + rr;
-      int64_t rc = row < r_end ? row : r_end - 1;
-      if (PAIRS) rc = row_index[(int64_t)k * n_out + rc];
-      const float* gp = row < r_end ? gout + rc * Cout + co0 + c4 * 4 : g_zero_row + (c4 & 15) * 4;
-      gv[i] = *reinterpret_cast<const f32x4*>(gp);
-    }
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      int lin = tid + 256 * i;
-      int c4 = lin % (BMc / 4);
-      const float* ap = src[i] < 0 ? g_zero_row + (c4 & 15) * 4 : in + (int64_t)src[i] * Cin + ci0 + c4 * 4;
-      av[i] = *reinterpret_cast<const f32x4*>(ap);
-    }
-  };
-  if (r_begin < r_end) load_chunk(r_begin);
-  for (int64_t rb = r_begin; rb < r_end; rb += BKR) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      int lin = tid + 256 * i;
-      int rr = lin / (BMc / 4), c4 = lin % (BMc / 4);
-      *reinterpret_cast<f32x4*>(&As[rr * BMc + c4 * 4]) = av[i];
-    }
-#pragma unroll
-    for (int i = 0; i < GR; ++i) {
-      int lin = tid + 256 * i;
-      int rr = lin / (BNc / 4), c4 = lin % (BNc / 4);
-      *reinterpret_cast<f32x4*>(&Gs[rr * BNc + c4 * 4]) = gv[i];
-    }
-    __syncthreads();
-    if (rb + BKR < r_end) load_chunk(rb + BKR);
-#pragma unroll
-    for (int q = 0; q < BKR / 8; ++q) {
-      float a[TM][4], b[TN][4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a[i][e] = As[(8 * q + 4 * h + e) * BMc + wr * (BMc / 2) + i * 32 + r];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b[j][e] = Gs[(8 * q + 4 * h + e) * BNc + wc * (BNc / 2) + j * 32 + r];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
-    }
-  }
-  float* dst = part + ((int64_t)blockIdx.x * K + k) * Cin * Cout;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int row = ci0 + wr * (BMc / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        int col = co0 + wc * (BNc / 2) + j * 32 + r;
-        dst[(int64_t)row * Cout + col] = acc[i][j][e];
-      }
-}
-
-// Deeper-pipelined weight gradient (64-channel Cin tile x BNc, 32-row chunks; same partial layout and results as
-// k_wgrad_mfma).  r2 ISA reading of the pair-list path of k_wgrad_mfma: every gout row of a chunk went through its own
-// `row index load -> s_waitcnt vmcnt(0) -> row load` chain (a bounds branch per load) — five exposed round trips in front of
-// 2 048 MFMA cycles.  Here the (input row, output row) indices of chunk t+2 are requested while chunk t+1's rows are
-// (branch-free: out-of-range rows read the zero row), and the MFMA fragments of 8-row step q+1 are read from LDS while step
-// q multiplies.  3 waves per SIMD.
-template <int BNc, bool HAS_NBR, bool PAIRS>
-__global__ __launch_bounds__(256, 3) void k_wgrad_mfma_p(const float* __restrict__ in, const float* __restrict__ gout,
-                                                          const int* __restrict__ nbr, const int* __restrict__ row_index,
-                                                          const int* __restrict__ cnt, float* __restrict__ part,
-                                                          int64_t n_out, int K, int Cin, int Cout, int64_t rows_per_split) {
-  constexpr int BMc = 64, BKR = 32;
-  constexpr int TN = BNc / 64;
-  constexpr int AR = 2, GR = BNc * BKR / 1024;   // float4 loads per thread per chunk
-  __shared__ __attribute__((aligned(16))) float As[BKR * BMc];
-  __shared__ __attribute__((aligned(16))) float Gs[BKR * BNc];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  const int tiles_n = Cout / BNc, tiles_m = Cin / BMc;
-  int y = blockIdx.y;
-  const int tn = y % tiles_n; y /= tiles_n;
-  const int tm = y % tiles_m; y /= tiles_m;
-  const int k = y;
-  const int ci0 = tm * BMc, co0 = tn * BNc;
-  int64_t total = n_out;
-  if (PAIRS) {
-    total = cnt[k];
-    rows_per_split = ((total + gridDim.x - 1) / gridDim.x + BKR - 1) / BKR * BKR;
-  }
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_split;
-  int64_t r_end = r_begin + rows_per_split;
-  if (r_end > total) r_end = total;
-
-  f32x16 acc[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-
-  if (r_begin < r_end) {
-    const int* tab_in = HAS_NBR ? nbr + (int64_t)k * n_out : nullptr;
-    const int* tab_out = PAIRS ? row_index + (int64_t)k * n_out : nullptr;
-    const int a_rr[AR] = {tid / 16, (tid + 256) / 16};
-    const int a_c4 = tid % 16;
-    int g_rr[GR];
-#pragma unroll
-    for (int i = 0; i < GR; ++i) g_rr[i] = (tid + 256 * i) / (BNc / 4);
-    const int g_c4 = tid % (BNc / 4);
-    // indices of a chunk (raw table entries; rows beyond the range are clamped here and zeroed at the row load)
-    int ia[AR], ig[GR], ian[AR], ign[GR];
-    auto fetch_idx = [&](int64_t rb, int (&va)[AR], int (&vg)[GR]) {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        int64_t row = rb + a_rr[i];
-        if (row >= r_end) row = r_end - 1;
-        va[i] = HAS_NBR ? tab_in[row] : (int)row;
-      }
-#pragma unroll
-      for (int i = 0; i < GR; ++i) {
-        int64_t row = rb + g_rr[i];
-        if (row >= r_end) row = r_end - 1;
-        vg[i] = PAIRS ? tab_out[row] : (int)row;
-      }
-    };
-    f32x4 av[AR], gv[GR];
-    auto load_rows = [&](int64_t rb) {          // rows of chunk rb from the indices in ia / ig
-#pragma unroll
-      for (int i = 0; i < GR; ++i) {
-        const bool ok = rb + g_rr[i] < r_end;
-        const float* gp = ok ? gout + (int64_t)ig[i] * Cout + co0 + g_c4 * 4 : g_zero_row + (g_c4 & 15) * 4;
-        gv[i] = *reinterpret_cast<const f32x4*>(gp);
-      }
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const bool ok = rb + a_rr[i] < r_end && ia[i] >= 0;
-        const float* ap = ok ? in + (int64_t)ia[i] * Cin + ci0 + a_c4 * 4 : g_zero_row + a_c4 * 4;
-        av[i] = *reinterpret_cast<const f32x4*>(ap);
-      }
-    };
-    fetch_idx(r_begin, ia, ig);
-    fetch_idx(r_begin + BKR < r_end ? r_begin + BKR : r_begin, ian, ign);
-    load_rows(r_begin);
-    for (int64_t rb = r_begin; rb < r_end; rb += BKR) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < AR; ++i) *reinterpret_cast<f32x4*>(&As[a_rr[i] * BMc + a_c4 * 4]) = av[i];
-#pragma unroll
-      for (int i = 0; i < GR; ++i) *reinterpret_cast<f32x4*>(&Gs[g_rr[i] * BNc + g_c4 * 4]) = gv[i];
-      __syncthreads();
-      // chunk t+1: its indices arrived a chunk ago; request chunk t+2's indices, then t+1's rows (unconditional: past the
-      // end the last chunk is re-read and never used)
-      const int64_t nb = rb + BKR < r_end ? rb + BKR : rb;
-      const int64_t nnb = nb + BKR < r_end ? nb + BKR : nb;
-#pragma unroll
-      for (int i = 0; i < AR; ++i) ia[i] = ian[i];
-#pragma unroll
-      for (int i = 0; i < GR; ++i) ig[i] = ign[i];
-      fetch_idx(nnb, ian, ign);
-      load_rows(nb);
-      float fa[2][4], fb[2][TN][4];
-      auto read_frag = [&](int q, int u) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          fa[u][e] = As[(8 * q + 4 * h + e) * BMc + wr * 32 + r];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) fb[u][j][e] = Gs[(8 * q + 4 * h + e) * BNc + wc * (BNc / 2) + j * 32 + r];
-        }
-      };
-      read_frag(0, 0);
-#pragma unroll
-      for (int q = 0; q < BKR / 8; ++q) {
-        if (q + 1 < BKR / 8) read_frag(q + 1, (q + 1) & 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q & 1][e], fb[q & 1][j][e], acc[j], 0, 0, 0);
-      }
-    }
-  }
-  float* dst = part + ((int64_t)blockIdx.x * K + k) * Cin * Cout;
-#pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = ci0 + wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      const int col = co0 + wc * (BNc / 2) + j * 32 + r;
-      dst[(int64_t)row * Cout + col] = acc[j][e];
-    }
-}
-
-// Dense-table weight gradient with KO kernel offsets per workgroup sharing ONE gout chunk.  With 64 input channels the
-// one-offset kernel above moves 24 KB (8 KB gathered rows + 16 KB of gout) per 0.5 MFLOP chunk = 22 FLOP/B and sits on
-// the fabric at ~4.3 TB/s (r2 measurement: 88 TF on the 437k-row level); re-using the staged gout rows for KO = 3 offsets
-// lifts that to 39 FLOP/B.  64 x BNc tile of gW[k] per offset, 4 waves as 2 x 2, reduction over rows in natural order.
-template <int BNc, int KO>
-__global__ __launch_bounds__(256, (BNc == 128) ? 2 : 3) void k_wgrad_multi(const float* __restrict__ in, const float* __restrict__ gout,
-                                                         const int* __restrict__ nbr, float* __restrict__ part, int64_t n_out,
-                                                         int K, int Cin, int Cout, int64_t rows_per_split) {
-  constexpr int TN = BNc / 64;
-  constexpr int GR = BNc * 32 / 1024;            // float4 gout loads per thread per 32-row chunk
-  __shared__ __attribute__((aligned(16))) float As[KO][32 * 64];
-  __shared__ __attribute__((aligned(16))) float Gs[32 * BNc];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  const int tiles_n = Cout / BNc, tiles_m = Cin / 64;
-  int y = blockIdx.y;
-  const int tn = y % tiles_n; y /= tiles_n;
-  const int tm = y % tiles_m; y /= tiles_m;
-  const int k0 = y * KO;
-  const int ci0 = tm * 64, co0 = tn * BNc;
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_split;
-  int64_t r_end = r_begin + rows_per_split;
-  if (r_end > n_out) r_end = n_out;
-
-  f32x16 acc[KO][TN];
-#pragma unroll
-  for (int o = 0; o < KO; ++o)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[o][j][e] = 0.f;
-
-  f32x4 av[KO][2], gv[GR];
-  auto load_chunk = [&](int64_t rb) {        // branch-free, batched: indices, gout rows, gathers
-    int src[KO][2];
-#pragma unroll
-    for (int o = 0; o < KO; ++o)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int rr = (tid + 256 * i) / 16;
-        const int64_t row = rb + rr;
-        const int64_t rc = row < r_end ? row : r_end - 1;
-        const int kk = k0 + o < K ? k0 + o : K - 1;
-        const int t = nbr[(int64_t)kk * n_out + rc];
-        src[o][i] = (row < r_end && k0 + o < K) ? t : -1;
-      }
-#pragma unroll
-    for (int i = 0; i < GR; ++i) {
-      const int lin = tid + 256 * i;
-      const int rr = lin / (BNc / 4), c4 = lin % (BNc / 4);
-      const int64_t row = rb + rr;
-      const float* gp = row < r_end ? gout + row * Cout + co0 + c4 * 4 : g_zero_row + (c4 & 15) * 4;
-      gv[i] = *reinterpret_cast<const f32x4*>(gp);
-    }
-#pragma unroll
-    for (int o = 0; o < KO; ++o)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int c4 = (tid + 256 * i) % 16;
-        const float* ap = src[o][i] < 0 ? g_zero_row + c4 * 4 : in + (int64_t)src[o][i] * Cin + ci0 + c4 * 4;
-        av[o][i] = *reinterpret_cast<const f32x4*>(ap);
-      }
-  };
-  if (r_begin < r_end) load_chunk(r_begin);
-  const bool prio = g_fc_prio == 0;               // see g_fc_prio (mode 1: forward / backward-data kernels only)
-  for (int64_t rb = r_begin; rb < r_end; rb += 32) {
-    __syncthreads();
-#pragma unroll
-    for (int o = 0; o < KO; ++o)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int lin = tid + 256 * i;
-        *reinterpret_cast<f32x4*>(&As[o][(lin / 16) * 64 + (lin % 16) * 4]) = av[o][i];
-      }
-#pragma unroll
-    for (int i = 0; i < GR; ++i) {
-      const int lin = tid + 256 * i;
-      *reinterpret_cast<f32x4*>(&Gs[(lin / (BNc / 4)) * BNc + (lin % (BNc / 4)) * 4]) = gv[i];
-    }
-    __syncthreads();
-    load_chunk(rb + 32 < r_end ? rb + 32 : rb);            // unconditional (see k_conv_mfma)
-    if (prio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float b[TN][4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b[j][e] = Gs[(8 * q + 4 * h + e) * BNc + wc * (BNc / 2) + j * 32 + r];
-#pragma unroll
-      for (int o = 0; o < KO; ++o) {
-        float a[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] = As[o][(8 * q + 4 * h + e) * 64 + wr * 32 + r];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[o][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[j][e], acc[o][j], 0, 0, 0);
-      }
-    }
-    if (prio) __builtin_amdgcn_s_setprio(0);
-  }
-#pragma unroll
-  for (int o = 0; o < KO; ++o) {
-    if (k0 + o >= K) break;
-    float* dst = part + ((int64_t)blockIdx.x * K + k0 + o) * Cin * Cout;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = ci0 + wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const int col = co0 + wc * (BNc / 2) + j * 32 + r;
-        dst[(int64_t)row * Cout + col] = acc[o][j][e];
-      }
-  }
-}
-
-// generic wgrad: block = (row range, k); each thread owns (ci,co) pairs strided by blockDim.
-__global__ void k_wgrad_fma(const float* __restrict__ in, const float* __restrict__ gout, const int* __restrict__ nbr,
-                            float* __restrict__ part, int64_t n_out, int K, int Cin, int Cout, int64_t rows_per_split) {
-  const int k = blockIdx.y;
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_split;
-  int64_t r_end = r_begin + rows_per_split;
-  if (r_end > n_out) r_end = n_out;
-  float* dst = part + ((int64_t)blockIdx.x * K + k) * Cin * Cout;
-  for (int p = threadIdx.x; p < Cin * Cout; p += blockDim.x) {
-    int ci = p / Cout, co = p % Cout;
-    float acc = 0.f;
-    for (int64_t o = r_begin; o < r_end; ++o) {
-      int i = nbr ? nbr[(int64_t)k * n_out + o] : (int)o;
-      if (i >= 0) acc = fmaf(in[(int64_t)i * Cin + ci], gout[o * Cout + co], acc);
-    }
-    dst[p] = acc;
-  }
-}
-
+// ---- weight gradient: the fixed-order sums of the partial products (kernels: wgrad_f32.h, wgrad_x6.h) ----
 __global__ void k_wgrad_reduce(const float* __restrict__ part, float* __restrict__ gW, int64_t elems, int S) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= elems) return;

@@ -33,16 +33,9 @@ __global__ __launch_bounds__(256, BN == 64 ? 4 : 3) void k_conv_h3r(
   const int n0 = blockIdx.y * BN;
   int S = gridDim.z, z = blockIdx.z;
   int kbase = 0;
-  if (cnt) {                                     // pair mode: see k_conv_x6
-    if (gridDim.z == 1 && K > 1) {
-      int k = 0;
-      for (; k < K - 1; ++k) {
-        const int64_t t = ((int64_t)cnt[k] + BM - 1) / BM;
-        if (bx < t) break;
-        bx -= t;
-      }
-      z = k;
-    }
+  if (cnt) {                                     // pair mode: tile_pair_walk (conv_tile.h)
+    const PairTile pt = tile_pair_walk<BM>(cnt, K, bx, z);
+    bx = pt.bx; z = pt.z;
     const int64_t stride = n_out;
     n_out = cnt[z];
     if (bx * BM >= n_out) return;
@@ -61,27 +54,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 4 : 3) void k_conv_h3r(
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  unsigned int kmask;
-  {
-    if (tid == 0) kmask_s = 0u;
-    __syncthreads();
-    if (tid < BM) {
-      unsigned int mk = 0u;
-      int64_t row = m0 + tid;
-      if (row < n_out) {
-        if (HAS_NBR) {
-          for (int k = z; k < K; k += S)
-            if (nbr[(int64_t)k * n_out + row] >= 0) mk |= 1u << k;
-        } else {
-          mk = 1u;
-        }
-      }
-      for (int off = 32; off > 0; off >>= 1) mk |= __shfl_xor(mk, off, 64);
-      if (lane == 0 && mk) atomicOr(&kmask_s, mk);
-    }
-    __syncthreads();
-    kmask = (unsigned int)__builtin_amdgcn_readfirstlane((int)kmask_s);
-  }
+  const unsigned int kmask = (unsigned int)__builtin_amdgcn_readfirstlane((int)tile_offset_mask<BM, HAS_NBR>(&kmask_s, nbr, m0, n_out, z, K, S, tid, lane));
   constexpr unsigned X6_DEAD = 0x80000000u;
 
   if (kmask) {

@@ -76,20 +76,10 @@ __global__ __launch_bounds__(256, (KO * (BMc / 64) * (BNc / 64) >= 6) ? 2 : 3) v
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
   const int r = lane & 31, h = lane >> 5;
-  const int tiles_n = Cout / BNc, tiles_m = Cin / BMc;
-  int y = blockIdx.y;
-  const int tn = y % tiles_n; y /= tiles_n;
-  const int tm = y % tiles_m; y /= tiles_m;
-  const int k0 = y * KO;
-  const int ci0 = tm * BMc, co0 = tn * BNc;
-  int64_t total = n_out;
-  if (PAIRS) {
-    total = cnt[k0];
-    rows_per_split = ((total + gridDim.x - 1) / gridDim.x + 31) / 32 * 32;
-  }
-  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_split;
-  int64_t r_end = r_begin + rows_per_split;
-  if (r_end > total) r_end = total;
+  const WgradTile wt = wgrad_tile<BMc, BNc>(Cin, Cout, KO);
+  const int k0 = wt.k0, ci0 = wt.ci0, co0 = wt.co0;
+  const WgradRows rows = wgrad_rows<PAIRS, 32>(cnt, k0, n_out, rows_per_split);
+  const int64_t r_begin = rows.begin, r_end = rows.end;
 
   f32x16 acc[KO][TM][TN];
 #pragma unroll

@@ -269,6 +269,7 @@ DEVICE_IDENTICAL_SOURCES = {
     'f17a9bc9f17e6a93': '7094ae11604f2248',      # csrc/exec_ops.h: the executor's row and descriptor layouts by name (host code only)
     'db8f1d2038ec0dfd': '7094ae11604f2248',      # csrc/conv_route.h: every convolution launch's route decided once, as data (host code only)
     'be6908a911e0989e': '7094ae11604f2248',      # csrc/norm_route.h: every normalisation launch's route decided once, as data (host code only)
+    '02ba23ed176093b4': '7094ae11604f2248',      # csrc/conv_tile.h: the kernels' shared tile prologue and weight-gradient decode; fp32 / stem kernels in headers of their own
 }
 
 
