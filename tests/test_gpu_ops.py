@@ -93,8 +93,41 @@ def test_kernel_maps_exact(ks, s):
     assert np.array_equal(nt, ref_t)
 
 
-def _conv_case(dev, n_points, Cin, Cout, ks, s, flags, seed=5, B=2, level_q=1, x6=None):
-    """x6: None = the default route (split-bf16 kernels where they exist), False = the fp32 MFMA / FMA kernels"""
+def _layer_routes(km, n_in, n_out, K, Cin, Cout, flags, x6):
+    """What the route query (fc_conv_fwd_route / fc_conv_wgrad_route, csrc/conv_route.h) says the forward, backward-data and
+    weight-gradient launches of Fn.sparse_conv on this map become, with the table kind and flags functional._SparseConv hands them
+    -> {'fwd' | 'dgrad' | 'wgrad': fields, the enums by their header names}"""
+    import fcaf3d_amd.functional as Fn
+    from fcaf3d_amd import _lib as L
+    from fcaf3d_amd.sparse import PAIR_CONV_ROWS
+    E = L.header_enums()
+    names = {'family': 'FC_FAM_', 'wsrc': 'FC_WSRC_', 'mode': 'FC_MODE_', 'epi': 'FC_EPI_'}
+
+    def named(r, over={}):
+        pre = dict(names, **over)
+        return {k: next((e for e, x in E.items() if k in pre and e.startswith(pre[k]) and x == v), v) for k, v in r.items()}
+
+    def conv(n_i, n_o, ci, co, pair_rows, transposed):
+        mfma = not (flags & Fn.CONV_FMA) and ci % 32 == 0 and co % 64 == 0
+        fl = flags | Fn.CONV_X6 if (x6 and mfma) else flags | Fn.CONV_WT if (transposed and Fn.DGRAD_WT) else flags
+        kind, live = E['FC_TABLE_SORTED' if (mfma and km.sort_rows) else 'FC_TABLE_DENSE'], 0
+        if km.use_pairs and pair_rows <= PAIR_CONV_ROWS and mfma:
+            kind, live = E['FC_TABLE_PAIRS'], km.pair_tiles(transposed=transposed)
+        rc, r = L.route('fc_conv_fwd_route', n_i, n_o, K, ci, co, fl, kind, live)
+        assert rc == 0
+        return named(r)
+    wpairs = km.use_pairs and not (flags & Fn.CONV_FMA) and Cin % 64 == 0 and Cout % 64 == 0
+    rc, w = L.route('fc_conv_wgrad_route', n_in, n_out, K, Cin, Cout, flags | Fn.WGRAD_X6 if x6 else flags,
+                    E['FC_TABLE_PAIRS' if wpairs else 'FC_TABLE_DENSE'])
+    assert rc == 0
+    return {'fwd': conv(n_in, n_out, Cin, Cout, n_out, False), 'dgrad': conv(n_out, n_in, Cout, Cin, n_in, True),
+            'wgrad': named(w, {'family': 'FC_WFAM_', 'table': 'FC_TABLE_'})}
+
+
+def _conv_case(dev, n_points, Cin, Cout, ks, s, flags, seed=5, B=2, level_q=1, x6=None, routes=None):
+    """x6: None = the default route (split-bf16 kernels where they exist), False = the fp32 MFMA / FMA kernels.
+    routes: {'fwd' | 'dgrad' | 'wgrad': {route field: value}} the launches of this case must take (`_layer_routes`): the case names
+    the kernels it claims to test and fails, before it launches, once the routing rules send the shape elsewhere"""
     import fcaf3d_amd.functional as Fn
     from fcaf3d_amd.sparse import CoordMap
     _, c_ref, _ = _scene_coords(seed, n_points=n_points, B=B)
@@ -120,6 +153,10 @@ def _conv_case(dev, n_points, Cin, Cout, ks, s, flags, seed=5, B=2, level_q=1, x
         Fn.X6 = x6
     try:
         km = cm.kernel_map(om, ks)
+        if routes:
+            got = _layer_routes(km, cm.n, om.n, ks ** 3, Cin, Cout, flags, Fn.X6)
+            for part, want in routes.items():
+                assert {k: got[part][k] for k in want} == want, (part, got[part], want)
         out_g = Fn.sparse_conv(xg, wg, km, om.n)
         gx_g, gw_g = torch.autograd.grad(out_g, [xg, wg], go.to(dev))
     finally:
@@ -186,8 +223,16 @@ def test_conv_mfma_k3s2_and_k1s2():
 
 @pytest.mark.parametrize('Cin,Cout,n,q', [(64, 64, 6000, 4), (128, 128, 6000, 4), (256, 256, 6000, 4), (64, 128, 100000, 1)])
 def test_conv_fp32_mfma_route(Cin, Cout, n, q):
-    """the fp32 MFMA kernels (v_mfma_f32_32x32x2_f32; FC_X6=0) stay a tested route"""
-    _conv_case(_dev(), n, Cin, Cout, 3, 1, 0, level_q=q, B=1 if n > 50000 else 2, x6=False)
+    """the fp32 MFMA kernels (v_mfma_f32_32x32x2_f32; FC_X6=0) stay a tested route.  What the route query says these shapes take, on
+    their mask-sorted tables: 10.9k rows — an offset-split launch of 128-row tiles inside the 768...1536-workgroup band, so
+    k_conv_glds forward and k_conv_mfma backward-data (the LDS-DMA image cannot be read transposed); 92.5k rows — unsplit,
+    k_conv_mfma_p both ways; the weight gradients walk the pair lists on the fp32 kernels"""
+    big = n > 50000
+    fwd, dgrad = ('FC_FAM_MFMA_P', 'FC_FAM_MFMA_P') if big else ('FC_FAM_GLDS', 'FC_FAM_MFMA')
+    _conv_case(_dev(), n, Cin, Cout, 3, 1, 0, level_q=q, B=1 if big else 2, x6=False,
+               routes={'fwd': dict(family=fwd, bm=128, mode='FC_MODE_FP32', wsrc='FC_WSRC_FP32'),
+                       'dgrad': dict(family=dgrad, bm=128, mode='FC_MODE_FP32', wsrc='FC_WSRC_FP32_T'),
+                       'wgrad': dict(mode='FC_MODE_FP32', table='FC_TABLE_PAIRS')})
 
 
 def test_split_bf16_convolution_sits_at_fp32_rounding_level_against_fp64():
@@ -233,11 +278,37 @@ def test_split_bf16_convolution_sits_at_fp32_rounding_level_against_fp64():
 
 @pytest.mark.parametrize('Cin,Cout', [(64, 64), (64, 128)])
 def test_conv_mfma_large_tiles(Cin, Cout):
-    # > 65k output rows -> the 128-row tile variants
-    _conv_case(_dev(), 100000, Cin, Cout, 3, 1, 0, B=1)
+    # 92.5k rows on the mask-sorted table: UNSPLIT launches (S = 1, statistics epilogue in the kernel) of 128-row tiles on the split
+    # route through buffer descriptors — k_conv_x6 on 64-column tiles, k_conv_h3r on 128-column ones (conv_route.h takes 128-row
+    # tiles from n > 64 and four tiles on, not from a row count) — and k_wgrad_x6t over the pair lists
+    fam = {64: 'FC_FAM_X6', 128: 'FC_FAM_H3R'}
+    _conv_case(_dev(), 100000, Cin, Cout, 3, 1, 0, B=1,
+               routes={'fwd': dict(family=fam[Cout], bm=128, bn=Cout, s=1, mode='FC_MODE_H3', wsrc='FC_WSRC_IMAGE', buf=1, epi='FC_EPI_KERNEL'),
+                       'dgrad': dict(family='FC_FAM_X6', bm=128, bn=64, s=1, mode='FC_MODE_H3', wsrc='FC_WSRC_IMAGE', buf=1),
+                       'wgrad': dict(family='FC_WFAM_X6T', bm=64, bn=Cout, table='FC_TABLE_PAIRS', mode='FC_MODE_H3')})
 
 
 _BM128, _BM256 = 2 << Fn.CONV_BM_SHIFT, 3 << Fn.CONV_BM_SHIFT
+
+
+_PAIRS_FP32 = dict(table='FC_TABLE_PAIRS', mode='FC_MODE_FP32')
+# The launch each flag of test_conv_kernel_variants_behind_flags is about, as the route query names it on that test's shapes.  The
+# backward-data pass reads the kernel transposed, which k_conv_glds cannot: it stays on k_conv_mfma.  The layer's weight gradient
+# walks the pair lists there, so FC_CONV_WGRAD_MULTI_OFF has nothing to switch (the dense-table kernels behind it:
+# test_dense_table_weight_gradient_kernels, tests/test_gpu_conv_exact.py) and the pipe flags pick k_wgrad_mfma / k_wgrad_mfma_p.
+_FLAG_ROUTES = {
+    _BM256: {'fwd': dict(family='FC_FAM_GLDS', bm=256, bn=64, wm=4), 'dgrad': dict(family='FC_FAM_MFMA', bm=256, bn=64, wm=4)},
+    Fn.CONV_WGRAD_MULTI_OFF: {'wgrad': dict(_PAIRS_FP32, ko=1)},
+    Fn.CONV_PIPE_ON: {'fwd': dict(family='FC_FAM_MFMA_P', bm=128), 'dgrad': dict(family='FC_FAM_MFMA_P', bm=128)},
+    Fn.CONV_PIPE_ON | _BM128: {'fwd': dict(family='FC_FAM_MFMA_P', bm=128), 'dgrad': dict(family='FC_FAM_MFMA_P', bm=128)},
+    Fn.CONV_PIPE_ON | _BM256: {'fwd': dict(family='FC_FAM_MFMA_P', bm=256, bn=64), 'dgrad': dict(family='FC_FAM_MFMA_P', bm=256, bn=64)},
+    Fn.CONV_GLDS: {'fwd': dict(family='FC_FAM_GLDS', bm=128), 'dgrad': dict(family='FC_FAM_MFMA', bm=128)},
+    Fn.CONV_GLDS | _BM256: {'fwd': dict(family='FC_FAM_GLDS', bm=256, bn=64), 'dgrad': dict(family='FC_FAM_MFMA', bm=256, bn=64)},
+    Fn.CONV_PIPE_OFF: {'fwd': dict(family='FC_FAM_MFMA', bm=128), 'dgrad': dict(family='FC_FAM_MFMA', bm=128)},
+    Fn.CONV_WGRAD_PIPE_OFF: {'wgrad': dict(_PAIRS_FP32, family='FC_WFAM_MFMA')},
+    Fn.CONV_WGRAD_PIPE_ON: {'wgrad': dict(_PAIRS_FP32, family='FC_WFAM_MFMA_P')},
+    Fn.CONV_WGRAD_PIPE_OFF | Fn.CONV_WGRAD_MULTI_OFF: {'wgrad': dict(_PAIRS_FP32, family='FC_WFAM_MFMA', ko=1)},
+}
 
 
 @pytest.mark.parametrize('flags,what', [(_BM256, '256x64 LDS tile (4x1 waves)'),
@@ -252,9 +323,10 @@ _BM128, _BM256 = 2 << Fn.CONV_BM_SHIFT, 3 << Fn.CONV_BM_SHIFT
                                         (Fn.CONV_WGRAD_PIPE_OFF | Fn.CONV_WGRAD_MULTI_OFF, 'r1 weight-gradient kernel, one offset per workgroup')])
 def test_conv_kernel_variants_behind_flags(flags, what):
     """every flag-selected kernel variant (conv.hip; the defaults are chosen by measurement) against the oracle,
-    forward + backward-data + backward-weights, on a strided and an unstrided map"""
-    _conv_case(_dev(), 9000, 64, 128, 3, 1, flags, level_q=4, x6=False)
-    _conv_case(_dev(), 9000, 64, 64, 3, 2, flags, level_q=2, x6=False)
+    forward + backward-data + backward-weights, on a strided and an unstrided map (15.4k result rows each: offset-split launches on
+    the mask-sorted tables, weight gradients over the pair lists).  _FLAG_ROUTES: what the route query must say the flag did there"""
+    _conv_case(_dev(), 9000, 64, 128, 3, 1, flags, level_q=4, x6=False, routes=_FLAG_ROUTES[flags])
+    _conv_case(_dev(), 9000, 64, 64, 3, 2, flags, level_q=2, x6=False, routes=_FLAG_ROUTES[flags])
 
 
 def test_pair_list_convolution_linear_live_tile_launch():
@@ -682,10 +754,12 @@ def _stats_case(dev, n_points, Cin, Cout, level_q, seed, B=2):
 
 
 @pytest.mark.parametrize('n_points,Cin,Cout,q,route', [
-    (100000, 64, 64, 4, 'tile epilogue'),           # ~64k rows: unsplit launch on the (mask-sorted) neighbour table
-    (100000, 128, 128, 8, 'pair lists'),            # ~16k rows, sparse: per offset over the pair lists, k_sum_pairs_stats
-    (100000, 256, 256, 16, 'pair lists, 64-row blocks'),   # ~3.7k rows
-    (100000, 256, 256, 32, 'pair lists, few rows'),  # ~900 rows: <= 64 row blocks of 16 rows
+    # what the route query says (fc_conv_fwd_route | FC_TABLE_STATS; the labels are the test ids and stay as they were):
+    (100000, 64, 64, 4, 'tile epilogue'),           # 62.4k rows: unsplit k_conv_x6 on the mask-sorted table, epilogue in the kernel
+    (100000, 128, 128, 8, 'pair lists'),            # 15.4k rows, above PAIR_CONV_ROWS since r6: offset-split (S = 8) k_conv_h3r on the
+                                                    # mask-sorted table, k_sum_parts_stats — no longer a pair-list launch
+    (100000, 256, 256, 16, 'pair lists, 64-row blocks'),   # 3.6k rows: per offset over the pair lists, k_sum_pairs_stats
+    (100000, 256, 256, 32, 'pair lists, few rows'),  # 870 rows: the same, <= 64 row blocks of 16 rows
 ])
 def test_conv_statistics_epilogue(n_points, Cin, Cout, q, route):
     """fc_conv_fwd_stats / fc_conv_fwd_pairs_tiles_stats: the result is bit for bit the plain launch's, and the table holds the
