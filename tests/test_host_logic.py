@@ -270,6 +270,7 @@ DEVICE_IDENTICAL_SOURCES = {
     'db8f1d2038ec0dfd': '7094ae11604f2248',      # csrc/conv_route.h: every convolution launch's route decided once, as data (host code only)
     'be6908a911e0989e': '7094ae11604f2248',      # csrc/norm_route.h: every normalisation launch's route decided once, as data (host code only)
     '02ba23ed176093b4': '7094ae11604f2248',      # csrc/conv_tile.h: the kernels' shared tile prologue and weight-gradient decode; fp32 / stem kernels in headers of their own
+    '2af8226cd1ab8dab': '7094ae11604f2248',      # csrc/norm_elem.h: the normalisation kernels' shared blocks; kernel families in headers of their own, norm.hip host only
 }
 
 
