@@ -458,6 +458,14 @@ int run_op_impl(Ctx& c, const int64_t* op) {
       if (c.dry) return 0;
       if ((int)m[MAP_K] != 8) return FC_EINVAL;
       if (op[NORM_POOL_FWD_AMAX_OUT_P1] > 0) fc_amax_out_hint(P1<unsigned>(c, op[NORM_POOL_FWD_AMAX_OUT_P1]));
+      if (op[NORM_POOL_FWD_MASK_P1] > 0)      // a training program: the per-child mask for the backward pass, the arg-max rows only where kept
+        return fc_norm_act_maxpool8_mask_fwd(P<const float>(c, op[NORM_POOL_FWD_X]), P<const int>(c, op[NORM_POOL_FWD_SEG]),
+                                             op[NORM_POOL_FWD_SEG] >= 0 ? 4 : 0, (int)op[NORM_POOL_FWD_C], P<const float>(c, op[NORM_POOL_FWD_MEAN]),
+                                             P<const float>(c, op[NORM_POOL_FWD_VAR]), (float)as_double(op[NORM_POOL_FWD_EPS]),
+                                             P<const float>(c, op[NORM_POOL_FWD_GAMMA]), P<const float>(c, op[NORM_POOL_FWD_BETA]),
+                                             (int)op[NORM_POOL_FWD_ACT], reinterpret_cast<const int*>(m[MAP_NBR]), m[MAP_N_OUT],
+                                             P<float>(c, op[NORM_POOL_FWD_OUT]), P<int>(c, op[NORM_POOL_FWD_ARG]), P<float>(c, op[NORM_POOL_FWD_Y]),
+                                             P<int>(c, op[NORM_POOL_FWD_PARENT]), P1<unsigned long long>(c, op[NORM_POOL_FWD_MASK_P1]), st);
       return fc_norm_act_maxpool8_fwd(P<const float>(c, op[NORM_POOL_FWD_X]), P<const int>(c, op[NORM_POOL_FWD_SEG]),
                                       op[NORM_POOL_FWD_SEG] >= 0 ? 4 : 0, (int)op[NORM_POOL_FWD_C], P<const float>(c, op[NORM_POOL_FWD_MEAN]),
                                       P<const float>(c, op[NORM_POOL_FWD_VAR]), (float)as_double(op[NORM_POOL_FWD_EPS]),
@@ -470,6 +478,15 @@ int run_op_impl(Ctx& c, const int64_t* op) {
       const int64_t n = c.dims[op[POOL_NORM_BWD_N]];
       const int C = (int)op[POOL_NORM_BWD_C], nseg = (int)c.dims[op[POOL_NORM_BWD_NSEG]];
       if (!want_ws(c, s, fc_maxpool8_norm_act_bwd_ws_bytes(n, C, nseg))) return 0;
+      if (op[POOL_NORM_BWD_MASK_P1] > 0)
+        return fc_maxpool8_mask_norm_act_bwd(P<const float>(c, op[POOL_NORM_BWD_X]), P<const float>(c, op[POOL_NORM_BWD_G_POOL]),
+                                             P1<const unsigned long long>(c, op[POOL_NORM_BWD_MASK_P1]), P<const int>(c, op[POOL_NORM_BWD_PARENT]),
+                                             P<const int>(c, op[POOL_NORM_BWD_SEG]), op[POOL_NORM_BWD_SEG] >= 0 ? 4 : 0, n, C, nseg,
+                                             P<const float>(c, op[POOL_NORM_BWD_MEAN]), P<const float>(c, op[POOL_NORM_BWD_VAR]),
+                                             P<const float>(c, op[POOL_NORM_BWD_CNT]), (float)as_double(op[POOL_NORM_BWD_EPS]),
+                                             P<const float>(c, op[POOL_NORM_BWD_GAMMA]), P<const float>(c, op[POOL_NORM_BWD_BETA]),
+                                             (int)op[POOL_NORM_BWD_ACT], P<float>(c, op[POOL_NORM_BWD_GX]), P<float>(c, op[POOL_NORM_BWD_SUMS]),
+                                             c.ws[s], c.ws_bytes[s], st);
       return fc_maxpool8_norm_act_bwd(P<const float>(c, op[POOL_NORM_BWD_X]), P<const float>(c, op[POOL_NORM_BWD_G_POOL]),
                                       P<const int>(c, op[POOL_NORM_BWD_ARG]), P<const int>(c, op[POOL_NORM_BWD_PARENT]),
                                       P<const int>(c, op[POOL_NORM_BWD_SEG]), op[POOL_NORM_BWD_SEG] >= 0 ? 4 : 0, n, C, nseg,

@@ -254,16 +254,17 @@ enum {  // the stem's instance norm + activation + 2x2x2 max pool in one pass
   NORM_POOL_FWD_ACT,
   NORM_POOL_FWD_MAP,   // (map) K = 8
   NORM_POOL_FWD_OUT,
-  NORM_POOL_FWD_ARG,   // arg-max rows
+  NORM_POOL_FWD_ARG,   // arg-max rows | -1 (with MASK_P1 only)
   NORM_POOL_FWD_Y,     // the normalised tensor, stored for `decisions` only | -1
   NORM_POOL_FWD_AMAX_OUT_P1,
   NORM_POOL_FWD_PARENT,  // child row -> pooled row, for the backward pass | -1
+  NORM_POOL_FWD_MASK_P1, // per-child arg-max mask (8 bytes per input row), for the backward pass: ARG may then be -1 (fc_norm_act_maxpool8_mask_fwd)
   NORM_POOL_FWD_END
 };
 enum {  // ... and its backward: pool backward + instance-norm backward without the scattered gradient in between
   POOL_NORM_BWD_X = 2,
   POOL_NORM_BWD_G_POOL,
-  POOL_NORM_BWD_ARG,
+  POOL_NORM_BWD_ARG,   // | -1 (with MASK_P1 only)
   POOL_NORM_BWD_PARENT,
   POOL_NORM_BWD_SEG,   // | -1
   POOL_NORM_BWD_N,     // (dim)
@@ -278,6 +279,7 @@ enum {  // ... and its backward: pool backward + instance-norm backward without 
   POOL_NORM_BWD_ACT,
   POOL_NORM_BWD_GX,
   POOL_NORM_BWD_SUMS,
+  POOL_NORM_BWD_MASK_P1, // the forward's mask: read instead of ARG (fc_maxpool8_mask_norm_act_bwd)
   POOL_NORM_BWD_END
 };
 enum {  // inv = -1, inv[rows[i]] = i

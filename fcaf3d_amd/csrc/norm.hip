@@ -55,9 +55,9 @@ static int bn_fwd(const float* x, int64_t n, int C, float eps, const float* gamm
 }
 
 // every backward entry point: the argument checks, the route, its workspace, its launches.  gy2 (nullable): a second contribution to the
-// incoming gradient; table: gy's producer's [nb_part][2][C]; POOL: gy is the pooled gradient, read through parent / argrow; amax (nullable):
+// incoming gradient; table: gy's producer's [nb_part][2][C]; POOL (norm_rows.h POOL_*): gy is the pooled gradient, read through parent and argrow (POOL_ARG: the arg-max rows; POOL_MASK: the per-child mask); amax (nullable):
 // max |gx| into the caller's (zeroed) word — late_hint: the word of fc_amax_out_hint, consumed once the checks have passed
-template <bool POOL>
+template <int POOL>
 static int norm_bwd(int form, const float* x, const float* y, const float* gy, const float* gy2, const int* parent, const int* argrow, const int* seg,
                     int seg_stride, int64_t n, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps, const float* gamma,
                     const float* beta, int act, float* gx, float* gres, float* sums, const float* table, int64_t nb_part, int64_t small_elems, void* ws,
@@ -71,14 +71,26 @@ static int norm_bwd(int form, const float* x, const float* y, const float* gy, c
     return FC_OK;
   }
   if (r.sums == FC_NRED_PARTIAL) {
-    k_norm_bwd_partial<POOL><<<FC_GRID(r.red, stream)>>>(x, y, gy, gy2, parent, argrow, seg, seg_stride, n, C, nseg, mean, var, eps, act, gamma, beta, r.red_rpb, (float*)ws);
+    // the instantiation that reads the operands this call has (norm_rows.h): y only where the activation's derivative is taken from it
+    const bool from_y = act && y;
+#define FC_PARTIAL(P, Y, G2) \
+  k_norm_bwd_partial<P, Y, G2><<<FC_GRID(r.red, stream)>>>(x, y, gy, gy2, parent, argrow, seg, seg_stride, n, C, nseg, mean, var, eps, act, gamma, beta, r.red_rpb, (float*)ws)
+    if constexpr (POOL != POOL_NONE) {
+      if (from_y || gy2) return FC_EINVAL;      // (the pooled entry point passes neither)
+      FC_PARTIAL(POOL, false, false);
+    } else if (from_y) {
+      if (gy2) FC_PARTIAL(POOL_NONE, true, true); else FC_PARTIAL(POOL_NONE, true, false);
+    } else {
+      if (gy2) FC_PARTIAL(POOL_NONE, false, true); else FC_PARTIAL(POOL_NONE, false, false);
+    }
+#undef FC_PARTIAL
     FC_CHECK_LAUNCH();
     table = (const float*)ws;
   }
   if (r.apply == FC_NBAPPLY_PROLOGUE) {
     k_bn1_bwd_apply<<<FC_GRID(r.ap, stream)>>>(x, y, gy, gy2, n, C, r.rpb, table, (int)r.np, mean, var, eps, gamma, beta, act, gx, gres, sums, r.cg, amax);
   } else {
-    k_stats_final<<<FC_GRID(r.fin, stream)>>>(table, nullptr, r.np, nseg, 2 * C, 2, sums, nullptr);
+    k_stats_final<<<FC_GRID(r.fin, stream)>>>(table, r.np, nseg, 2 * C, sums);
     FC_CHECK_LAUNCH();
     k_norm_bwd_apply<POOL><<<FC_GRID(r.ap, stream)>>>(x, y, gy, gy2, parent, argrow, seg, seg_stride, n, C, mean, var, eps, gamma, beta, sums, cnt, act, gx, gres, amax);
   }
@@ -113,10 +125,10 @@ static int col_stats(bool stats, const float* x, const int* seg, int seg_stride,
   const RowBlocks b = row_blocks(n, MAXBLOCKS);
   float* part = (float*)ws;
   float* part_cnt = stats ? part + b.nb * nseg * 2 * C : nullptr;
-  k_stats_partial<<<(unsigned)b.nb, g.threads, g.lds_fwd, stream>>>(x, seg, seg_stride, n, C, nseg, nullptr, stats ? 2 : 0, b.rpb, part, part_cnt);
+  k_stats_partial<<<(unsigned)b.nb, g.threads, g.lds_fwd, stream>>>(x, seg, seg_stride, n, C, nseg, stats, b.rpb, part, part_cnt);
   FC_CHECK_LAUNCH();
   if (stats) k_seg_meanvar_final<<<FC_GRID(final_launch(nseg, C), stream)>>>(part, part_cnt, b.nb, nseg, C, out, var, cnt);
-  else k_stats_final<<<FC_GRID(final_launch(nseg, C), stream)>>>(part, nullptr, b.nb, nseg, C, 2, out, nullptr);
+  else k_stats_final<<<FC_GRID(final_launch(nseg, C), stream)>>>(part, b.nb, nseg, C, out);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
@@ -188,7 +200,7 @@ int fc_bn_act_train_fwd(const float* x, int64_t n, int C, float eps, const float
 int fc_bn_act_train_bwd(const float* x, const float* y, const float* gy, int64_t n, int C, const float* mean,
                         const float* var, float eps, const float* gamma, const float* beta, int act, float* gx, float* gres,
                         float* sums, void* ws, int64_t ws_bytes, hipStream_t stream) {
-  return norm_bwd<false>(FC_NFORM_SMALL, x, y, gy, nullptr, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, nullptr, eps, gamma, beta, act, gx, gres, sums,
+  return norm_bwd<POOL_NONE>(FC_NFORM_SMALL, x, y, gy, nullptr, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, nullptr, eps, gamma, beta, act, gx, gres, sums,
                          nullptr, 0, 0, ws, ws_bytes, stream, nullptr, true);
 }
 
@@ -216,7 +228,7 @@ int fc_norm_act_bwd(const float* x, const float* y, const float* gy, const int* 
                     const float* beta, int act, float* gx, float* gres, float* sums, void* ws, int64_t ws_bytes,
                     hipStream_t stream) {
   unsigned* ao = take_amax_out();
-  return norm_bwd<false>(FC_NFORM_SEG, x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums,
+  return norm_bwd<POOL_NONE>(FC_NFORM_SEG, x, y, gy, nullptr, nullptr, nullptr, seg, seg_stride, n, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums,
                          nullptr, 0, 0, ws, ws_bytes, stream, ao);
 }
 
@@ -251,7 +263,7 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
                     float* gres, float* sums, const float* part, int64_t nb_part, int64_t small_elems, void* ws, int64_t ws_bytes,
                     hipStream_t stream) {
   unsigned* ao = take_amax_out();
-  return norm_bwd<false>(FC_NFORM_TRAIN, x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums, part, nb_part,
+  return norm_bwd<POOL_NONE>(FC_NFORM_TRAIN, x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums, part, nb_part,
                          small_elems, ws, ws_bytes, stream, ao);
 }
 
@@ -304,8 +316,22 @@ int fc_norm_act_maxpool8_fwd(const float* x, const int* seg, int seg_stride, int
   unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |out| into the caller's (zeroed) word
   if (n_out < 0 || C < 4 || C % 4 || act < 0 || act > 2) return FC_EINVAL;
   if (n_out == 0) return FC_OK;
-  k_norm_act_maxpool8_fwd<<<FC_GRID(rows_launch(n_out, C), stream)>>>(x, seg, seg_stride, C, mean, var, eps, gamma, beta, act, nbr, n_out, out, argrow, y,
-                                                                     parent, ao);
+  k_norm_act_maxpool8_fwd<false><<<FC_GRID(rows_launch(n_out, C), stream)>>>(x, seg, seg_stride, C, mean, var, eps, gamma, beta, act, nbr, n_out, out, argrow,
+                                                                            y, parent, nullptr, ao);
+  FC_CHECK_LAUNCH();
+  return FC_OK;
+}
+
+// the same pass writing the per-child arg-max mask (8 bytes per input row) for fc_maxpool8_mask_norm_act_bwd; argrow (nullable) only for a caller
+// that reads the arg-max rows itself.  C == 64: the mask word is 64 channels wide
+int fc_norm_act_maxpool8_mask_fwd(const float* x, const int* seg, int seg_stride, int C, const float* mean, const float* var, float eps,
+                                  const float* gamma, const float* beta, int act, const int* nbr, int64_t n_out, float* out,
+                                  int* argrow, float* y, int* parent, unsigned long long* mask, hipStream_t stream) {
+  unsigned* ao = take_amax_out();                // fc_amax_out_hint: max |out| into the caller's (zeroed) word
+  if (n_out < 0 || C != 64 || act < 0 || act > 2 || !parent || !mask) return FC_EINVAL;
+  if (n_out == 0) return FC_OK;
+  k_norm_act_maxpool8_fwd<true><<<FC_GRID(rows_launch(n_out, C), stream)>>>(x, seg, seg_stride, C, mean, var, eps, gamma, beta, act, nbr, n_out, out, argrow,
+                                                                           y, parent, mask, ao);
   FC_CHECK_LAUNCH();
   return FC_OK;
 }
@@ -317,8 +343,19 @@ int fc_maxpool8_norm_act_bwd(const float* x, const float* gout, const int* argro
                              const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
                              hipStream_t stream) {
   if (!parent || !argrow) return FC_EINVAL;
-  return norm_bwd<true>(FC_NFORM_SEG, x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, nullptr,
+  return norm_bwd<POOL_ARG>(FC_NFORM_SEG, x, nullptr, gout, nullptr, parent, argrow, seg, seg_stride, n_in, C, nseg, mean, var, cnt, eps, gamma, beta, act, gx, nullptr,
                         sums, nullptr, 0, 0, ws, ws_bytes, stream, nullptr);      // (the hint is not consumed)
+}
+
+// fc_maxpool8_norm_act_bwd reading the mask of fc_norm_act_maxpool8_mask_fwd where that reads the arg-max rows: the same route, launches and order of
+// every sum; the select has the same values, so gx and sums are its bits
+int fc_maxpool8_mask_norm_act_bwd(const float* x, const float* gout, const unsigned long long* mask, const int* parent, const int* seg,
+                                  int seg_stride, int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps,
+                                  const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
+                                  hipStream_t stream) {
+  if (!parent || !mask || C != 64) return FC_EINVAL;
+  return norm_bwd<POOL_MASK>(FC_NFORM_SEG, x, nullptr, gout, nullptr, parent, reinterpret_cast<const int*>(mask), seg, seg_stride, n_in, C, nseg, mean, var, cnt,
+                             eps, gamma, beta, act, gx, nullptr, sums, nullptr, 0, 0, ws, ws_bytes, stream, nullptr);      // (the hint is not consumed)
 }
 
 int fc_inverse_rows(const int* rows, int64_t n, int64_t n_inv, int* inv, hipStream_t stream) {

@@ -21,7 +21,8 @@ __global__ void k_bn1_partial(const float* __restrict__ x, int64_t n, int C, int
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t r = rb + (int64_t)u * nrl;
-      v[u] = r < r1 ? *reinterpret_cast<const float4*>(x + r * C + cl * 4) : sh;
+      // (a padding row re-reads row 0, which IS the shift: as `r < r1 ? load : sh` the compiler selects between two ADDRESSES and keeps sh on the stack)
+      v[u] = *reinterpret_cast<const float4*>(x + (r < r1 ? r : 0) * C + cl * 4);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {

@@ -52,20 +52,35 @@ __global__ void k_norm_act_fwd(const float* __restrict__ x, const int* __restric
 // row r's incoming gradient is gy[pool_parent[r]][c] where pool_arg[pool_parent[r]][c] == r, else 0: what fc_maxpool_bwd scatters into a
 // zeroed matrix, formed on the fly.  Only the loads differ: the sums run over the same rows in the same order, hence the same bits.
 // (A template parameter, not a run-time test: the plain instantiation is the kernel every other layer runs and keeps its code.)
-// (At the 128-register cap and spilling, profiles/r7_notes.md section 11: row_span moves its register allocation, so it keeps that text.)
-template <bool POOL>
-__global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gy,
+// POOL_MASK (r7, C == 64): pool_arg points at the per-child mask the forward kernel wrote instead (k_norm_act_maxpool8_fwd<true>), one 64-bit word
+// per INPUT row, bit c set exactly where pool_arg[pool_parent[r]][c] == r.  The select takes the same values, so the sums keep their bits; the
+// 16 gathered bytes of arg-max rows per float4 group become 4 linear ones (a lane reads the 32-bit half that holds its nibble).
+enum { POOL_NONE, POOL_ARG, POOL_MASK };
+__device__ __forceinline__ unsigned pool_mask_nibble(const int* __restrict__ pool_mask, int64_t r, int cl) {
+  return (reinterpret_cast<const unsigned*>(pool_mask)[2 * r + (cl >> 3)] >> ((cl & 7) * 4)) & 15u;
+}
+// v where keep, else +0.f — the value of `keep ? v : 0.f` as an AND on the bits: written as a select, the compiler turns the 16-byte row load behind it
+// into 12 bytes + a 4-byte load under the predicate, which waits for the predicate's own load before it is even issued
+__device__ __forceinline__ float keep_if(float v, bool keep) { return __uint_as_float(__float_as_uint(v) & (keep ? 0xffffffffu : 0u)); }
+// FROM_Y (act && y) / GY2 (gy2 != NULL), r7: whether the y and gy2 rows are read at all is compile-time too.  Four rows of every operand are in flight
+// per thread beside eight float4 accumulators; as run-time tests the kernel was allocated for the case that reads all four operands and spilled
+// in every case (168 / 220 bytes of scratch per lane under the 128-register cap of a kernel without a launch bound).  An instantiation now
+// holds the row registers it loads and no others; the bound tells the compiler the 256 threads it is launched with, and four waves per SIMD are
+// asked for because the grid (at most 1 024 blocks of 4 waves) is exactly one resident round at four and two rounds at fewer.  The forms that read
+// three row operands (gy2, or the pooled gather) keep a few spilled values in the segment loop and none in the row loop; the one that reads all four
+// (y and gy2, which the training step does not launch) has three spill instructions in the row loop as well (profiles/r7_notes.md section 12).
+template <int POOL, bool FROM_Y, bool GY2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_norm_bwd_partial(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gy,
                                    const float* __restrict__ gy2, const int* __restrict__ pool_parent,
-                                   const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C, int nseg,
+                                   const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C_rt, int nseg,
                                    const float* __restrict__ mean, const float* __restrict__ var, float eps, int act,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    int64_t rpb, float* __restrict__ part) {
+  const int C = POOL == POOL_MASK ? 64 : C_rt;      // (the mask form exists for 64 channels only: its row geometry folds into constants)
   extern __shared__ float sm[];               // [rl][2][C]
   __shared__ int srange[2];
   const auto [cl, rl, nrl] = lane_coord(C / 4);
-  const int64_t r0 = (int64_t)blockIdx.x * rpb;      // (a copy of row_span)
-  int64_t r1 = r0 + rpb;
-  if (r1 > n) r1 = n;
+  const auto [r0, r1] = row_span(rpb, n);
   int s_lo, s_hi;
   seg_range(seg, seg_stride, r0, r1, &s_lo, &s_hi, srange);
   // a row range inside ONE segment (almost every block: rows are nearly segment-contiguous) needs no per-row segment test —
@@ -82,12 +97,19 @@ __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __r
                               1.f / sqrtf(va.w + eps));
       const float4 gm = gamma ? *reinterpret_cast<const float4*>(gamma + cl * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
       const float4 bt = beta ? *reinterpret_cast<const float4*>(beta + cl * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const bool from_y = act && y;
       for (int64_t rb = r0 + rl; rb < r1; rb += 4 * nrl) {
         // branch-free batch: the 4 x (x, gy, y) rows are requested together (rows past the range re-read row r0 and are
         // dropped by `ok`), r3 — a `continue` in front of each load serialised them
         float4 xv[4], gv[4], yv[4], g2[4];
         bool ok[4];
+        int po[4];
+        if (POOL) {                              // the four parent rows first: the gathers wait for them, and one wait serves all four
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int64_t r = rb + (int64_t)u * nrl;
+            po[u] = pool_parent[r < r1 ? r : r0];
+          }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int64_t r = rb + (int64_t)u * nrl;
@@ -95,24 +117,31 @@ __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __r
           const int64_t rc = ok[u] ? r : r0;
           if (chk) ok[u] = ok[u] && seg[rc * seg_stride] == s;
           xv[u] = *reinterpret_cast<const float4*>(x + rc * C + cl * 4);
-          if (POOL) {
-            const int64_t o = pool_parent[rc];
+          if (POOL == POOL_MASK) {
+            const int64_t o = po[u];
+            const unsigned m = pool_mask_nibble(pool_arg, rc, cl);
+            gv[u] = *reinterpret_cast<const float4*>(gy + o * C + cl * 4);
+            gv[u].x = keep_if(gv[u].x, m & 1u); gv[u].y = keep_if(gv[u].y, m & 2u);
+            gv[u].z = keep_if(gv[u].z, m & 4u); gv[u].w = keep_if(gv[u].w, m & 8u);
+          } else if (POOL == POOL_ARG) {
+            const int64_t o = po[u];
             const int4 a = *reinterpret_cast<const int4*>(pool_arg + o * C + cl * 4);
             gv[u] = *reinterpret_cast<const float4*>(gy + o * C + cl * 4);
-            gv[u].x = a.x == rc ? gv[u].x : 0.f; gv[u].y = a.y == rc ? gv[u].y : 0.f;
-            gv[u].z = a.z == rc ? gv[u].z : 0.f; gv[u].w = a.w == rc ? gv[u].w : 0.f;
+            const int ri = (int)rc;            // (pool_arg names rows in 32 bits, so a pooled matrix has fewer than 2^31 of them)
+            gv[u].x = keep_if(gv[u].x, a.x == ri); gv[u].y = keep_if(gv[u].y, a.y == ri);
+            gv[u].z = keep_if(gv[u].z, a.z == ri); gv[u].w = keep_if(gv[u].w, a.w == ri);
           } else {
             gv[u] = *reinterpret_cast<const float4*>(gy + rc * C + cl * 4);
           }
-          if (gy2) g2[u] = *reinterpret_cast<const float4*>(gy2 + rc * C + cl * 4);
-          if (from_y) yv[u] = *reinterpret_cast<const float4*>(y + rc * C + cl * 4);
+          if (GY2) g2[u] = *reinterpret_cast<const float4*>(gy2 + rc * C + cl * 4);
+          if (FROM_Y) yv[u] = *reinterpret_cast<const float4*>(y + rc * C + cl * 4);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (!ok[u]) continue;
           float4 g = gv[u];
-          if (gy2) { g.x += g2[u].x; g.y += g2[u].y; g.z += g2[u].z; g.w += g2[u].w; }
-          if (from_y) {
+          if (GY2) { g.x += g2[u].x; g.y += g2[u].y; g.z += g2[u].z; g.w += g2[u].w; }
+          if (FROM_Y) {
             g.x *= act_bwd_from_y(yv[u].x, act); g.y *= act_bwd_from_y(yv[u].y, act);
             g.z *= act_bwd_from_y(yv[u].z, act); g.w *= act_bwd_from_y(yv[u].w, act);
           } else if (act) {
@@ -151,16 +180,17 @@ __global__ void k_norm_bwd_partial(const float* __restrict__ x, const float* __r
 }
 
 // backward pass 3:  gx = gamma*invstd*( g' - sum_g/cnt - xhat * sum_gx/cnt ) ; gres = g'
-// pool_parent / pool_arg: see k_norm_bwd_partial
-template <bool POOL>
+// pool_parent / pool_arg, POOL_MASK: see k_norm_bwd_partial
+template <int POOL>
 __global__ void k_norm_bwd_apply(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ gy,
                                  const float* __restrict__ gy2, const int* __restrict__ pool_parent,
-                                 const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C,
+                                 const int* __restrict__ pool_arg, const int* __restrict__ seg, int seg_stride, int64_t n, int C_rt,
                                  const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                  const float* __restrict__ sums /*[seg][2][C]*/,
                                  const float* __restrict__ cnt, int act, float* __restrict__ gx, float* __restrict__ gres,
                                  unsigned* __restrict__ amax_out) {
+  const int C = POOL == POOL_MASK ? 64 : C_rt;      // (see k_norm_bwd_partial)
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4n = C / 4;
   unsigned am = 0u;
@@ -171,7 +201,12 @@ __global__ void k_norm_bwd_apply(const float* __restrict__ x, const float* __res
   float inv_n = 1.f / cnt[s];
   float xv[4], gv[4], muv[4], vav[4], gam[4], bet[4] = {0.f, 0.f, 0.f, 0.f}, s1[4], s2[4], yv[4], o[4], gr[4];
   *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(x + r * C + c);
-  if (POOL) {
+  if (POOL == POOL_MASK) {
+    const int64_t o = pool_parent[r];
+    const unsigned m = pool_mask_nibble(pool_arg, r, c >> 2);
+    *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(gy + o * C + c);
+    gv[0] = (m & 1u) ? gv[0] : 0.f; gv[1] = (m & 2u) ? gv[1] : 0.f; gv[2] = (m & 4u) ? gv[2] : 0.f; gv[3] = (m & 8u) ? gv[3] : 0.f;
+  } else if (POOL == POOL_ARG) {
     const int64_t o = pool_parent[r];
     const int4 a = *reinterpret_cast<const int4*>(pool_arg + o * C + c);
     *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(gy + o * C + c);

@@ -2,11 +2,10 @@
 #pragma once
 
 // ---- pass 1: partial sums of f(x) per (block, segment, channel) --------------------------------
-// mode 0: sum x ; mode 1: sum (x-mean[seg])^2 ; mode 2 (r5): sum x AND sum x^2 in one pass, part layout [block][seg][2][C]
+// sq == false: sum x, part layout [block][seg][C] ; sq (r5): sum x AND sum x^2 in one pass, part layout [block][seg][2][C]
 // block = (C/4 lanes of float4) x (row lanes); C % 4 == 0, C <= 1024; rows [b*rpb, (b+1)*rpb)
 __global__ void k_stats_partial(const float* __restrict__ x, const int* __restrict__ seg, int seg_stride, int64_t n, int C,
-                                int nseg, const float* __restrict__ mean, int mode, int64_t rpb, float* __restrict__ part,
-                                float* __restrict__ part_cnt) {
+                                int nseg, bool sq, int64_t rpb, float* __restrict__ part, float* __restrict__ part_cnt) {
   extern __shared__ float sm[];               // [rl][C] staging for the cross-row-lane reduction
   __shared__ int srange[2];
   const int c4n = C / 4;
@@ -19,13 +18,11 @@ __global__ void k_stats_partial(const float* __restrict__ x, const int* __restri
   const bool chk = seg && s_lo != s_hi;
   for (int s = 0; s < nseg; ++s) {
     float4 acc[4];
-    float4 sq = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 sqs = make_float4(0.f, 0.f, 0.f, 0.f);
     float cnt = 0.f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (s >= s_lo && s <= s_hi) {
-      float4 mu = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (mode == 1) mu = *reinterpret_cast<const float4*>(mean + (int64_t)s * C + cl * 4);
       for (int64_t rb = r0 + rl; rb < r1; rb += 4 * nrl) {
         float4 vv[4];
         bool ok[4];
@@ -41,11 +38,7 @@ __global__ void k_stats_partial(const float* __restrict__ x, const int* __restri
         for (int u = 0; u < 4; ++u) {
           if (!ok[u]) continue;
           float4 v = vv[u];
-          if (mode == 1) {
-            v.x -= mu.x; v.y -= mu.y; v.z -= mu.z; v.w -= mu.w;
-            v.x *= v.x; v.y *= v.y; v.z *= v.z; v.w *= v.w;
-          }
-          if (mode == 2) { sq.x += v.x * v.x; sq.y += v.y * v.y; sq.z += v.z * v.z; sq.w += v.w * v.w; }
+          if (sq) { sqs.x += v.x * v.x; sqs.y += v.y * v.y; sqs.z += v.z * v.z; sqs.w += v.w * v.w; }
           acc[u].x += v.x; acc[u].y += v.y; acc[u].z += v.z; acc[u].w += v.w;
           cnt += 1.f;
         }
@@ -62,7 +55,7 @@ __global__ void k_stats_partial(const float* __restrict__ x, const int* __restri
     if (cl == 0) smc[rl] = cnt;
     __syncthreads();
     const int64_t slot = (int64_t)blockIdx.x * nseg + s;
-    float* dst = mode == 2 ? part + slot * 2 * C : part + slot * C;
+    float* dst = sq ? part + slot * 2 * C : part + slot * C;
     if (rl == 0) {
       float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int j = 0; j < nrl; ++j) {
@@ -76,9 +69,9 @@ __global__ void k_stats_partial(const float* __restrict__ x, const int* __restri
         part_cnt[slot] = c;
       }
     }
-    if (mode == 2) {                             // the squares through the same staging buffer
+    if (sq) {                                    // the squares through the same staging buffer
       __syncthreads();
-      *reinterpret_cast<float4*>(&sm[(rl * c4n + cl) * 4]) = sq;
+      *reinterpret_cast<float4*>(&sm[(rl * c4n + cl) * 4]) = sqs;
       __syncthreads();
       if (rl == 0) {
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -92,7 +85,7 @@ __global__ void k_stats_partial(const float* __restrict__ x, const int* __restri
   }
 }
 
-// r5: per-segment mean / biased variance / count from the one-pass partials of k_stats_partial mode 2 ([block][seg][2][C] +
+// r5: per-segment mean / biased variance / count from the one-pass partials of k_stats_partial with squares ([block][seg][2][C] +
 // counts [block][seg]): 4 channels x 64 slices per 256-thread block, fp64 accumulation in a fixed order (the instance norm of the
 // stem read its 148 MB input twice — mean, then centred squares — in four launches; now once, in two)
 static_assert(FIN_CB == 4 && FIN_SL == 64, "k_seg_meanvar_final spells out the 4 channels x 64 slices its launch (final_launch) gives it");
@@ -131,14 +124,10 @@ __global__ __launch_bounds__(256) void k_seg_meanvar_final(const float* __restri
   }
 }
 
-// ---- pass 2: sum partials over blocks (fixed order); block = 16 channels x 64 slices -----------------
-// mode 0: out = sum / cnt (mean), also writes cnt[seg];  mode 1: out = sum / cnt (biased variance); mode 2: out = sum
-// (FIN_CB channels x FIN_SL slices per block, 256 threads since r5: norm_route.h)
-__global__ __launch_bounds__(256) void k_stats_final(const float* __restrict__ part, const float* __restrict__ part_cnt,
-                                                      int64_t nblocks, int nseg, int C, int mode, float* __restrict__ out,
-                                                      float* __restrict__ cnt_io) {
+// ---- pass 2: out[seg][c] = the sum of part[block][seg][c] over the blocks (fixed order); block = FIN_CB channels x FIN_SL slices (256
+// threads since r5: norm_route.h)
+__global__ __launch_bounds__(256) void k_stats_final(const float* __restrict__ part, int64_t nblocks, int nseg, int C, float* __restrict__ out) {
   __shared__ float red[FIN_SL][FIN_CB + 1];
-  __shared__ float redc[FIN_SL];
   const int cgroups = (C + FIN_CB - 1) / FIN_CB;
   const int s = blockIdx.x / cgroups, cg = blockIdx.x % cgroups;
   const int cl = threadIdx.x & (FIN_CB - 1), j = threadIdx.x / FIN_CB;
@@ -147,34 +136,21 @@ __global__ __launch_bounds__(256) void k_stats_final(const float* __restrict__ p
   // summation order is fixed by the code, hence still deterministic
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   if (c < C) {
+    const float* p = part + (int64_t)s * C + c;      // (one block reads the table once: past the L1)
+    const int64_t st = (int64_t)nseg * C;
     int64_t b = j;
     for (; b + 3 * FIN_SL < nblocks; b += 4 * FIN_SL) {
-      const float v0 = fc_ld(&part[(b * nseg + s) * C + c]), v1 = fc_ld(&part[((b + FIN_SL) * nseg + s) * C + c]);      // (one block reads the
-      const float v2 = fc_ld(&part[((b + 2 * FIN_SL) * nseg + s) * C + c]), v3 = fc_ld(&part[((b + 3 * FIN_SL) * nseg + s) * C + c]);   //  table once: past the L1)
+      const float v0 = fc_ld(&p[b * st]), v1 = fc_ld(&p[(b + FIN_SL) * st]);
+      const float v2 = fc_ld(&p[(b + 2 * FIN_SL) * st]), v3 = fc_ld(&p[(b + 3 * FIN_SL) * st]);
       a0 += v0; a1 += v1; a2 += v2; a3 += v3;
     }
-    for (; b < nblocks; b += FIN_SL) a0 += fc_ld(&part[(b * nseg + s) * C + c]);
+    for (; b < nblocks; b += FIN_SL) a0 += fc_ld(&p[b * st]);
   }
-  float acc = (a0 + a1) + (a2 + a3);
-  red[j][cl] = acc;
-  if (mode == 0 && cl == 0) {
-    float cc = 0.f;
-    for (int64_t b = j; b < nblocks; b += FIN_SL) cc += fc_ld(&part_cnt[b * nseg + s]);
-    redc[j] = cc;
-  }
+  red[j][cl] = (a0 + a1) + (a2 + a3);
   __syncthreads();
   if (j == 0 && c < C) {
     float t = 0.f;
     for (int q = 0; q < FIN_SL; ++q) t += red[q][cl];
-    float cnt = 1.f;
-    if (mode == 0) {
-      float cc = 0.f;
-      for (int q = 0; q < FIN_SL; ++q) cc += redc[q];
-      if (c == 0) cnt_io[s] = cc;
-      cnt = cc;
-    } else if (mode == 1) {
-      cnt = cnt_io[s];
-    }
-    out[(int64_t)s * C + c] = (mode == 2) ? t : (cnt > 0.f ? t / cnt : 0.f);
+    out[(int64_t)s * C + c] = t;
   }
 }

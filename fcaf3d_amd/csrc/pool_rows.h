@@ -72,11 +72,16 @@ __global__ void k_maxpool_bwd(const float* __restrict__ gout, const int* __restr
 // (and y, when asked for) are bit for bit those of fc_norm_act_fwd + fc_maxpool_fwd.  The children of a pooled row lie in one
 // scene (seg of the first present child).  y (nullable): the normalised tensor itself — every child has one parent, so every
 // row is written once.  parent (nullable): parent[child row] = pooled row, for the backward pass (k_norm_bwd_* pool_parent).
+// MASK (C == 64: the 16 threads of a pooled row are adjacent lanes): mask[child row] = one 64-bit word, bit c set exactly where
+// argrow[pooled row][c] == child row, for the backward pass (norm_rows.h POOL_MASK), which then reads 8 linear bytes per input row instead
+// of gathering the arg-max rows; argrow may then be NULL and is not stored.  out, parent and the amax word are those of <false>.
+template <bool MASK>
 __global__ void k_norm_act_maxpool8_fwd(const float* __restrict__ x, const int* __restrict__ seg, int seg_stride, int C,
                                         const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                         const float* __restrict__ gamma, const float* __restrict__ beta, int act,
                                         const int* __restrict__ nbr, int64_t n_out, float* __restrict__ out, int* __restrict__ argrow,
-                                        float* __restrict__ y, int* __restrict__ parent, unsigned* __restrict__ amax_out) {
+                                        float* __restrict__ y, int* __restrict__ parent, unsigned long long* __restrict__ mask,
+                                        unsigned* __restrict__ amax_out) {
   const int c4n = C / 4;
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned am = 0u;
@@ -125,7 +130,28 @@ __global__ void k_norm_act_maxpool8_fwd(const float* __restrict__ x, const int* 
   }
   float4 ob = make_float4(arg[0] < 0 ? 0.f : best[0], arg[1] < 0 ? 0.f : best[1], arg[2] < 0 ? 0.f : best[2], arg[3] < 0 ? 0.f : best[3]);
   *reinterpret_cast<float4*>(out + o * C + c) = ob;
-  *reinterpret_cast<int4*>(argrow + o * C + c) = make_int4(arg[0], arg[1], arg[2], arg[3]);
+  if (!MASK || argrow) *reinterpret_cast<int4*>(argrow + o * C + c) = make_int4(arg[0], arg[1], arg[2], arg[3]);
+  if (MASK) {
+    // this lane's four channels: which child won each, a nibble per child slot k at bits 4k .. 4k + 3 (absent children and rows without
+    // children: 0)
+    unsigned won = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const unsigned nib = (unsigned)(arg[0] == idx[k]) | (unsigned)(arg[1] == idx[k]) << 1 | (unsigned)(arg[2] == idx[k]) << 2 |
+                           (unsigned)(arg[3] == idx[k]) << 3;
+      won |= (idx[k] < 0 ? 0u : nib) << (4 * k);
+    }
+    // lane k of the row's 16 stores child k's word, as the parent store above: bits 4L .. 4L + 3 are lane L's nibble of slot k.  (The 16
+    // lanes of a pooled row are all inside `t < n_out * c4n` or all outside, so every lane read is active.)
+    const int k = (c >> 2) & 7;
+    unsigned long long word = 0ull;
+#pragma unroll
+    for (int L = 0; L < 16; ++L) word |= (unsigned long long)((__shfl(won, L, 16) >> (4 * k)) & 15u) << (4 * L);
+    int mine = -1;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mine = (c == 4 * q) ? idx[q] : mine;
+    if (mine >= 0) mask[mine] = word;
+  }
   amax_fold(am, ob.x); amax_fold(am, ob.y); amax_fold(am, ob.z); amax_fold(am, ob.w);
   }
   if (amax_out) amax_commit(am, amax_out);

@@ -318,7 +318,7 @@ class NetProgram:
         maps[mn['stem']] = cm0.kernel_map(m1, 3).desc(conv=False)
         maps[mn['pool']] = m1.kernel_map(m2, 2).desc(conv=False)
         kms = {}
-        setd('n0', cm0.n); setd('n1', m1.n); setd('n2', m2.n); setd('B', batch_size); setd('one', 1)
+        setd('n0', cm0.n); setd('n1', m1.n); setd('n1w', 2 * m1.n); setd('n2', m2.n); setd('B', batch_size); setd('one', 1)
         prev, lv = m2, []
         for li in range(1, nl + 1):
             mi = prev.strided(2)
@@ -807,12 +807,17 @@ class _Emitter:
         t_in = p.T('n1', 64) if p.keep_state else -1
         if p.keep_state:
             p.relu_outs.append((t_in, 'n1', 64))
-        t_pool, arg = p.T('n2', 64), p.T('n2', 64)
+        # the arg-max rows (n2 x 64 ints): what an inference program's kernel stores, and what `decisions` reads (keep_state).  A training
+        # program's backward pass reads a per-child mask instead — one 64-bit word per n1 row, bit c set where arg[parent[r]][c] == r,
+        # written by the same forward kernel (norm.hip fc_norm_act_maxpool8_mask_fwd): two 4-byte words per row, the dimension 'n1w'
+        t_pool = p.T('n2', 64)
+        arg = p.T('n2', 64) if (p.keep_state or not tr) else -1
         p.pool_arg = (arg, 'n2', 64)
         ap = self.folded(t_pool)
         pool_parent = p.T('n1', 1) if tr else -1          # child row -> pooled row (4 bytes per row), for the backward pass
+        pool_mask = p.T('n1w', 1) if tr else -1
         p.emit(F, OP_NORM_POOL_FWD, S_MAIN, x=t_stem, seg=seg1, c=64, mean=mean_in, var=var_in, eps=_f(inorm.eps), gamma=p.S(inorm.weight),
-               beta=p.S(inorm.bias), act=relu, map=p.M('pool'), out=t_pool, arg=arg, y=t_in, amax_out=ap, parent=pool_parent)
+               beta=p.S(inorm.bias), act=relu, map=p.M('pool'), out=t_pool, arg=arg, y=t_in, amax_out=ap, parent=pool_parent, mask=pool_mask)
         if tr:
             p.in_sums = p.T('B', 2 * 64, 'b')
 
@@ -821,11 +826,11 @@ class _Emitter:
                 g_pool = self.grads.take(t_pool, 'n2', 64)
                 g_stem = p.T('n1', 64, 'b')
                 # pool backward + instance-norm backward without the scattered gradient in between: the normalisation backward's
-                # kernels read row r's gradient as g_pool[parent[r]] where arg[parent[r]] == r, else 0 (norm.hip pool_parent) — the sums
-                # in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
+                # kernels read row r's gradient as g_pool[parent[r]] where the mask's bit is set (arg[parent[r]] == r), else 0 (norm.hip
+                # pool_parent) — the sums in the order of OP_NORM_BWD, the same bits; y is not read (bn_pre recomputes act' from t_stem)
                 p.emit(self.Bk, OP_POOL_NORM_BWD, S_MAIN, x=t_stem, g_pool=g_pool, arg=arg, parent=pool_parent, seg=seg1, n=p.D('n1'), c=64,
                        nseg=p.D('B'), mean=mean_in, var=var_in, cnt=cnt_in, eps=_f(inorm.eps), gamma=p.S(inorm.weight),
-                       beta=p.S(inorm.bias), act=relu, gx=g_stem, sums=p.in_sums)
+                       beta=p.S(inorm.bias), act=relu, gx=g_stem, sums=p.in_sums, mask=pool_mask)
                 self.wgrad(S_MAIN, OP_STEM_WGRAD, col=col, gout=g_stem, map=p.M('stem'), gw=p.G(stem.kernel))
                 self.wrote(stem.kernel)
             self.tape.append(bwd)

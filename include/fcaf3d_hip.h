@@ -37,9 +37,10 @@ extern "C" {
  * fc_conv_wgrad_route added: the launch a convolution call becomes, as data), -> 11 (fc_bn_train_fwd_route / fc_bn_train_bwd_route
  * added: the launches a normalisation call becomes, as data), -> 12 (fc_eval_match / fc_eval_match_ws_bytes added: the matching
  * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss), -> 14
- * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch).  A caller built against
+ * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch), -> 15
+ * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask).  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 14
+#define FC_ABI_VERSION 15
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -485,6 +486,20 @@ int fc_maxpool8_norm_act_bwd(const float* x, const float* gout, const int* argro
                              int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt, float eps,
                              const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws, int64_t ws_bytes,
                              hipStream_t stream);
+
+/* The same pair (me_resnet.py:22-24) with a per-child arg-max MASK between the directions instead of the arg-max rows: mask (n_in 64-bit
+ * words, one per INPUT row r) has bit c set exactly where argrow[parent[r]][c] == r.  C must be 64 (anything else: -1); parent and mask are
+ * required.  Forward: out, parent, y and the amax word are those of fc_norm_act_maxpool8_fwd; argrow may be NULL and is then not stored.
+ * Backward: the launches, route (FC_NFORM_SEG over the n_in rows), workspace (fc_maxpool8_norm_act_bwd_ws_bytes) and summation order of
+ * fc_maxpool8_norm_act_bwd, and `bit ? gout[parent[r]][c] : 0` has the values of its arg-max comparison: gx and sums are bit for bit
+ * its.  Per input row the backward kernels read 8 linear bytes where they gathered 256 bytes of arg-max rows. */
+int fc_norm_act_maxpool8_mask_fwd(const float* x, const int* seg, int seg_stride, int C, const float* mean, const float* var, float eps,
+                                  const float* gamma, const float* beta, int act, const int* nbr, int64_t n_out, float* out,
+                                  int* argrow, float* y, int* parent, unsigned long long* mask, hipStream_t stream);
+int fc_maxpool8_mask_norm_act_bwd(const float* x, const float* gout, const unsigned long long* mask, const int* parent, const int* seg,
+                                  int seg_stride, int64_t n_in, int C, int nseg, const float* mean, const float* var, const float* cnt,
+                                  float eps, const float* gamma, const float* beta, int act, float* gx, float* sums, void* ws,
+                                  int64_t ws_bytes, hipStream_t stream);
 
 /* r7 — the neck's sparse sum `inputs[i] + x` (fcaf3d_neck_with_head.py:101) written by the normalisation that produces x: where
  * every row of inputs[i] lies in x's coordinate set the sum is x with inputs[i] added at rows[.].  fc_inverse_rows: inv (n_inv
