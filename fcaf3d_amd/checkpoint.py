@@ -43,12 +43,15 @@ def load_state_dict(module, state_dict, strict=False, logger=None):
 
 def load_checkpoint(model, filename, map_location=None, strict=False, logger=None,
                     revise_keys=((r'^module\.', ''),)):
-    """mmcv.runner.load_checkpoint(model, filename, map_location, strict, logger, revise_keys) -> checkpoint dict."""
+    """mmcv.runner.load_checkpoint(model, filename, map_location, strict, logger, revise_keys) -> checkpoint dict, with the report
+    of load_state_dict (unexpected / missing / mismatched keys) under 'load_report'."""
     checkpoint = torch.load(filename, map_location=map_location, weights_only=False)
     sd = _state_dict_of(checkpoint)
     for pat, rep in revise_keys:
         sd = OrderedDict((re.sub(pat, rep, k), v) for k, v in sd.items())
-    load_state_dict(model, sd, strict, logger)
+    report = load_state_dict(model, sd, strict, logger)
+    if isinstance(checkpoint, dict):
+        checkpoint['load_report'] = report
     return checkpoint
 
 

@@ -23,6 +23,7 @@ The module path stays the general route (and the cross-check of the tests: forwa
 program covers BasicBlock backbones (depth 14 / 18 / 34) with the FCAF3D neck when no pruning bites (`plan_maps` succeeded), the
 split-bf16 convolution route (FC_X6=1) and heads of at most 64 fused columns; anything else falls back.
 """
+import operator
 import os
 import struct
 
@@ -91,8 +92,9 @@ _FORWARD_SINGLE = _NECK_FORWARD = None       # set by fcaf3d_neck_with_head at i
 
 
 class NetProgram:
-    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None):
-        """keep_state (default: the module's KEEP_STATE now): the stem's normalised output is stored for `decisions`.
+    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None, frozen=-1):
+        """frozen: the backbone's frozen prefix of a training program (`frontier`: -1 none, 0 the stem, k the stem and layer1 .. layerk).
+        keep_state (default: the module's KEEP_STATE now): the stem's normalised output is stored for `decisions`.
         tail0: the finest neck level is PRUNED this step (`pts_threshold` bites there, fcaf3d_neck_with_head.py:110-126): the
         program ends at that level's union — `x0`, exported as a fourth differentiable output — and `_prune` + out_block_0 +
         forward_single of level 0 run on the per-operator path, attached by autograd (single_stage_sparse._exec_forward)"""
@@ -100,6 +102,7 @@ class NetProgram:
         self.tail0 = tail0
         self.keep_state = bool(KEEP_STATE if keep_state is None else keep_state)
         self.training = training
+        self.frozen = int(frozen) if training else -1
         self.wgrad_async = wgrad_async and training
         bb, nh = det.backbone, det.neck_with_head
         self.nl = min(bb.n_outs, 4)
@@ -230,11 +233,14 @@ class NetProgram:
         """the network as `extract_feat` runs it (me_resnet.py:14-50; fcaf3d_neck_with_head.py:94-108, :256-279): stem, backbone
         levels, then neck level i and the head of level i from the coarsest down; last the backward schedule"""
         bb, nh = self.det.backbone, self.det.neck_with_head
+        em.frozen = self.frozen >= 0
         x = em.stem(bb.conv1[0], bb.conv1[1])
         levels = []
         for li in range(1, self.nl + 1):
+            em.frozen = li <= self.frozen
             x = em.level(li, getattr(bb, f'layer{li}'), x)
             levels.append(x)
+        em.frozen = False
         self.out_idx = (self.T('Nall', 1), self.T('Nall', nh.n_reg_outs), self.T('Nall', nh.n_classes), self.T('Nall', 1))
         if self.training:
             em.tape.append(lambda: em.flush_small(S_MAIN))               # reversed walk: reached after the whole neck's backward
@@ -466,10 +472,11 @@ class NetProgram:
         addr[gi] = gbuf.data_ptr() + go
         desc = self._small.copy()
         desc[:, 1] = gbuf.data_ptr() + self._small_goff
-        r, C = self._small_in
-        B = int(dims[self.dim_names['B']])
-        desc[r, 0], desc[r + 1, 0] = addr[self.in_sums], addr[self.in_sums] + 4 * C
-        desc[r:r + 2, 3] = B
+        if self._small_in is not None:                      # (a frozen stem has no rows in the descriptor)
+            r, C = self._small_in
+            B = int(dims[self.dim_names['B']])
+            desc[r, 0], desc[r + 1, 0] = addr[self.in_sums], addr[self.in_sums] + 4 * C
+            desc[r:r + 2, 3] = B
         desc_dev = L.upload(desc, self.dev)
         addr[self.dyn['small_desc']] = desc_dev.data_ptr()
         gv = self._grad_views(gbuf)
@@ -616,6 +623,11 @@ class _Emitter:
         self.branch_params = {}          # level -> parameters whose gradient is written on S_HEAD by that branch
         self.flushed = 0                 # rows of p.small that an OP_SMALL_GRADS covers already
         self.producer = {}               # forward tensor -> (index of the OP_CONV that wrote it, rows, columns)
+        # the frontier of a fine-tuning program: a layer walked while `frozen` is set emits the rows an inference
+        # program emits for it and leaves nothing on the tape; a forward tensor NEEDS a gradient only if a trainable layer lies upstream
+        self.frozen = False
+        self.needs = set()
+        self.unjoined = []               # head branches whose neck tensor needs no gradient: nothing to deliver, joined at the end
         self.n_reg, self.n_cls, self.Cn = nh.n_reg_outs, nh.n_classes, nh.centerness_conv.in_channels
         self.n_heads = p.nl - (1 if p.tail0 else 0)
         self.head_partials = 0           # levels whose partial of the packed head kernel's gradient has been emitted
@@ -719,19 +731,26 @@ class _Emitter:
         ax = self.amax_fwd(x, rows_in, Cin, stream)
         p.emit(F, OP_CONV, stream, x=x, img=p.IMG(w, False), map=m, dir=0, out=y, n=n, cin=Cin, cout=Cout, amax_x=ax)
         self.producer[y] = (len(F) - 1, rows_out, Cout)
+        need_in = x in self.needs
+        if self.frozen:
+            assert not need_in and dense is None and not w.requires_grad
+            return y
 
         def bwd():
             gy = G.take(y, rows_out, Cout) if stream == S_MAIN else G.own(y)
-            gx = p.T(rows_in, Cin, 'b')
             ag = (self.amax_of[gy] if gy in self.amax_of else self.amax_op(Bk, stream, gy, rows_out, Cout)) if self.amax else -1
-            p.emit(Bk, OP_CONV, stream, x=gy, img=p.IMG(w, True), map=m, dir=1, out=gx, n=n, cin=Cout, cout=Cin, amax_x=ag)
-            G.src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
+            if need_in:                  # (an input behind the frontier: the weight gradient alone)
+                gx = p.T(rows_in, Cin, 'b')
+                p.emit(Bk, OP_CONV, stream, x=gy, img=p.IMG(w, True), map=m, dir=1, out=gx, n=n, cin=Cout, cout=Cin, amax_x=ag)
+                G.src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
             self.wgrad(stream, OP_WGRAD, x=x, gout=gy, map=m, gw=p.G(w) if gw is None else gw, n=n, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
             if gw is None:
                 self.wrote(w)
-            G.arrive(x, gx, rows_in, Cin, stream)
+            if need_in:
+                G.arrive(x, gx, rows_in, Cin, stream)
         if self.tr:
             self.tape.append(bwd)
+            self.needs.add(y)
         return y
 
     def bn(self, x, mod, act, rows, res=None, stream=S_MAIN, add=None):
@@ -739,7 +758,9 @@ class _Emitter:
         apply kernel also adds tensor[inverse[r]] to row r behind the activation (the neck's sparse sum) — y IS the sum then"""
         # ... which is legal because the layer's backward never reads y: without a residual act' is recomputed from x (y = -1 below)
         assert add is None or res is None
-        p, F, Bk, G, tr = self.p, self.F, self.Bk, self.grads, self.tr
+        p, F, Bk, G = self.p, self.F, self.Bk, self.grads
+        tr = self.tr and not self.frozen  # a frozen layer: the running statistics are the statistics, as in an inference program
+        assert tr or not self.tr or (x not in self.needs and (res is None or res not in self.needs))
         b, C = mod.bn, mod.bn.num_features
         y = p.T(rows, C)
         mean, var, cnt = (p.T('one', C), p.T('one', C), p.T('one', 1)) if tr else (-1, -1, -1)
@@ -789,12 +810,15 @@ class _Emitter:
             G.arrive(x, gx, rows, C, stream)
             if res is not None:
                 G.arrive(res, gres, rows, C, stream)
+        assert x in self.needs and (res is None or res in self.needs)
         self.tape.append(bwd)
+        self.needs.add(y)
         return y
 
     def stem(self, stem, inorm):
         """me_resnet.py conv1: the 3-channel convolution, instance norm + ReLU, max pool -> (tensor, rows, channels)"""
-        p, F, tr, relu = self.p, self.F, self.tr, Fn.ACT['relu']
+        p, F, relu = self.p, self.F, Fn.ACT['relu']
+        tr = self.tr and not self.frozen  # a frozen stem emits an inference program's rows: no col buffer, the arg-max rows, no mask
         x0, seg1 = p.DY('x0'), p.DY('seg1')
         t_stem = p.T('n1', 64)
         col = p.T('n1', 84) if tr else -1
@@ -834,6 +858,7 @@ class _Emitter:
                 self.wgrad(S_MAIN, OP_STEM_WGRAD, col=col, gout=g_stem, map=p.M('stem'), gw=p.G(stem.kernel))
                 self.wrote(stem.kernel)
             self.tape.append(bwd)
+            self.needs.add(t_pool)
         return t_pool, 'n2', 64
 
     def level(self, li, layer, x):
@@ -893,7 +918,7 @@ class _Emitter:
             gfb = p.T(fb_rows, Ci, 'b')
             p.emit(Bk, OP_GATHER, S_MAIN, src=gu, idx=rows_i, n=p.D(fb_rows), c=Ci, dst=gfb)
             G.arrive(fb, gfb, fb_rows, Ci, S_MAIN)
-        if tr:
+        if tr and fb in self.needs:                      # (a backbone tensor behind the frontier takes no share of the union's gradient)
             self.tape.append(bwd_union)
         return u, g_rows, Ci
 
@@ -964,9 +989,14 @@ class _Emitter:
                 self.flush_small(S_HEAD)                 # this branch's normalisation layer
                 self.branch = None
                 p.emit(Bk, OP_RECORD, S_HEAD, event=EV_HB + lvl)
-                self.grads.deliver(xt, lvl)
+                if xt in self.needs:
+                    self.grads.deliver(xt, lvl)
+                else:
+                    self.unjoined.append(lvl)
         for e in reversed(self.main):
             e()
+        for lvl in self.unjoined:                        # (its parameters' gradients are final once the main stream has joined it)
+            self.join(lvl)
         assert not self.grads.behind and not self.branch_params, 'a head branch was never joined'
         if not p.wgrad_async:
             # without the weight-gradient stream the partials were written on the streams of their levels (main, head): the
@@ -1037,6 +1067,9 @@ def program_for(det, training, tail0=False):
     nh = det.neck_with_head
     if tail0 and min(det.backbone.n_outs, 4) < 2:
         return None
+    front = frontier(det) if training else -1
+    if front is None:
+        return None
     key = (bool(training), bool(Fn.WGRAD_ASYNC), bool(nh.head_overlap), bool(tail0))
     keep = bool(KEEP_STATE)                    # the recorder flips it at run time: a program built without the stem's normalised output
                                                # must never be handed to `decisions`
@@ -1046,7 +1079,43 @@ def program_for(det, training, tail0=False):
     mode = Fn.split_mode() if Fn.X6 else -1
     cache = det.__dict__.setdefault('_programs', {})
     sig = NetProgram.signature(det)
-    prog = cache.get(key + (fuse, mode, keep))
+    prog = cache.get(key + (fuse, mode, keep, front))
     if prog is None or prog._sig != sig:
-        prog = cache[key + (fuse, mode, keep)] = NetProgram(det, *key, keep_state=keep)
+        prog = cache[key + (fuse, mode, keep, front)] = NetProgram(det, *key, keep_state=keep, frozen=front)
     return prog
+
+
+_FLAGS = (operator.attrgetter('requires_grad'), operator.attrgetter('training'))
+
+
+def frontier(det):
+    """the frozen prefix of the backbone that a TRAINING program of this detector stops its backward pass at, read from the
+    parameters' requires_grad and the modules' training flags as they are NOW (part of the program cache key: freezing a stage or
+    calling train() / eval() on it never meets a stale program):
+
+      -1   nothing is frozen (every parameter requires a gradient, every BatchNorm is in training mode): today's program
+       0   the stem is frozen (conv1.0's kernel, conv1.1's weight and bias)
+       k   the stem and layer1 .. layerk are frozen: none of their parameters requires a gradient and their BatchNorm are in eval mode
+     None  anything else — a frozen parameter behind a trainable one, an eval-mode BatchNorm in a trainable stage (`norm_eval`), a
+           frozen neck or head layer: no program, the module path takes the step (autograd handles what it can)
+
+    What is read per call is two tuples of flags; the verdict per pair of tuples is cached on the detector."""
+    lists = det.__dict__.get('_frontier_lists')
+    if lists is None:
+        bb = det.backbone
+        stages = [bb.conv1] + [getattr(bb, f'layer{i}') for i in range(1, min(bb.n_outs, 4) + 1)]
+        rest = [m for n, m in det.named_children() if m is not bb]
+        params = [list(s.parameters()) for s in stages] + [[q for m in rest for q in m.parameters()]]
+        norms = [[m for m in s.modules() if isinstance(m, MEnn.MinkowskiBatchNorm)] for s in stages] + \
+                [[m for r in rest for m in r.modules() if isinstance(m, MEnn.MinkowskiBatchNorm)]]
+        lists = det.__dict__['_frontier_lists'] = (params, norms, [q for g in params for q in g], [m for g in norms for m in g], {})
+    params, norms, all_p, all_n, verdicts = lists
+    flags = (tuple(map(_FLAGS[0], all_p)), tuple(map(_FLAGS[1], all_n)))
+    if flags in verdicts:
+        return verdicts[flags]
+    k = -1
+    while k + 1 < len(params) - 1 and not any(q.requires_grad for q in params[k + 1]) and not any(m.training for m in norms[k + 1]):
+        k += 1
+    ok = all(q.requires_grad for g in params[k + 1:] for q in g) and all(m.training for g in norms[k + 1:] for m in g)
+    v = verdicts[flags] = k if ok else None
+    return v

@@ -62,8 +62,40 @@ class MEResNet3D(ResNetBase):
              34: (MEnn.BasicBlock, (3, 4, 6, 3)), 50: (MEnn.Bottleneck, (4, 3, 6, 3)),
              101: (MEnn.Bottleneck, (3, 4, 23, 3))}
 
-    def __init__(self, in_channels, depth, n_outs=4):
+    def __init__(self, in_channels, depth, n_outs=4, frozen_stages=-1):
+        """frozen_stages (optional; the reference's config dicts build unchanged): mmdet's ResNet._freeze_stages / train(), third
+        party and not in the reference tree, restated for this backbone:
+
+          -1      nothing is frozen (the default: today's model, same parameters, names and state dict)
+           0      the stem: conv1.0's kernel and conv1.1's instance-norm weight and bias get requires_grad=False (an instance norm
+                  has no running statistics: its forward is unchanged)
+          k >= 1  additionally layer1 .. layerk: their parameters get requires_grad=False and the modules are KEPT in eval() by
+                  `train(mode)`, so their MinkowskiBatchNorm use the running statistics and do not update them
+
+        Values outside -1 .. min(n_outs, 4) raise ValueError.  (`norm_eval` for trainable stages and freezing neck or head layers
+        are not implemented.)"""
         if depth not in self._ARCH:
             raise ValueError(f'invalid depth={depth}')
         self.BLOCK, self.LAYERS = self._ARCH[depth]
         super().__init__(in_channels, n_outs)
+        if not isinstance(frozen_stages, int) or not -1 <= frozen_stages <= min(n_outs, 4):
+            raise ValueError(f'invalid frozen_stages={frozen_stages!r}: -1 .. {min(n_outs, 4)}')
+        self.frozen_stages = frozen_stages
+        self._freeze_stages()
+
+    def frozen_modules(self):
+        """the stem and the levels that `frozen_stages` freezes, in forward order"""
+        if self.frozen_stages < 0:
+            return []
+        return [self.conv1] + [getattr(self, f'layer{i}') for i in range(1, self.frozen_stages + 1)]
+
+    def _freeze_stages(self):
+        for m in self.frozen_modules():
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._freeze_stages()
+        return self

@@ -37,14 +37,21 @@ class FlatAdamW:
     interface the runner and the LR hook use: `param_groups`, `defaults`, `zero_grad`, `state_dict` / `load_state_dict` in
     torch's own layout (per-parameter `step`, `exp_avg`, `exp_avg_sq`), so mmcv-style checkpoints round-trip."""
 
-    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, multipliers=None):
+        """multipliers: one (lr_mult, decay_mult) per parameter of `flat`, in its order (param_multipliers); None: all 1"""
         self.flat = flat
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
-        self.param_groups = [dict(self.defaults, params=flat.params)]
+        self.param_groups = [dict(self.defaults, params=flat.params)]      # ONE schedule group: the LR hook scales every parameter alike
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.norm_clip = torch.zeros(2, dtype=torch.float32, device=flat.data.device)      # [global grad norm, clip coefficient]
         self.steps = 0
+        self.multipliers = [(float(a), float(b)) for a, b in multipliers] if multipliers is not None else [(1.0, 1.0)] * len(flat.params)
+        assert len(self.multipliers) == len(flat.params)
+        self.runs, self.table = None, None       # all ones: fc_adamw_step, as without multipliers
+        if any(mm != (1.0, 1.0) for mm in self.multipliers):
+            self.runs = group_runs(flat.offsets, self.multipliers)
+            self.table = torch.from_numpy(pack_runs(*self.runs, flat.n)).to(flat.data.device)      # uploaded once
 
     def zero_grad(self, set_to_none=True):
         for p in self.flat.params:
@@ -66,23 +73,51 @@ class FlatAdamW:
             ws = L.workspace(L.query('fc_grad_norm_ws_bytes', f.n), f.data.device)
             L.call('fc_grad_norm', L.ptr(f.grad), f.n, float(max_norm), L.ptr(self.norm_clip), L.ptr(ws), ws.numel(), L.stream())
             clip = self.norm_clip
-        L.call('fc_adamw_step', L.ptr(f.data), L.ptr(f.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), f.n, float(g['lr']),
-               float(b1), float(b2), float(g['eps']), float(g['weight_decay']), 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps,
-               L.ptr(clip), L.stream())
+        if self.table is None:
+            L.call('fc_adamw_step', L.ptr(f.data), L.ptr(f.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), f.n, float(g['lr']),
+                   float(b1), float(b2), float(g['eps']), float(g['weight_decay']), 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps,
+                   L.ptr(clip), L.stream())
+        else:
+            L.call('fc_adamw_step_groups', L.ptr(f.data), L.ptr(f.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), f.n, float(g['lr']),
+                   float(b1), float(b2), float(g['eps']), float(g['weight_decay']), 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps,
+                   L.ptr(clip), L.ptr(self.table), len(self.runs[0]), L.stream())
         return self.norm_clip[0].clone() if clip is not None else None      # a copy: norm_clip is rewritten by the next step
 
     def _views(self, buf):
         return [buf[o:o + p.numel()].view(p.shape) for p, o in zip(self.flat.params, self.flat.offsets)]
 
     def state_dict(self):
+        """torch's layout.  Without multipliers: one group over all parameters.  With them: one group per parameter carrying its
+        EFFECTIVE lr / weight_decay (what mmcv's constructor hands torch.optim.AdamW), so the file reads as the reference's would"""
         m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
         state = {i: dict(step=torch.tensor(float(self.steps)), exp_avg=m[i].clone(), exp_avg_sq=v[i].clone())
                  for i in range(len(m))} if self.steps else {}
         group = {k: val for k, val in self.param_groups[0].items() if k != 'params'}
-        group['params'] = list(range(len(self.flat.params)))
-        return dict(state=state, param_groups=[group])
+        if self.table is None:
+            return dict(state=state, param_groups=[dict(group, params=list(range(len(self.flat.params))))])
+        groups = [dict(group, lr=group['lr'] * a, weight_decay=group['weight_decay'] * b, params=[i])
+                  for i, (a, b) in enumerate(self.multipliers)]
+        return dict(state=state, param_groups=groups)
 
     def load_state_dict(self, sd):
+        """accepts one group over all parameters or one group per parameter; per-parameter rates that are not ONE base rate
+        times the configured multipliers raise (the checkpoint was written under another paramwise_cfg)"""
+        groups = sd['param_groups']
+        if len(groups) == 1:
+            base = dict(groups[0])
+        else:
+            if len(groups) != len(self.multipliers) or any(list(gr['params']) != [i] for i, gr in enumerate(groups)):
+                raise ValueError(f'optimizer state holds {len(groups)} parameter groups: expected 1, or one per parameter ({len(self.multipliers)})')
+            base = dict(groups[0])
+            for key, col in (('lr', 0), ('weight_decay', 1)):
+                pairs = list(zip(groups, self.multipliers))      # the base rate: a parameter with multiplier 1 holds it exactly
+                ref = next((gr[key] for gr, mm in pairs if mm[col] == 1.0),
+                           next((gr[key] / mm[col] for gr, mm in pairs if mm[col] > 0), self.param_groups[0][key]))
+                for i, (gr, mm) in enumerate(zip(groups, self.multipliers)):
+                    if abs(gr[key] - ref * mm[col]) > 1e-6 * max(abs(ref * mm[col]), abs(gr[key])):
+                        raise ValueError(f"optimizer state: parameter {i} has {key} {gr[key]!r}, the configured multipliers give "
+                                         f"{ref!r} x {mm[col]!r}: it was written under another paramwise_cfg")
+                base[key] = ref
         m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
         steps = 0
         with torch.no_grad():
@@ -93,27 +128,124 @@ class FlatAdamW:
                 v[int(i)].copy_(st['exp_avg_sq'])
                 steps = int(st['step'])
         self.steps = steps
-        for k, val in sd['param_groups'][0].items():
+        for k, val in base.items():
             if k != 'params':
                 self.param_groups[0][k] = tuple(val) if k == 'betas' else val
 
 
+def group_runs(offsets, multipliers):
+    """-> (begin, lr_mult, decay_mult): the maximal stretches of consecutive parameters with equal multipliers, each by the float
+    offset of its first parameter in the flat buffers"""
+    begin, lr, dec = [], [], []
+    for o, (a, b) in zip(offsets, multipliers):
+        if not begin or (a, b) != (lr[-1], dec[-1]):
+            begin.append(int(o)); lr.append(float(a)); dec.append(float(b))
+    return begin, lr, dec
+
+
+def pack_runs(begin, lr_mult, decay_mult, n):
+    """fc_adamw_groups_pack (csrc_post/optim_groups.hip, a pure host function): the validated run table as the kernel reads it
+    -> uint8 array.  ValueError on what the library refuses (include/fcaf3d_hip.h lists it)"""
+    import ctypes
+    R = len(begin)
+    b = np.ascontiguousarray(begin, dtype=np.int64)
+    a = np.ascontiguousarray(lr_mult, dtype=np.float32)
+    d = np.ascontiguousarray(decay_mult, dtype=np.float32)
+    out = np.zeros(max(int(L.lib().fc_adamw_groups_table_bytes(R)), 1), dtype=np.uint8)
+    rc = L.lib().fc_adamw_groups_pack(b.ctypes.data_as(ctypes.c_void_p), a.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
+                                      R, int(n), out.ctypes.data_as(ctypes.c_void_p), out.nbytes if R else 0)
+    if rc != 0:
+        raise ValueError(f'fc_adamw_groups_pack refused the run table (status {rc}): {R} runs over {n} floats, at most {MAX_RUNS} runs')
+    return out
+
+
+MAX_RUNS = 1024        # include/fcaf3d_hip.h FC_ADAMW_MAX_RUNS
+_PARAMWISE_KEYS = ('custom_keys', 'bias_lr_mult', 'bias_decay_mult', 'norm_decay_mult')
+
+
+def param_multipliers(model, paramwise_cfg):
+    """-> {parameter name: (lr_mult, decay_mult)} for every parameter of `model`: mmcv's DefaultOptimizerConstructor.add_params
+    (third party, not in the reference tree; the configs of configs/fcaf3d/ pass no paramwise_cfg).  The rule, restated:
+
+      custom_keys = {key: dict(lr_mult=1, decay_mult=1)}: of the keys that are SUBSTRINGS of the parameter's full name the longest
+          wins, ties broken alphabetically; its lr_mult / decay_mult (default 1) are the parameter's multipliers.
+      Only when no custom key matches:
+          bias_lr_mult      the learning rate of parameters named `bias` outside normalisation layers
+          norm_decay_mult   the weight decay of every parameter of a normalisation layer
+          bias_decay_mult   the weight decay of parameters named `bias` outside normalisation layers
+
+    A normalisation layer is what mmcv tests for: torch's _BatchNorm / _InstanceNorm / GroupNorm / LayerNorm — here the
+    nn.BatchNorm1d inside a MinkowskiBatchNorm.  MinkowskiInstanceNorm is a plain nn.Module to that test (as ME's is to mmcv), so
+    the stem's instance-norm `bias` takes the BIAS multipliers and its `weight` none.  Any other key of mmcv's constructor
+    (dwconv_decay_mult, dcn_offset_lr_mult, bypass_duplicate, ...) raises KeyError: no FCAF3D layer is of those kinds."""
+    cfg = dict(paramwise_cfg or {})
+    for k in cfg:
+        if k not in _PARAMWISE_KEYS:
+            raise KeyError(f'paramwise_cfg key {k!r} is not implemented ({", ".join(_PARAMWISE_KEYS)})')
+    custom = cfg.get('custom_keys') or {}
+    for k, val in custom.items():
+        for kk in val:
+            if kk not in ('lr_mult', 'decay_mult'):
+                raise KeyError(f'paramwise_cfg custom_keys[{k!r}] key {kk!r} is not implemented (lr_mult, decay_mult)')
+    keys = sorted(sorted(custom), key=len, reverse=True)
+    norms = (torch.nn.modules.batchnorm._BatchNorm, torch.nn.modules.instancenorm._InstanceNorm, torch.nn.GroupNorm, torch.nn.LayerNorm)
+    out = {}
+    for prefix, mod in model.named_modules():
+        is_norm = isinstance(mod, norms)
+        for name, _ in mod.named_parameters(recurse=False):
+            full = f'{prefix}.{name}' if prefix else name
+            if full in out:
+                continue
+            key = next((k for k in keys if k in full), None)
+            if key is not None:
+                out[full] = (float(custom[key].get('lr_mult', 1.0)), float(custom[key].get('decay_mult', 1.0)))
+                continue
+            lr_mult = decay_mult = 1.0
+            if name == 'bias' and not is_norm and cfg.get('bias_lr_mult') is not None:
+                lr_mult = float(cfg['bias_lr_mult'])
+            if is_norm:
+                if cfg.get('norm_decay_mult') is not None:
+                    decay_mult = float(cfg['norm_decay_mult'])
+            elif name == 'bias' and cfg.get('bias_decay_mult') is not None:
+                decay_mult = float(cfg['bias_decay_mult'])
+            out[full] = (lr_mult, decay_mult)
+    return out
+
+
 def build_optimizer(model, cfg, flat=None):
-    """cfg: the `optimizer` dict of a config (type AdamW / Adam / SGD, mmcv's constructor keys).  `flat`: the model's
-    FlatParams (GPU): AdamW then runs on the flat buffers (FlatAdamW)."""
+    """cfg: the `optimizer` dict of a config (type AdamW / Adam / SGD, mmcv's constructor keys; `paramwise_cfg`: per-parameter
+    multipliers, param_multipliers).  `flat`: the model's FlatParams (GPU): AdamW then runs on the flat buffers (FlatAdamW, which
+    keeps one schedule group and applies the multipliers in its kernel); the torch optimizers get one group per parameter with
+    lr = base * lr_mult and weight_decay = base * decay_mult, as mmcv builds them."""
     cfg = dict(cfg)
     kind = cfg.pop('type')
-    params = [p for p in model.parameters() if p.requires_grad]
+    paramwise = cfg.pop('paramwise_cfg', None)
+    if kind not in ('AdamW', 'Adam', 'SGD'):
+        raise KeyError(f'optimizer type {kind!r} is not used by any FCAF3D config')
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    params = [p for _, p in named]
+    mults = None
+    if paramwise:
+        by_name = param_multipliers(model, paramwise)
+        mults = {id(p): by_name[n] for n, p in named}
     fused = all(p.is_cuda for p in params)
     if kind == 'AdamW' and flat is not None:
-        return FlatAdamW(flat, **cfg)
+        return FlatAdamW(flat, multipliers=[mults[id(p)] for p in flat.params] if mults else None, **cfg)
+    if mults:
+        base_wd = cfg.get('weight_decay')
+        groups = []
+        for p in params:
+            a, b = mults[id(p)]
+            gr = dict(params=[p], lr=cfg['lr'] * a)
+            if base_wd is not None:
+                gr['weight_decay'] = base_wd * b
+            groups.append(gr)
+        params = groups
     if kind == 'AdamW':
         return torch.optim.AdamW(params, fused=fused, **cfg)
     if kind == 'Adam':
         return torch.optim.Adam(params, fused=fused, **cfg)
-    if kind == 'SGD':
-        return torch.optim.SGD(params, **cfg)
-    raise KeyError(f'optimizer type {kind!r} is not used by any FCAF3D config')
+    return torch.optim.SGD(params, **cfg)
 
 
 class StepLrUpdater:
@@ -434,7 +566,7 @@ def _save(model, tr, work_dir, epoch, it, seed, cfg_ck):
 
 
 def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=None, seed=0, device=None, max_gb=64.0, on_batch=None,
-        step=None):
+        step=None, load_from=None):
     """What the reference's tools/train.py does through mmdet3d/apis/train.py train_model: mmcv's EpochBasedRunner with its
     optimizer, LR, checkpoint, evaluation and text-logger hooks, for `cfg.runner.max_epochs` epochs.
 
@@ -445,6 +577,11 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                          grad_norm, time, data_time), read back from the device once per line
       resume_from        a checkpoint written here: model, optimizer, epoch and iteration continue where it stopped; the batches of
                          the remaining epochs are the straight run's (data.DeviceLoader draws by (seed, epoch, index))
+      load_from          (default cfg.load_from, configs/fcaf3d/fcaf3d.py:46) a checkpoint to FINE-TUNE from, as mmdet's
+                         train_detector treats it: resume_from wins when both are given; otherwise the weights alone are loaded
+                         with strict=False (a head of another n_classes is reported as mismatched and keeps its initialisation)
+                         BEFORE the TrainStep builds its flat buffers, the run starts at epoch 1, iteration 0 with a fresh
+                         optimizer, and the load report is written once to the log as a record with mode 'load'
 
     train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`).  Under
     torch.distributed every rank calls fit: the loaders shard, rank 0 alone writes files, evaluate gathers over the group.
@@ -462,6 +599,14 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     if val_loader is None and ev_interval > 0 and cfg.get('data', {}).get('val') is not None:
         vs = DT.build_dataset(cfg.data.val)
         val_loader = DT.DeviceLoader(DT.ResidentScenes(vs, device, max_gb), vs.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
+    if load_from is None:
+        load_from = cfg.get('load_from')
+    load_report = None
+    if load_from is not None and resume_from is None:
+        from .checkpoint import load_checkpoint
+        load_report = load_checkpoint(model, load_from, map_location=device, strict=False)['load_report']
+        if step is not None:
+            step.invalidate_images()
     if world > 1:
         for t in list(model.parameters()) + list(model.buffers()):
             torch.distributed.broadcast(t.data, 0)            # every rank starts from rank 0's weights, as DDP's constructor does
@@ -479,6 +624,9 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
         os.makedirs(work_dir, exist_ok=True)
         log_path = os.path.join(work_dir, time.strftime('%Y%m%d_%H%M%S') + '.log.json')
     log = _Log(log_path, (cfg.get('log_config') or {}).get('interval', 50))
+    if load_report is not None:
+        log.write(dict(mode='load', load_from=str(load_from), unexpected=list(load_report['unexpected']), missing=list(load_report['missing']),
+                       mismatched=[[k, list(a), list(b)] for k, a, b in load_report['mismatched']]))
     ck_cfg = cfg.get('checkpoint_config') or {}
     max_epochs = int(cfg.runner['max_epochs'])
     model.train()

@@ -38,9 +38,10 @@ extern "C" {
  * added: the launches a normalisation call becomes, as data), -> 12 (fc_eval_match / fc_eval_match_ws_bytes added: the matching
  * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss), -> 14
  * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch), -> 15
- * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask).  A caller built against
+ * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask), -> 16 (fc_adamw_groups_table_bytes /
+ * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers).  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 15
+#define FC_ABI_VERSION 16
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -693,6 +694,27 @@ int fc_grad_norm(const float* g, int64_t n, float max_norm, float* out, void* ws
 int fc_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, float bias_correction1, float bias_correction2, const float* norm_and_clip,
                   hipStream_t stream);
+
+/* AdamW with a learning-rate and a weight-decay multiplier per parameter: optimizer = dict(type='AdamW', lr=0.001,
+ * weight_decay=0.0001) (configs/fcaf3d/fcaf3d.py:30) with mmcv's paramwise_cfg on top.  mmcv's DefaultOptimizerConstructor is
+ * third party and no config of the tree passes a paramwise_cfg: No reference counterpart for the constructor; the rule is restated
+ * at runner.param_multipliers.  A RUN is a maximal stretch of consecutive parameters of the flat buffers with equal multipliers,
+ * given by the float offset of its first parameter.  fc_adamw_groups_pack (pure host function) validates R runs over buffers of n
+ * floats and packs them into `out` (fc_adamw_groups_table_bytes(R) bytes = 12 R; 0 for an R outside 1 .. FC_ADAMW_MAX_RUNS: R first
+ * 64-float slice indices, R rate multipliers, R decay multipliers), which the caller uploads once.  FC_EINVAL: begin[0] != 0,
+ * offsets not strictly ascending, an offset that is no multiple of 64 floats or is >= n, R < 1 or R > FC_ADAMW_MAX_RUNS, a
+ * multiplier that is negative or not finite, n % 4 != 0, n / 64 >= 2^32; FC_EWS: out_bytes too small. */
+#define FC_ADAMW_MAX_RUNS 1024
+int64_t fc_adamw_groups_table_bytes(int R);
+int fc_adamw_groups_pack(const int64_t* begin, const float* lr_mult, const float* decay_mult, int R, int64_t n, void* out,
+                         int64_t out_bytes);
+/* fc_adamw_step's pass (configs/fcaf3d/fcaf3d.py:30; same arithmetic, same 28 B per parameter, one launch) with lr * lr_mult[r]
+ * and weight_decay * decay_mult[r] for the run r a 16-byte vector lies in; table_dev: the packed table of fc_adamw_groups_pack on
+ * the device.  lr_mult == 0 leaves the run's parameters bit-unchanged while its moments advance; padding floats stay zero.  With
+ * every multiplier 1 the result is fc_adamw_step's (the host calls that one then).  No reference counterpart for the run lookup. */
+int fc_adamw_step_groups(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float bias_correction1, float bias_correction2, const float* norm_and_clip,
+                         const void* table_dev, int R, hipStream_t stream);
 
 /* SURVEY.md 8(f) rank 4 "bf16 fast mode" (No reference counterpart: the reference trains in fp32 throughout, configs/fcaf3d/fcaf3d.py:30-33
  * sets no fp16 hook).  A process-global, flagged NON-PARITY switch: while on, the split-bf16 convolution launches that read a
