@@ -42,6 +42,7 @@ def parse_header(path=HEADER):
 
 
 EXEC_OPS = os.path.join(_HERE, 'csrc', 'exec_ops.h')
+PLAN_LAYOUT = os.path.join(_HERE, 'csrc', 'plan_layout.h')      # the coordinate plan's tables (plan.py), in the same dialect
 
 
 def parse_enums(path=EXEC_OPS):

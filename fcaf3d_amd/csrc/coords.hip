@@ -7,6 +7,7 @@
 //   every ME.Minkowski* call in me_resnet.py:19-24,56-62 and fcaf3d_neck_with_head.py:52-71,
 //   fcaf3d_neck_with_head.py:101 (union), :115-116 (features_at_coordinates), :125 (pruning).
 #include "fc_common.h"
+#include "coord_rules.h"      // the rules this path shares with the native plan (plan.hip)
 
 extern "C" {
 
@@ -263,36 +264,14 @@ __global__ void k_table_init(unsigned long long* __restrict__ keys, int* __restr
   }
 }
 
-__device__ static inline int4 quantize(int4 c, int q) {
-  if (q > 1) {
-    c.y = fc_floor_div(c.y, q) * q;
-    c.z = fc_floor_div(c.z, q) * q;
-    c.w = fc_floor_div(c.w, q) * q;
-  }
-  return c;
-}
-
-// `bad` (nullable): set when a coordinate does not fit fc_pack's 16 bits per axis (with room for the largest kernel
-// offset) or the batch index its 16 bits — e.g. an inf / far-outlier point: such a key would alias another voxel.
+// `bad` (nullable): set when a coordinate is out of the range of the hash keys (fc_coord_out_of_range).
 __global__ void k_hash_insert(const int4* __restrict__ coords, int64_t n, int q, unsigned long long* keys, int* vals,
                               unsigned long long mask, int* __restrict__ slot, int* __restrict__ bad) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int4 c = quantize(coords[i], q);
-  if (bad && (c.x < 0 || c.x > 32767 || c.y < -FC_COORD_LIMIT || c.y > FC_COORD_LIMIT || c.z < -FC_COORD_LIMIT ||
-              c.z > FC_COORD_LIMIT || c.w < -FC_COORD_LIMIT || c.w > FC_COORD_LIMIT))
-    *bad = 1;
-  unsigned long long key = fc_pack(c.x, c.y, c.z, c.w);
-  unsigned long long h = fc_mix(key) & mask;
-  while (true) {
-    unsigned long long prev = atomicCAS(&keys[h], FC_EMPTY_KEY, key);
-    if (prev == FC_EMPTY_KEY || prev == key) {
-      atomicMin(&vals[h], (int)i);   // first occurrence (smallest row) wins — Appendix A.2
-      slot[i] = (int)h;
-      return;
-    }
-    h = (h + 1) & mask;
-  }
+  int4 c = fc_quantize(coords[i], q);
+  if (bad && fc_coord_out_of_range(c)) *bad = 1;
+  fc_hash_insert(keys, vals, mask, c, i, slot);
 }
 
 __global__ void k_flag_bad_count(const int* __restrict__ bad, int* __restrict__ n_out_dev) {
@@ -311,7 +290,7 @@ __global__ void k_unique_finalize(const int4* __restrict__ coords, int64_t n, in
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !flags[i]) return;
   int p = pos[i];
-  out_coords[p] = quantize(coords[i], q);
+  out_coords[p] = fc_quantize(coords[i], q);
   if (first_idx) first_idx[p] = (int)i;
   vals[slot[i]] = p;   // table now maps key -> row of the new coordinate set
 }

@@ -1,4 +1,4 @@
-"""The coordinate phase of one step through the two native calls of csrc/plan.hip (r6).
+"""The coordinate phase of one step through the two native calls of csrc/plan.hip (r6; their tables: csrc/plan_layout.h).
 
 `plan_step(det, points, ...)` replaces, for the standard FCAF3D topologies (BasicBlock backbone), what
 `SingleStageSparse3DDetector.voxelize` + `SparseTensor(...)` + `plan_maps` did with ~420 launches and ~25 blocking read-backs driven
@@ -21,20 +21,15 @@ import torch
 from . import _lib as L
 from . import sparse as SP
 
-# ---- layout of the native tables (csrc/plan.hip) --------------------------------------------------------------------------------
-C_B, C_NL, C_NFEAT, C_VS, C_FEATDIV, C_TOTAL, C_BACKWARD, C_SORT_MIN, C_PAIR_ROWS, C_PTS_THR, C_TARGETS, C_COORDS_IN, C_FEATS_IN, \
-    C_PT_STRIDE, C_NECK, C_VS_HEAD, C_PROBE = range(17)
-HDR = 16
-H_S, H_NEED2, H_PRUNE, H_NMAPS, H_STRUCT, H_NALL, H_F0, H_TGT_PTS, H_TGT_SCENE, H_TGT_LEVEL, H_TGT_ORDER, H_TGT_SEG, H_NHEAD, H_BAD = range(14)
-SETW, MAXSETS, MAPR, METAW, MAXLV = 8, 24, 64, 8, 8
-S_COORDS, S_N, S_STRIDE, S_KEYS, S_VALS, S_CAP, S_PARENT, S_ROWS = range(8)
-(MW_IN, MW_OUT, MW_K, MW_NIN, MW_NOUT, MW_NBR, MW_NBRT, MW_SORT, MW_SORTI, MW_SORTT, MW_SORTTI, MW_PI, MW_PO, MW_POS, MW_CNT, MW_TILES,
- MW_TPI, MW_TPO, MW_TPOS, MW_TCNT, MW_TTILES, MW_FLAGS) = range(22)
-MW_DESC_F, MW_DESC_B = 24, 44
+# ---- layout of the native tables: every word name (C_*, H_*, S_*, MW_*, MWF_*, META_*, CNT_*, PK_*, HDR, SETW, MAPR ...) is read from
+# csrc/plan_layout.h, the text csrc/plan.hip compiles; the descriptors inside a map record are sparse.MAPW words
+globals().update({k: v for block in L.parse_enums(L.PLAN_LAYOUT) for k, v in block.items()})
+_PAIR_LISTS = (SP.PAIR_IN, SP.PAIR_OUT, SP.PAIR_POS, SP.PAIR_CNT)      # the address words of a pair-list group (MW_PI .., MW_TPI ..)
 
 PROBE = False           # True: HIP-event brackets around every launch of the plans (fc_plan_probe_read; bench.py hbm_kernels)
 PROBE_KINDS = ('tables_init', 'collate_insert', 'flags_scan', 'finalize_insert', 'gen_coords', 'kernel_maps', 'children_maps', 'fill',
                'transpose', 'row_masks', 'radix_argsort', 'permute', 'pair_lists', 'union_rows', 'head_arrays')
+assert len(PROBE_KINDS) == PK_KINDS
 TRACE = None            # a list: (tag, perf_counter) marks of every plan (tools/hostprof.py --lookahead)
 ENABLED = True          # False: the per-operator coordinate phase (sparse.py), kept as the cross-check (tests/test_gpu_plan.py)
 
@@ -73,6 +68,11 @@ class StepPlan:
     __slots__ = ('x', 'sets', 'maps', 'head_maps', 'prune_level', 'targets', 'arenas', 'out', 'backward', 'structured', 'counts')
 
 
+def pinned_words(B, nl):
+    """ints of the pinned blocks: fc_plan_levels' counts; fc_plan_maps' counters of the most maps nl levels have + the staged segment starts"""
+    return (METAW + B) * (3 + nl) + PAD, CNT_MAP * (MAPS_FIXED + MAPS_PER_LEVEL * nl) + CNT_TAIL + nl * B + 1 + PAD
+
+
 class Planner:
     """per-detector state of the native plan: cfg words, pinned read-back buffers (one set per thread that plans)"""
 
@@ -82,12 +82,9 @@ class Planner:
 
     def _bufs(self, B, nl):
         t = self._tls
-        key = (B, nl)
-        if getattr(t, 'key', None) != key:
-            S = 3 + nl
-            t.key = key
-            t.counts = torch.zeros(METAW * S + S * B + 64, dtype=torch.int32).pin_memory()
-            t.cnt = torch.zeros(64 * (2 + 4 * nl) + MAXLV + nl * B + 1 + 64, dtype=torch.int32).pin_memory()
+        if getattr(t, 'key', None) != (B, nl):
+            t.key = (B, nl)
+            t.counts, t.cnt = (torch.zeros(n, dtype=torch.int32).pin_memory() for n in pinned_words(B, nl))
             t.out = np.zeros(L.lib().fc_plan_out_words(B, nl), dtype=np.int64)
             t.cfg = np.zeros(L.lib().fc_plan_cfg_words(), dtype=np.int64)
             t.scenes = np.zeros((max(B, 1), 3), dtype=np.int64)
@@ -202,11 +199,11 @@ class Planner:
             km = SP.KernelMap.__new__(SP.KernelMap)
             fl = int(o[MW_FLAGS])
             lazy = {'nbr': (int(o[MW_NBR]), (K, n_out), torch.int32)}
-            d = dict(n_in=n_in, n_out=n_out, K=K, sort_rows=bool(fl & 1), use_pairs=bool(fl & 2), _arenas=ar, _desc={})
-            conv = m >= 2
+            d = dict(n_in=n_in, n_out=n_out, K=K, sort_rows=bool(fl & MWF_SORT_ROWS), use_pairs=bool(fl & MWF_USE_PAIRS), _arenas=ar, _desc={})
+            conv = m >= MAPS_FIXED
             if conv:
                 if o[MW_PI]:
-                    lazy['_pairs'] = [(int(o[MW_PI + w]), (K, n_out) if w < 3 else (K,), torch.int32) for w in range(4)]
+                    lazy['_pairs'] = [(int(o[MW_PI + w]), (K,) if w == SP.PAIR_CNT else (K, n_out), torch.int32) for w in _PAIR_LISTS]
                     if n_out <= SP.PAIR_CONV_ROWS:
                         d['_tiles'] = int(o[MW_TILES])
                 else:
@@ -218,7 +215,7 @@ class Planner:
                 if backward:
                     lazy['_nbr_t'] = (int(o[MW_NBRT]), (K, n_in), torch.int32)
                     if o[MW_TPI]:
-                        lazy['_pairs_t'] = [(int(o[MW_TPI + w]), (K, n_in) if w < 3 else (K,), torch.int32) for w in range(4)]
+                        lazy['_pairs_t'] = [(int(o[MW_TPI + w]), (K,) if w == SP.PAIR_CNT else (K, n_in), torch.int32) for w in _PAIR_LISTS]
                         d['_tiles_t'] = int(o[MW_TTILES])
                     else:
                         d['_pairs_t'] = None
@@ -226,13 +223,13 @@ class Planner:
                         lazy['_sorted_t'] = [(int(o[MW_SORTT]), (K, n_in), torch.int32), (int(o[MW_SORTTI]), (n_in,), torch.int32)]
                     else:
                         d['_sorted_t'] = None
-                    d['_desc'][(True, True)] = o[MW_DESC_B:MW_DESC_B + 20]
+                    d['_desc'][(True, True)] = o[MW_DESC_B:MW_DESC_B + SP.MAPW]
                 else:
                     d.update(_nbr_t=None, _pairs_t=None, _sorted_t=None)
-                d['_desc'][(True, False)] = o[MW_DESC_F:MW_DESC_F + 20]
+                d['_desc'][(True, False)] = o[MW_DESC_F:MW_DESC_F + SP.MAPW]
             else:
                 d.update(_nbr_t=None, _pairs=None, _pairs_t=None, _sorted=None, _sorted_t=None)
-                d['_desc'][(False, True)] = d['_desc'][(False, False)] = o[MW_DESC_F:MW_DESC_F + 20]
+                d['_desc'][(False, True)] = d['_desc'][(False, False)] = o[MW_DESC_F:MW_DESC_F + SP.MAPW]
             d['_lazy'] = lazy
             km.__dict__.update(d)
             ks = {27: 3, 8: 2, 1: 1}[K]

@@ -163,22 +163,20 @@ int fc_gather_coords(const int* src, const int* idx, int64_t n, int* dst, hipStr
  * :56-62) in ONE call: points of B scenes -> the sets [cm0, m1, m2, L1..Lnl] (strides 1, 2, 4, 8 ...), each with its voxel hash,
  * rows in order of first occurrence, level 0 with its feature rows.  The chain runs with device-resident row counts; the call
  * ends with its single host read-back (rows per set, rows per set and scene, range flags) and fills `out`.
- *   cfg (fc_plan_cfg_words() int64): [0] B, [1] nl, [2] nfeat, [3] voxel size (double bits), [4] feature divisor (double bits),
- *     [5] total points, [6] backward tables wanted, [7] mask-sorted tables from this many rows, [8] pair-list convolution up to this
- *     many rows, [9] pts_threshold (-1: none), [10] head location arrays wanted, [11] / [12] pre-voxelised coords / feats (device
- *     pointers, 0 = collate from the points), [13] floats per point, [14] neck sets wanted, [15] the head's voxel size (double bits).
+ *   cfg (fc_plan_cfg_words() int64): the C_* words of fcaf3d_amd/csrc/plan_layout.h — sizes, voxel sizes (double bits), which tables
+ *     are wanted, the row thresholds of the convolution routes, pts_threshold, optional pre-voxelised input (device pointers).
  *   scenes: B x {device pointer, points, floats per point} (int64).  arena1: fc_plan_stage1_bytes bytes of device memory.
- *   counts_host: PINNED host ints, 8 (3 + nl) + (3 + nl) B.  out: fc_plan_out_words int64 (layout: csrc/plan.hip, fcaf3d_amd/plan.py).
+ *   counts_host: PINNED host ints, METAW (3 + nl) + (3 + nl) B.  out: fc_plan_out_words int64.  Every word of cfg, out, the counts and
+ * the counter block is declared in fcaf3d_amd/csrc/plan_layout.h (the text plan.hip compiles and fcaf3d_amd/plan.py reads).
  * fc_plan_maps, with those counts: every kernel map of the backbone and of the neck (fcaf3d_neck_with_head.py:52, :60-71, :101:
  * generated children sets and their maps by index arithmetic, union rows of the backbone levels), the derived tables of each
  * convolution route (mask-sorted tables, pair lists, transposed tables) and the head's location / scene / level arrays
  * (fcaf3d_neck_with_head.py:276-277) into arena2 (fc_plan_stage2_bytes), ending with ITS single read-back (pair-list counts, union
- * hits) into cnt_host (PINNED ints, 64 maps + 8 + nl B + 1).  Same sets, tables and row orders as the per-operator entry points above.
+ * hits) into cnt_host (PINNED ints, CNT_MAP maps + CNT_TAIL + nl B + 1).  Same sets, tables and row orders as the per-operator entry points above.
  * fc_argsort27: the stable argsort of 27-bit occupancy masks used for the mask-sorted tables (No reference counterpart).
- * cfg[16] != 0: every launch (group) of the two calls is bracketed with a HIP-event pair; fc_plan_probe_read(ms, bytes, kind, cap),
- * called after the device has drained, returns the brackets since the last read-out with their compulsory bytes and kind (0 tables,
- * 1 collate + insert, 2 winner flags + scan, 3 finalize + next insert, 4 generated coordinates, 5 kernel maps, 6 children maps, 7 fills,
- * 8 transposes, 9 row masks, 10 radix argsort, 11 permute, 12 pair lists, 13 union rows, 14 head arrays): bench.py's
+ * cfg[C_PROBE] != 0: every launch (group) of the two calls is bracketed with a HIP-event pair; fc_plan_probe_read(ms, bytes, kind, cap),
+ * called after the device has drained, returns the brackets since the last read-out with their compulsory bytes and kind (PK_* of
+ * plan_layout.h; fcaf3d_amd/plan.py PROBE_KINDS names them): bench.py's
  * `roofline.hbm_kernels` (the reference times whole iterations only: tools/analysis_tools/benchmark.py:64-91). */
 int fc_plan_cfg_words(void);
 int fc_plan_out_words(int B, int nl);

@@ -14,6 +14,11 @@ from fcaf3d_amd.synthetic import make_scene
 
 pytestmark = pytest.mark.gpu
 
+# words of a kernel-map descriptor (csrc/exec_ops.h, read by sparse.py) that hold a device address
+_PAIR_LISTS = (SP.PAIR_IN, SP.PAIR_OUT, SP.PAIR_POS, SP.PAIR_CNT)
+_ADDRESS_WORDS = {SP.MAP_NBR, SP.MAP_NBR_T, SP.MAP_FWD_TAB, SP.MAP_FWD_IDX, SP.MAP_BWD_TAB, SP.MAP_BWD_IDX} | \
+    {g + k for g in (SP.MAP_PAIRS, SP.MAP_PAIRS_T) for k in _PAIR_LISTS}
+
 
 def _dev():
     assert torch.cuda.is_available()
@@ -83,8 +88,12 @@ def _maps_eq(a, b, backward, what):
                 _eq(ia, ib, what + ' sorted_t order')
     for key in ((True, True), (True, False)) if backward else ((True, False),):
         da, db = a.desc(*key), b.desc(*key)
-        assert (da[0], da[1], da[2], da[13], da[18], da[19]) == (db[0], db[1], db[2], db[13], db[18], db[19]), (what, key, da, db)
-        assert [bool(v) for v in da[3:13]] == [bool(v) for v in db[3:13]], (what, key)
+        assert len(da) == len(db) == SP.MAPW
+        for w in range(SP.MAPW):            # the whole descriptor: addresses agree in null-ness, every other word is equal
+            if w in _ADDRESS_WORDS:
+                assert bool(da[w]) == bool(db[w]), (what, key, w, da, db)
+            else:
+                assert da[w] == db[w], (what, key, w, da, db)
 
 
 def _lookup_all(cm, q):
@@ -171,6 +180,69 @@ def test_native_plan_equals_the_per_operator_coordinate_phase(levels, seeds, n_p
             ta, tb = prep_a[2], prep_b[2]
             for k in ('pts', 'scene', 'ct', 'bt', 'labels', 'posf', 'inv_pos', 'inv_den'):
                 _eq(ta[k], tb[k], f'targets {k}')
+    torch.cuda.synchronize()
+
+
+def test_plan_made_descriptors_point_at_the_plans_own_tables():
+    """every word of the descriptors fc_plan_maps fills (csrc/plan.hip fill_descriptor) against the KernelMap accessor of that name:
+    two levels with the row thresholds at 4 096 put the five convolution maps on five different descriptor shapes"""
+    dev = _dev()
+    det = _build(levels=2).to(dev).train()
+    pts, gtb, gtl = _batch((51, 52), dev, 4000)
+    saved = SP.SORT_MIN_ROWS, SP.PAIR_CONV_ROWS
+    SP.SORT_MIN_ROWS = SP.PAIR_CONV_ROWS = 4096
+    try:
+        PL.ENABLED = False
+        try:
+            xa = det._sparse_input(pts, (gtb, gtl))
+            det.plan_maps(xa.cmap)
+        finally:
+            PL.ENABLED = True
+        _, ma, la = _walk(det, xa.cmap, True)
+        ga = la[-1].generate()
+        ref = dict(ma[2:] + [('gsame0', ga.kernel_map(ga, 3))])
+        det._sparse_input(pts, (gtb, gtl))
+        sp = det._step_plan
+        assert sp is not None and sp.structured and sp.backward
+        names = ['down1', 'ds1', 'same1', 'down2', 'ds2', 'same2', 'gsame0']
+        assert len(sp.maps) == 2 + len(names)
+        got = dict(zip(names, sp.maps[2:]))
+        FWD, BWD, WGRAD = SP.MAP_ROUTE_FWD_PAIRS, SP.MAP_ROUTE_BWD_PAIRS, SP.MAP_ROUTE_WGRAD_PAIRS
+        # (sort_rows, use_pairs, route bits of desc(True, True)): the shapes this test is about
+        want_route = dict(down1=(True, True, WGRAD), same1=(True, True, WGRAD), down2=(False, True, FWD | WGRAD),
+                          same2=(False, True, FWD | BWD | WGRAD), gsame0=(False, False, 0), ds1=(False, False, 0), ds2=(False, False, 0))
+        for name, km in got.items():
+            assert (km.sort_rows, km.use_pairs, int(km.desc(True, True)[SP.MAP_FLAGS])) == want_route[name], name
+        assert got['gsame0'].n_out == 8 * got['same2'].n_out > 4096 and got['down1'].n_in > got['down1'].n_out > 4096 > got['down2'].n_out
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else 0
+        for name, km in got.items():
+            for backward in (False, True):
+                d = km.desc(True, backward)
+                flags = int(d[SP.MAP_FLAGS])
+                assert flags == int(ref[name].desc(True, backward)[SP.MAP_FLAGS]), (name, backward)
+                want = np.zeros(SP.MAPW, dtype=np.int64)
+                want[SP.MAP_N_IN], want[SP.MAP_N_OUT], want[SP.MAP_K], want[SP.MAP_NBR] = km.n_in, km.n_out, km.K, km.nbr.data_ptr()
+                want[SP.MAP_FLAGS] = flags
+                if flags & FWD:
+                    want[SP.MAP_PAIRS + SP.PAIR_TILES] = km.pair_tiles()
+                else:
+                    want[SP.MAP_FWD_TAB], want[SP.MAP_FWD_IDX] = (ptr(t) for t in km.sorted_fwd())
+                if flags & (FWD | WGRAD):
+                    for k, t in zip(_PAIR_LISTS, km.pairs()):
+                        want[SP.MAP_PAIRS + k] = t.data_ptr()
+                if backward:
+                    want[SP.MAP_NBR_T] = km.nbr_t.data_ptr()
+                    if flags & BWD:
+                        for k, t in zip(_PAIR_LISTS, km.pairs_t()):
+                            want[SP.MAP_PAIRS_T + k] = t.data_ptr()
+                        want[SP.MAP_PAIRS_T + SP.PAIR_TILES] = km.pair_tiles(transposed=True)
+                    else:
+                        want[SP.MAP_BWD_TAB], want[SP.MAP_BWD_IDX] = (ptr(t) for t in km.sorted_bwd())
+                assert d.tolist() == want.tolist(), (name, backward, d, want)
+    finally:
+        SP.SORT_MIN_ROWS, SP.PAIR_CONV_ROWS = saved
     torch.cuda.synchronize()
 
 

@@ -271,6 +271,7 @@ DEVICE_IDENTICAL_SOURCES = {
     'be6908a911e0989e': '7094ae11604f2248',      # csrc/norm_route.h: every normalisation launch's route decided once, as data (host code only)
     '02ba23ed176093b4': '7094ae11604f2248',      # csrc/conv_tile.h: the kernels' shared tile prologue and weight-gradient decode; fp32 / stem kernels in headers of their own
     '2af8226cd1ab8dab': '7094ae11604f2248',      # csrc/norm_elem.h: the normalisation kernels' shared blocks; kernel families in headers of their own, norm.hip host only
+    'dce6dbc252e73433': 'f5479fc07ba0b2a4',      # csrc/plan_layout.h: the coordinate plan's table layouts declared once; plan kernels in headers by family, plan.hip host only
 }
 
 
