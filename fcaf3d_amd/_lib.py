@@ -64,7 +64,7 @@ def parse_enums(path=EXEC_OPS):
     return blocks
 
 
-ABI_VERSION = 16        # include/fcaf3d_hip.h FC_ABI_VERSION
+ABI_VERSION = 17        # include/fcaf3d_hip.h FC_ABI_VERSION
 _lib = None
 _protos = None
 
@@ -131,11 +131,11 @@ def header_enums():
 
 
 _ROUTE_FIELDS = {'fc_conv_fwd_route': 'FC_ROUTE_', 'fc_conv_wgrad_route': 'FC_WROUTE_', 'fc_bn_train_fwd_route': 'FC_NROUTE_',
-                 'fc_bn_train_bwd_route': 'FC_NROUTE_'}
+                 'fc_bn_train_bwd_route': 'FC_NROUTE_', 'fc_bn_eval_bwd_route': 'FC_NROUTE_'}
 
 
 def route(name, *args):
-    """fc_conv_fwd_route / fc_conv_wgrad_route / fc_bn_train_fwd_route / fc_bn_train_bwd_route(*args) -> (status, {field: value}),
+    """fc_conv_fwd_route / fc_conv_wgrad_route / fc_bn_train_fwd_route / fc_bn_train_bwd_route / fc_bn_eval_bwd_route(*args) -> (status, {field: value}),
     the fields under the header's FC_ROUTE_* / FC_WROUTE_* / FC_NROUTE_* names in lower case: the launch the matching
     entry point would make of that call (pure host functions)"""
     out = (ctypes.c_int * 16)()

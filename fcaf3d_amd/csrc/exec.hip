@@ -212,7 +212,7 @@ int run_op_impl(Ctx& c, const int64_t* op) {
     static const int ko = getenv("FC_KO_OPS") ? atoi(getenv("FC_KO_OPS")) : 0;
     const int64_t o = op[ROW_OP];
     if (!c.dry && (((ko & 1) && (o == OP_WGRAD || o == OP_STEM_WGRAD)) || ((ko & 2) && o == OP_CONV) ||
-                   ((ko & 4) && (o == OP_BN_FWD || o == OP_BN_BWD || o == OP_COL_STATS || o == OP_NORM_POOL_FWD || o == OP_POOL_NORM_BWD))))
+                   ((ko & 4) && (o == OP_BN_FWD || o == OP_BN_BWD || o == OP_BN_EVAL_BWD || o == OP_COL_STATS || o == OP_NORM_POOL_FWD || o == OP_POOL_NORM_BWD))))
       return 0;
   }
 #endif
@@ -385,6 +385,17 @@ int run_op_impl(Ctx& c, const int64_t* op) {
                              P<const float>(c, op[BN_BWD_BETA]), (int)op[BN_BWD_ACT], P<float>(c, op[BN_BWD_GX]),
                              P<float>(c, op[BN_BWD_GRES]), P<float>(c, op[BN_BWD_SUMS]), part, nbp, c.bn_small_elems, c.ws[s],
                              c.ws_bytes[s], st);
+    }
+    case OP_BN_EVAL_BWD: {
+      const int64_t n = c.dims[op[BN_EVAL_BWD_N]];
+      const int C = (int)op[BN_EVAL_BWD_C];
+      float* sums = P<float>(c, op[BN_EVAL_BWD_SUMS]);
+      if (!want_ws(c, s, fc_bn_eval_bwd_ws_bytes(n, C, op[BN_EVAL_BWD_SUMS] >= 0))) return 0;
+      return fc_bn_eval_bwd(P<const float>(c, op[BN_EVAL_BWD_X]), P<const float>(c, op[BN_EVAL_BWD_Y]), P<const float>(c, op[BN_EVAL_BWD_GY]),
+                            P1<const float>(c, op[BN_EVAL_BWD_GY2_P1]), n, C, P<const float>(c, op[BN_EVAL_BWD_RMEAN]),
+                            P<const float>(c, op[BN_EVAL_BWD_RVAR]), (float)as_double(op[BN_EVAL_BWD_EPS]), P<const float>(c, op[BN_EVAL_BWD_GAMMA]),
+                            P<const float>(c, op[BN_EVAL_BWD_BETA]), (int)op[BN_EVAL_BWD_ACT], P<float>(c, op[BN_EVAL_BWD_GX]),
+                            P<float>(c, op[BN_EVAL_BWD_GRES]), sums, P1<unsigned>(c, op[BN_EVAL_BWD_AMAX_GX_P1]), c.ws[s], c.ws_bytes[s], st);
     }
     case OP_STEM_WGRAD: {
       const int64_t* m = c.maps + op[STEM_WGRAD_MAP] * MAPW;

@@ -24,7 +24,8 @@ enum { ROW_OP, ROW_STREAM };     // the two words every row starts with
 enum {
   OP_STEM_FWD = 1, OP_COL_STATS, OP_NORM_FWD, OP_MAXPOOL_FWD, OP_CONV, OP_BN_FWD, OP_UNION_FWD, OP_HEAD_FWD, OP_RECORD, OP_WAIT,
   OP_HEAD_BWD, OP_WGRAD, OP_BN_BWD, OP_NORM_BWD, OP_MAXPOOL_BWD, OP_STEM_WGRAD, OP_GATHER, OP_ADD, OP_SMALL_GRADS,
-  OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD, OP_INV_ROWS
+  OP_PERMUTE_GENT, OP_HEAD_WFIN, OP_COPY, OP_COL_SUM, OP_ROW_SUM, OP_AMAX, OP_CLEAR, OP_NORM_POOL_FWD, OP_POOL_NORM_BWD, OP_INV_ROWS,
+  OP_BN_EVAL_BWD
 };
 
 // ---- operator fields
@@ -289,12 +290,32 @@ enum {  // inv = -1, inv[rows[i]] = i
   INV_ROWS_INV,
   INV_ROWS_END
 };
+enum {  // the backward through a BatchNorm that reads its running statistics (fc_bn_eval_bwd): one pass, no producer table
+  BN_EVAL_BWD_X = 2,
+  BN_EVAL_BWD_Y,            // the layer's output | -1 (no residual: act' is recomputed from X)
+  BN_EVAL_BWD_GY,
+  BN_EVAL_BWD_N,            // (dim)
+  BN_EVAL_BWD_C,
+  BN_EVAL_BWD_RMEAN,
+  BN_EVAL_BWD_RVAR,
+  BN_EVAL_BWD_EPS,          // (f64)
+  BN_EVAL_BWD_GAMMA,
+  BN_EVAL_BWD_BETA,
+  BN_EVAL_BWD_ACT,
+  BN_EVAL_BWD_GX,
+  BN_EVAL_BWD_GRES,         // | -1
+  BN_EVAL_BWD_SUMS,         // d beta, d gamma (2, C) | -1 (gamma and beta frozen: no sums, no workspace)
+  BN_EVAL_BWD_GY2_P1,       // a second gradient contribution, added on the fly
+  BN_EVAL_BWD_AMAX_GX_P1,
+  BN_EVAL_BWD_END
+};
 
 static_assert(STEM_FWD_END <= OPW && COL_STATS_END <= OPW && CONV_END <= OPW && BN_FWD_END <= OPW && HEAD_FWD_END <= OPW, "operator row");
 static_assert(RECORD_END <= OPW && WAIT_END <= OPW && HEAD_BWD_END <= OPW && WGRAD_END <= OPW && BN_BWD_END <= OPW, "operator row");
 static_assert(STEM_WGRAD_END <= OPW && GATHER_END <= OPW && ADD_END <= OPW && SMALL_GRADS_END <= OPW && PERMUTE_GENT_END <= OPW, "operator row");
 static_assert(HEAD_WFIN_END <= OPW && COPY_END <= OPW && COL_SUM_END <= OPW && ROW_SUM_END <= OPW && AMAX_END <= OPW, "operator row");
 static_assert(CLEAR_END <= OPW && NORM_POOL_FWD_END <= OPW && POOL_NORM_BWD_END <= OPW && INV_ROWS_END <= OPW, "operator row");
+static_assert(BN_EVAL_BWD_END <= OPW && OP_BN_EVAL_BWD == OP_INV_ROWS + 1, "operator row; existing opcodes keep their numbers");
 
 // ---- kernel-map descriptor (sparse.KernelMap.desc): device addresses as plain integers, 0 where a table is not built
 enum {  // one group of exact pair lists, relative to MAP_PAIRS / MAP_PAIRS_T

@@ -14,6 +14,7 @@
 #include "norm_stats.h"      // k_stats_partial, k_seg_meanvar_final, k_stats_final
 #include "norm_rows.h"       // k_norm_act_fwd, k_norm_bwd_partial, k_norm_bwd_apply
 #include "norm_bn.h"         // k_bn1_partial / _apply / _bwd_apply, k_bn_finalize, k_bn2_apply / _finalize, k_bn_running
+#include "norm_eval.h"     // k_bn_eval_bwd
 #include "pool_rows.h"       // k_maxpool_fwd / 8_fwd / _bwd, k_norm_act_maxpool8_fwd, k_inverse_rows, k_gather_rows, k_scatter_rows_add
 
 // ---- r6: max |.| of what a kernel writes, for the convolution that will gather it (csrc/conv_x6.h h3: the operand's scale) ----------
@@ -265,6 +266,39 @@ int fc_bn_train_bwd(const float* x, const float* y, const float* gy, const float
   unsigned* ao = take_amax_out();
   return norm_bwd<POOL_NONE>(FC_NFORM_TRAIN, x, y, gy, gy2, nullptr, nullptr, nullptr, 0, n, C, 1, mean, var, cnt, eps, gamma, beta, act, gx, gres, sums, part, nb_part,
                          small_elems, ws, ws_bytes, stream, ao);
+}
+
+// ---- eval-mode BatchNorm in a layer that trains: the backward with constant statistics (norm_eval.h) ----------------------------------
+int fc_bn_eval_bwd_route(int64_t n, int C, int want_sums, int* out) {
+  return out ? route_out(norm_eval_bwd_route(n, C, want_sums != 0), out) : FC_EINVAL;
+}
+int64_t fc_bn_eval_bwd_ws_bytes(int64_t n, int C, int want_sums) { return norm_eval_bwd_route(n, C, want_sums != 0).ws_bytes; }
+
+// sums (2, C) = [d beta, d gamma], NULL where gamma and beta are frozen; amax_gx (nullable): max |gx| into the caller's (zeroed) word
+int fc_bn_eval_bwd(const float* x, const float* y, const float* gy, const float* gy2, int64_t n, int C, const float* running_mean,
+                   const float* running_var, float eps, const float* gamma, const float* beta, int act, float* gx, float* gres,
+                   float* sums, unsigned* amax_gx, void* ws, int64_t ws_bytes, hipStream_t stream) {
+  if (act < 0 || act > 2) return FC_EINVAL;
+  const NormRoute r = norm_eval_bwd_route(n, C, sums != nullptr);
+  if (int rc = route_check(r, ws_bytes)) return rc;
+  if (r.apply == FC_NBAPPLY_NONE) {      // no rows
+    if (sums) FC_HIP(hipMemsetAsync(sums, 0, sizeof(float) * 2 * C, stream));
+    return FC_OK;
+  }
+  const bool from_y = act && y;
+#define FC_EVAL(Y, G2, S) \
+  k_bn_eval_bwd<Y, G2, S><<<FC_GRID(r.ap, stream)>>>(x, y, gy, gy2, n, C, running_mean, running_var, eps, gamma, beta, act, r.rpb, r.cg, gx, gres, (float*)ws, amax_gx)
+#define FC_EVAL_S(Y, G2) do { if (sums) FC_EVAL(Y, G2, true); else FC_EVAL(Y, G2, false); } while (0)
+  if (from_y) { if (gy2) FC_EVAL_S(true, true); else FC_EVAL_S(true, false); }
+  else { if (gy2) FC_EVAL_S(false, true); else FC_EVAL_S(false, false); }
+#undef FC_EVAL_S
+#undef FC_EVAL
+  FC_CHECK_LAUNCH();
+  if (sums) {
+    k_stats_final<<<FC_GRID(r.fin, stream)>>>((const float*)ws, r.np, 1, 2 * C, sums);
+    FC_CHECK_LAUNCH();
+  }
+  return FC_OK;
 }
 
 int fc_amax_out_hint(unsigned* amax_word) {

@@ -141,4 +141,31 @@ static inline NormRoute norm_bwd_route(int64_t n, int C, int nseg, bool has_part
   r.apply = FC_NBAPPLY_FINAL, r.fin = final_launch(nseg, 2 * C), r.ap = rows_launch(n, C);
   return r;
 }
+
+// fc_bn_eval_bwd: the backward through a BatchNorm that reads its running statistics (norm_eval.h).  gx needs no sum, so there is one pass over the
+// rows whatever the size.  want_sums false (gamma and beta frozen): k_bn_eval_bwd on the geometry of k_norm_act_fwd, no workspace.  want_sums: the
+// same kernel row-blocked as k_norm_bwd_partial (over channel windows where the row blocks are few, ap_window), leaving [nb][1][2][C] partial sums
+// that k_stats_final adds in a fixed order.  n == 0: nothing
+// but the zero fill of the sums.
+static inline NormRoute norm_eval_bwd_route(int64_t n, int C, bool want_sums) {
+  NormRoute r = {};
+  StatsGeometry g;
+  if (n < 0 || !stats_geometry(C, &g)) return r;
+  r.cg = C, r.amax = FC_NAMAX_FOLDED;
+  r.sums = want_sums ? FC_NRED_PARTIAL : FC_NRED_NONE;
+  if (n == 0) return r;      // (apply FC_NBAPPLY_NONE)
+  r.apply = FC_NBAPPLY_ROWS;
+  if (!want_sums) {
+    r.ap = rows_launch(n, C);
+    return r;
+  }
+  const RowBlocks b = row_blocks(n, MAXBLOCKS);
+  r.np = r.nb = b.nb, r.red_rpb = r.rpb = b.rpb;
+  r.cg = ap_window(n, C);      // few row blocks: a block owns 64 channels, grid.y walks the windows
+  stats_geometry(r.cg, &g);
+  r.ap = {(unsigned)b.nb, (unsigned)(C / r.cg), g.threads, g.lds_bwd};
+  r.fin = final_launch(1, 2 * C);
+  r.ws_bytes = reduce_ws_bytes(n, C, 1);
+  return r;
+}
 #endif

@@ -92,8 +92,11 @@ _FORWARD_SINGLE = _NECK_FORWARD = None       # set by fcaf3d_neck_with_head at i
 
 
 class NetProgram:
-    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None, frozen=-1):
+    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None, frozen=-1, plan=None):
         """frozen: the backbone's frozen prefix of a training program (`frontier`: -1 none, 0 the stem, k the stem and layer1 .. layerk).
+        plan: the verdict of `freeze_plan` this program was asked for (None: `frozen`).  Either only NAMES the program: what a layer
+        emits is read from its own flags as they are now (its kernel's requires_grad, its BatchNorm's mode), which the caller has checked
+        against the verdict.
         keep_state (default: the module's KEEP_STATE now): the stem's normalised output is stored for `decisions`.
         tail0: the finest neck level is PRUNED this step (`pts_threshold` bites there, fcaf3d_neck_with_head.py:110-126): the
         program ends at that level's union — `x0`, exported as a fourth differentiable output — and `_prune` + out_block_0 +
@@ -103,6 +106,7 @@ class NetProgram:
         self.keep_state = bool(KEEP_STATE if keep_state is None else keep_state)
         self.training = training
         self.frozen = int(frozen) if training else -1
+        self.plan = plan if training else None
         self.wgrad_async = wgrad_async and training
         bb, nh = det.backbone, det.neck_with_head
         self.nl = min(bb.n_outs, 4)
@@ -233,14 +237,11 @@ class NetProgram:
         """the network as `extract_feat` runs it (me_resnet.py:14-50; fcaf3d_neck_with_head.py:94-108, :256-279): stem, backbone
         levels, then neck level i and the head of level i from the coarsest down; last the backward schedule"""
         bb, nh = self.det.backbone, self.det.neck_with_head
-        em.frozen = self.frozen >= 0
         x = em.stem(bb.conv1[0], bb.conv1[1])
         levels = []
         for li in range(1, self.nl + 1):
-            em.frozen = li <= self.frozen
             x = em.level(li, getattr(bb, f'layer{li}'), x)
             levels.append(x)
-        em.frozen = False
         self.out_idx = (self.T('Nall', 1), self.T('Nall', nh.n_reg_outs), self.T('Nall', nh.n_classes), self.T('Nall', 1))
         if self.training:
             em.tape.append(lambda: em.flush_small(S_MAIN))               # reversed walk: reached after the whole neck's backward
@@ -250,7 +251,7 @@ class NetProgram:
                 x = em.up(i, getattr(nh, f'up_block_{i + 1}'), x, levels[i])
             if i == 0 and self.tail0:
                 self.x0_idx = x                             # the pruned level's tail runs outside the program
-                if self.training:
+                if self.training and x[0] in em.needs:
                     em.grads.arrive(x[0], self.DY('g_x0'), *x[1:], S_MAIN)       # ... and hands back d loss / d x0
             else:
                 em.head(i, getattr(nh, f'out_block_{i}'), x)
@@ -453,7 +454,8 @@ class NetProgram:
         base = (ba.data_ptr() + ALIGN - 1) // ALIGN * ALIGN
         self._fill_arena(addr, dims, 'b', base)
         for k, g in zip(('g_cent', 'g_bbox', 'g_cls', 'g_x0'), gs):
-            addr[self.dyn[k]] = g.data_ptr()
+            if k in self.dyn:                               # (g_x0: only where the union behind the pruned tail needs a gradient)
+                addr[self.dyn[k]] = g.data_ptr()
         ai, ap, ad, ab = self._al
         addr[ai] = addr[ap] + dims[ad] * ab
         own = self._own_params()
@@ -477,8 +479,9 @@ class NetProgram:
             B = int(dims[self.dim_names['B']])
             desc[r, 0], desc[r + 1, 0] = addr[self.in_sums], addr[self.in_sums] + 4 * C
             desc[r:r + 2, 3] = B
-        desc_dev = L.upload(desc, self.dev)
-        addr[self.dyn['small_desc']] = desc_dev.data_ptr()
+        if 'small_desc' in self.dyn:                         # (a head-only program has no normalisation layer in its backward list)
+            desc_dev = L.upload(desc, self.dev)
+            addr[self.dyn['small_desc']] = desc_dev.data_ptr()
         gv = self._grad_views(gbuf)
         if not accum:
             for p in own:                                   # before the operators run: a data-parallel bucket may leave mid-way
@@ -623,9 +626,9 @@ class _Emitter:
         self.branch_params = {}          # level -> parameters whose gradient is written on S_HEAD by that branch
         self.flushed = 0                 # rows of p.small that an OP_SMALL_GRADS covers already
         self.producer = {}               # forward tensor -> (index of the OP_CONV that wrote it, rows, columns)
-        # the frontier of a fine-tuning program: a layer walked while `frozen` is set emits the rows an inference
-        # program emits for it and leaves nothing on the tape; a forward tensor NEEDS a gradient only if a trainable layer lies upstream
-        self.frozen = False
+        # a fine-tuning program (DESIGN.md sections 18, 19), layer by layer: a forward tensor NEEDS a gradient only if a trainable layer lies
+        # upstream; a layer with nothing to train and an input nobody needs emits the rows an inference program emits for it and leaves
+        # nothing on the tape; a frozen layer on the gradient path emits its backward-data half alone
         self.needs = set()
         self.unjoined = []               # head branches whose neck tensor needs no gradient: nothing to deliver, joined at the end
         self.n_reg, self.n_cls, self.Cn = nh.n_reg_outs, nh.n_classes, nh.centerness_conv.in_channels
@@ -717,10 +720,11 @@ class _Emitter:
         self.wrote(nh.centerness_conv.kernel, nh.reg_conv.kernel, nh.cls_conv.kernel, nh.cls_conv.bias)
 
     # ---- layers ------------------------------------------------------------------------------------------------------------
-    def conv(self, x, rows_in, rows_out, mod=None, mname=None, dense=None, stream=S_MAIN):
+    def conv(self, x, rows_in, rows_out, mod=None, mname=None, dense=None, stream=S_MAIN, trainable=None):
         """one convolution launch and its backward.  Either MinkowskiConvolution `mod` on kernel map `mname`
         (functional._SparseConv), or dense = (weights, address index their gradient goes to): the GEMM (n, Cin) x (Cin, Cout) of
-        the generative transposed convolution and of the fused 1x1 heads"""
+        the generative transposed convolution and of the fused 1x1 heads.  trainable (default: the kernel's requires_grad; the packed
+        head GEMM always): the weight gradient is emitted iff it holds, the backward-data launch iff the input needs a gradient"""
         p, F, Bk, G = self.p, self.F, self.Bk, self.grads
         if dense is None:
             w, gw, Cin, Cout, m, n = mod.kernel, None, mod.in_channels, mod.out_channels, p.M(mname), -1
@@ -732,25 +736,26 @@ class _Emitter:
         p.emit(F, OP_CONV, stream, x=x, img=p.IMG(w, False), map=m, dir=0, out=y, n=n, cin=Cin, cout=Cout, amax_x=ax)
         self.producer[y] = (len(F) - 1, rows_out, Cout)
         need_in = x in self.needs
-        if self.frozen:
-            assert not need_in and dense is None and not w.requires_grad
+        if trainable is None:
+            trainable = mod.kernel.requires_grad if dense is None else True
+        if not (self.tr and (trainable or need_in)):
             return y
 
         def bwd():
             gy = G.take(y, rows_out, Cout) if stream == S_MAIN else G.own(y)
             ag = (self.amax_of[gy] if gy in self.amax_of else self.amax_op(Bk, stream, gy, rows_out, Cout)) if self.amax else -1
-            if need_in:                  # (an input behind the frontier: the weight gradient alone)
+            if need_in:                  # (an input nobody upstream needs: the weight gradient alone)
                 gx = p.T(rows_in, Cin, 'b')
                 p.emit(Bk, OP_CONV, stream, x=gy, img=p.IMG(w, True), map=m, dir=1, out=gx, n=n, cin=Cout, cout=Cin, amax_x=ag)
                 G.src[gx] = (len(Bk) - 1, rows_in, Cin, stream)
-            self.wgrad(stream, OP_WGRAD, x=x, gout=gy, map=m, gw=p.G(w) if gw is None else gw, n=n, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
-            if gw is None:
-                self.wrote(w)
+            if trainable:                # (a frozen kernel on the gradient path: the backward-data launch alone)
+                self.wgrad(stream, OP_WGRAD, x=x, gout=gy, map=m, gw=p.G(w) if gw is None else gw, n=n, cin=Cin, cout=Cout, amax_x=ax, amax_gout=ag)
+                if gw is None:
+                    self.wrote(w)
             if need_in:
                 G.arrive(x, gx, rows_in, Cin, stream)
-        if self.tr:
-            self.tape.append(bwd)
-            self.needs.add(y)
+        self.tape.append(bwd)
+        self.needs.add(y)
         return y
 
     def bn(self, x, mod, act, rows, res=None, stream=S_MAIN, add=None):
@@ -759,9 +764,10 @@ class _Emitter:
         # ... which is legal because the layer's backward never reads y: without a residual act' is recomputed from x (y = -1 below)
         assert add is None or res is None
         p, F, Bk, G = self.p, self.F, self.Bk, self.grads
-        tr = self.tr and not self.frozen  # a frozen layer: the running statistics are the statistics, as in an inference program
-        assert tr or not self.tr or (x not in self.needs and (res is None or res not in self.needs))
+        tr = self.tr and mod.training     # a layer in eval mode: the running statistics are the statistics, as in an inference program
         b, C = mod.bn, mod.bn.num_features
+        affine = b.weight.requires_grad
+        assert affine == b.bias.requires_grad and (affine or not tr), 'gamma and beta train together, and always in training mode'
         y = p.T(rows, C)
         mean, var, cnt = (p.T('one', C), p.T('one', C), p.T('one', 1)) if tr else (-1, -1, -1)
         if act == Fn.ACT['relu']:
@@ -781,10 +787,33 @@ class _Emitter:
                res=-1 if res is None else res, act=act, momentum=_f(b.momentum), y=y, mean=mean, var=var, cnt=cnt,
                rmean=p.S(b.running_mean), rvar=p.S(b.running_var), nbt=p.S(b.num_batches_tracked), train=1 if tr else 0,
                producer=prod, groups=groups, amax_y=ay, add_inv=add_inv, add_src=add_src)
-        if not tr:
+        need_x, need_res = x in self.needs, res is not None and res in self.needs
+        if not self.tr or not (tr or affine or need_x or need_res):
             return y
-        sums = torch.zeros((2, C), dtype=torch.float32, device=p.dev)
-        si = p.S(sums)
+        sums = torch.zeros((2, C), dtype=torch.float32, device=p.dev) if affine else None
+        si = p.S(sums) if affine else -1
+
+        def bwd_eval():
+            # eval mode in a layer on the gradient path (`norm_eval`, a frozen neck in front of a trainable backbone): the statistics are
+            # constants, gx needs no sum — one pass (csrc/norm_eval.h), no table from the backward-data convolution that wrote gy, and
+            # sums only where gamma / beta train
+            if affine:
+                p.small.append((sums.data_ptr(), None, C, b.weight, b.bias))
+            gy, gy2 = G.take(y, rows, C, pair=True) if stream == S_MAIN else (G.own(y), None)
+            gx = p.T(rows, C, 'b')
+            gres = p.T(rows, C, 'b') if res is not None else -1
+            agx = self.folded(gx) if need_x else -1
+            p.emit(Bk, OP_BN_EVAL_BWD, stream, x=x, y=y if res is not None else -1, gy=gy, n=p.D(rows), c=C, rmean=p.S(b.running_mean),
+                   rvar=p.S(b.running_var), eps=_f(b.eps), gamma=p.S(b.weight), beta=p.S(b.bias), act=act, gx=gx, gres=gres, sums=si,
+                   gy2=-1 if gy2 is None else gy2, amax_gx=agx)
+            if need_x:
+                G.arrive(x, gx, rows, C, stream)
+            if need_res:
+                G.arrive(res, gres, rows, C, stream)
+        if not tr:
+            self.tape.append(bwd_eval)
+            self.needs.add(y)
+            return y
 
         def bwd():
             p.small.append((sums.data_ptr(), None, C, b.weight, b.bias))
@@ -818,7 +847,8 @@ class _Emitter:
     def stem(self, stem, inorm):
         """me_resnet.py conv1: the 3-channel convolution, instance norm + ReLU, max pool -> (tensor, rows, channels)"""
         p, F, relu = self.p, self.F, Fn.ACT['relu']
-        tr = self.tr and not self.frozen  # a frozen stem emits an inference program's rows: no col buffer, the arg-max rows, no mask
+        tr = self.tr and stem.kernel.requires_grad       # a frozen stem emits an inference program's rows: no col buffer, the arg-max rows, no mask
+        assert not self.tr or inorm.weight.requires_grad == inorm.bias.requires_grad == stem.kernel.requires_grad
         x0, seg1 = p.DY('x0'), p.DY('seg1')
         t_stem = p.T('n1', 64)
         col = p.T('n1', 84) if tr else -1
@@ -894,12 +924,13 @@ class _Emitter:
         gw_i = p.S(gw_tmp)
 
         def bwd_perm():
-            p.emit(Bk, OP_PERMUTE_GENT, S_WGRAD if p.wgrad_async else S_MAIN, src=gw_i, dst=p.G(up[0].kernel), cin=x_C, cout=Ci)
-            self.wrote(up[0].kernel)
+            if up[0].kernel.requires_grad:
+                p.emit(Bk, OP_PERMUTE_GENT, S_WGRAD if p.wgrad_async else S_MAIN, src=gw_i, dst=p.G(up[0].kernel), cin=x_C, cout=Ci)
+                self.wrote(up[0].kernel)
             self.flush_small(S_MAIN)                     # ... and after every neck level's up-block
         if tr:
             self.tape.append(bwd_perm)                   # forward order: BEFORE the GEMM, so the reversed walk reaches it after
-        t = self.conv(x, x_rows, x_rows, dense=(p.gent_w[p.gents.index(up[0])], gw_i))
+        t = self.conv(x, x_rows, x_rows, dense=(p.gent_w[p.gents.index(up[0])], gw_i), trainable=up[0].kernel.requires_grad)
         t = self.bn(t, up[1], elu, g_rows)
         t = self.conv(t, g_rows, g_rows, up[3], _Names.gsame(i))
         # x = inputs[i] + t: every backbone voxel lies in the generated set -> the union IS the generated set (sparse.CoordMap.union)
@@ -918,7 +949,7 @@ class _Emitter:
             gfb = p.T(fb_rows, Ci, 'b')
             p.emit(Bk, OP_GATHER, S_MAIN, src=gu, idx=rows_i, n=p.D(fb_rows), c=Ci, dst=gfb)
             G.arrive(fb, gfb, fb_rows, Ci, S_MAIN)
-        if tr and fb in self.needs:                      # (a backbone tensor behind the frontier takes no share of the union's gradient)
+        if tr and fb in self.needs and u in self.needs:  # (a backbone tensor behind the frontier takes no share of the union's gradient; a union nobody needs has none)
             self.tape.append(bwd_union)
         return u, g_rows, Ci
 
@@ -1067,9 +1098,10 @@ def program_for(det, training, tail0=False):
     nh = det.neck_with_head
     if tail0 and min(det.backbone.n_outs, 4) < 2:
         return None
-    front = frontier(det) if training else -1
+    front = freeze_plan(det) if training else -1
     if front is None:
         return None
+    by_plan = not isinstance(front, int)       # a per-layer plan: the program is named by it, `frozen` then says the declared prefix
     key = (bool(training), bool(Fn.WGRAD_ASYNC), bool(nh.head_overlap), bool(tail0))
     keep = bool(KEEP_STATE)                    # the recorder flips it at run time: a program built without the stem's normalised output
                                                # must never be handed to `decisions`
@@ -1081,7 +1113,11 @@ def program_for(det, training, tail0=False):
     sig = NetProgram.signature(det)
     prog = cache.get(key + (fuse, mode, keep, front))
     if prog is None or prog._sig != sig:
-        prog = cache[key + (fuse, mode, keep, front)] = NetProgram(det, *key, keep_state=keep, frozen=front)
+        if by_plan:
+            prog = NetProgram(det, *key, keep_state=keep, frozen=getattr(det.backbone, 'frozen_stages', -1), plan=front)
+        else:
+            prog = NetProgram(det, *key, keep_state=keep, frozen=front)
+        cache[key + (fuse, mode, keep, front)] = prog
     return prog
 
 
@@ -1097,7 +1133,8 @@ def frontier(det):
        0   the stem is frozen (conv1.0's kernel, conv1.1's weight and bias)
        k   the stem and layer1 .. layerk are frozen: none of their parameters requires a gradient and their BatchNorm are in eval mode
      None  anything else — a frozen parameter behind a trainable one, an eval-mode BatchNorm in a trainable stage (`norm_eval`), a
-           frozen neck or head layer: no program, the module path takes the step (autograd handles what it can)
+           frozen neck or head layer: no frozen PREFIX.  `freeze_plan` then decides whether the pattern is one the model declared
+           (and the executor compiles) or the module path takes the step (autograd handles any pattern)
 
     What is read per call is two tuples of flags; the verdict per pair of tuples is cached on the detector."""
     lists = det.__dict__.get('_frontier_lists')
@@ -1119,3 +1156,48 @@ def frontier(det):
     ok = all(q.requires_grad for g in params[k + 1:] for q in g) and all(m.training for g in norms[k + 1:] for m in g)
     v = verdicts[flags] = k if ok else None
     return v
+
+
+def _declared_flags(det, lists):
+    """the flag tuples (`frontier`'s two) that the constructors' declarations imply after train(): backbone.frozen_stages / norm_eval,
+    neck_with_head.norm_eval / frozen_neck"""
+    params, norms, _, _, _ = lists
+    bb, nh = det.backbone, det.neck_with_head
+    k, ne_b = getattr(bb, 'frozen_stages', -1), bool(getattr(bb, 'norm_eval', False))
+    ne_n, fn = bool(getattr(nh, 'norm_eval', False)), bool(getattr(nh, 'frozen_neck', False))
+    neck = {id(q) for m in (nh.neck_blocks() if hasattr(nh, 'neck_blocks') else ()) for q in m.parameters()}
+    neck_norms = {id(m) for b in (nh.neck_blocks() if hasattr(nh, 'neck_blocks') else ()) for m in b.modules()}
+    rg = tuple(s > k for s, g in enumerate(params[:-1]) for _ in g) + tuple(not (fn and id(q) in neck) for q in params[-1])
+    tm = tuple(s > k and not ne_b for s, g in enumerate(norms[:-1]) for _ in g) + \
+        tuple(not ((fn or ne_n) and id(m) in neck_norms) for m in norms[-1])
+    return rg, tm
+
+
+def freeze_plan(det):
+    """what a TRAINING program of this detector is compiled for, or None (the module path takes the step):
+
+      an int     `frontier(det)` wherever that is not None: nothing frozen, or a frozen prefix of the backbone
+      a tuple    the current flag tuples (every parameter's requires_grad, every BatchNorm's mode — a per-layer plan, hashable, part of
+                 the program cache key) when they are exactly what the constructors' declarations imply after train():
+                 MEResNet3D(frozen_stages, norm_eval) and Fcaf3DNeckWithHead(norm_eval, frozen_neck) in any combination.  The emitter
+                 then reads each layer's own flags: an eval-mode BatchNorm on the gradient path runs OP_BN_EVAL_BWD (with sums only
+                 where gamma / beta train), a frozen convolution on it its backward-data launch alone, a layer behind which nothing
+                 trains an inference program's rows
+      None       anything set by hand that no declaration implies (a lone layer2.eval(), one frozen neck kernel), frozen head
+                 kernels or scales, a training-mode BatchNorm with frozen gamma / beta, a stem whose convolution and norm differ,
+                 Bottleneck depths: autograd on the module path handles any of these
+
+    Verdicts are cached per pair of tuples and declaration, as `frontier` caches its own."""
+    front = frontier(det)
+    if front is not None:
+        return front
+    lists = det.__dict__['_frontier_lists']
+    _, _, all_p, all_n, _ = lists
+    bb, nh = det.backbone, det.neck_with_head
+    flags = (tuple(map(_FLAGS[0], all_p)), tuple(map(_FLAGS[1], all_n)))
+    decl = (getattr(bb, 'frozen_stages', -1), getattr(bb, 'norm_eval', False), getattr(nh, 'norm_eval', False), getattr(nh, 'frozen_neck', False))
+    verdicts = det.__dict__.setdefault('_plan_verdicts', {})
+    if (flags, decl) not in verdicts:
+        ok = getattr(bb.BLOCK, 'expansion', 1) == 1 and _declared_flags(det, lists) == flags
+        verdicts[(flags, decl)] = flags if ok else None
+    return verdicts[(flags, decl)]

@@ -88,8 +88,25 @@ class Fcaf3DNeckWithHead(nn.Module):
                  loss_bbox=dict(type='IoU3DLoss', loss_weight=1.0),
                  loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
                  train_cfg=None,
-                 test_cfg=None):
+                 test_cfg=None,
+                 norm_eval=False,
+                 frozen_neck=False):
+        """norm_eval / frozen_neck (optional bools, anything else raises ValueError; the reference's config dicts build unchanged, with
+        the same parameters, names and state dict):
+
+          norm_eval    after `train(True)` every MinkowskiBatchNorm of up_block_* / out_block_* is in eval(): it reads its running
+                       statistics and leaves them alone, while the convolutions, gamma and beta keep training (MEResNet3D's switch)
+          frozen_neck  every parameter of up_block_* / out_block_* gets requires_grad=False and `train()` keeps those blocks in eval();
+                       centerness_conv, reg_conv, cls_conv and the scales stay trainable — with backbone.frozen_stages = n_outs this is
+                       head-only training
+
+        The native executor compiles both, in every combination with the backbone's declarations (executor.freeze_plan).  Freezing single
+        head kernels or scales, or flags set by hand that no declaration implies, train on the module path."""
         super().__init__()
+        for name, v in (('norm_eval', norm_eval), ('frozen_neck', frozen_neck)):
+            if not isinstance(v, bool):
+                raise ValueError(f'invalid {name}={v!r}: a bool')
+        self.norm_eval, self.frozen_neck = norm_eval, frozen_neck
         self.voxel_size = voxel_size
         self.yaw_parametrization = yaw_parametrization
         self.assigner = build_assigner(assigner)
@@ -101,6 +118,28 @@ class Fcaf3DNeckWithHead(nn.Module):
         self.pts_threshold = pts_threshold
         self.n_classes, self.n_reg_outs = n_classes, n_reg_outs
         self._init_layers(in_channels, out_channels, n_reg_outs, n_classes)
+        self._freeze_neck()
+
+    def neck_blocks(self):
+        """up_block_* and out_block_*, in definition order"""
+        return [m for n, m in self.named_children() if n.startswith(('up_block_', 'out_block_'))]
+
+    def _freeze_neck(self):
+        if self.frozen_neck:
+            for m in self.neck_blocks():
+                m.eval()
+                for p in m.parameters():
+                    p.requires_grad = False
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._freeze_neck()
+        if mode and self.norm_eval:
+            for blk in self.neck_blocks():
+                for m in blk.modules():
+                    if isinstance(m, MEnn.MinkowskiBatchNorm):
+                        m.eval()
+        return self
 
     # ---- module graph (reference :49-86; parameter names per SURVEY.md Appendix B) -----------------
     @staticmethod

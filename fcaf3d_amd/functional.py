@@ -377,18 +377,29 @@ class _NormAct(torch.autograd.Function):
     def backward(ctx, gy):
         x, y, g, mean, var, cnt, seg, b = ctx.saved_tensors
         nseg, eps, act, has_res, stats_const, gshape, bshape = ctx.cfg
+        if stats_const and nseg != 1:      # (before any launch; the model has no such layer)
+            raise RuntimeError('backward through eval-mode normalisation over segments is not supported')
         gy = gy.contiguous()
         n, C = x.shape
         dev = x.device
         gx = torch.empty_like(x)
         gres = torch.empty_like(x) if has_res else None
+        if stats_const:
+            # constant statistics (an eval-mode BatchNorm whose layer trains): one pass, gx needs no sum (csrc/norm_eval.h); the sums
+            # only where gamma or beta takes a gradient
+            want = (gshape is not None and ctx.needs_input_grad[1]) or (bshape is not None and ctx.needs_input_grad[2])
+            sums = torch.empty((2, C), dtype=torch.float32, device=dev) if want else None
+            ws = L.workspace(L.query('fc_bn_eval_bwd_ws_bytes', n, C, int(want)), dev)
+            L.call('fc_bn_eval_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), None, n, C, L.ptr(mean), L.ptr(var), eps, L.ptr(g), L.ptr(b), act,
+                   L.ptr(gx), L.ptr(gres), L.ptr(sums), None, L.ptr(ws), ws.numel(), L.stream())
+            ggamma = sums[1].reshape(gshape) if want and gshape is not None and ctx.needs_input_grad[1] else None
+            gbeta = sums[0].reshape(bshape) if want and bshape is not None and ctx.needs_input_grad[2] else None
+            return gx, ggamma, gbeta, gres, None, None, None, None, None, None, None, None
         sums = torch.empty((nseg, 2, C), dtype=torch.float32, device=dev)
         ws = L.workspace(L.query('fc_norm_act_bwd_ws_bytes', n, C, nseg), dev)
         L.call('fc_norm_act_bwd', L.ptr(x), L.ptr(y), L.ptr(gy), L.ptr(seg), 4 if seg is not None else 0, n, C, nseg,
                L.ptr(mean), L.ptr(var), L.ptr(cnt), eps, L.ptr(g), L.ptr(b), act, L.ptr(gx), L.ptr(gres), L.ptr(sums),
                L.ptr(ws), ws.numel(), L.stream())
-        if stats_const:
-            raise RuntimeError('backward through eval-mode normalisation is not supported')
         if nseg == 1:
             ggamma = sums[0, 1].reshape(gshape) if gshape is not None else None
             gbeta = sums[0, 0].reshape(bshape) if bshape is not None else None

@@ -62,7 +62,7 @@ class MEResNet3D(ResNetBase):
              34: (MEnn.BasicBlock, (3, 4, 6, 3)), 50: (MEnn.Bottleneck, (4, 3, 6, 3)),
              101: (MEnn.Bottleneck, (3, 4, 23, 3))}
 
-    def __init__(self, in_channels, depth, n_outs=4, frozen_stages=-1):
+    def __init__(self, in_channels, depth, n_outs=4, frozen_stages=-1, norm_eval=False):
         """frozen_stages (optional; the reference's config dicts build unchanged): mmdet's ResNet._freeze_stages / train(), third
         party and not in the reference tree, restated for this backbone:
 
@@ -72,15 +72,24 @@ class MEResNet3D(ResNetBase):
           k >= 1  additionally layer1 .. layerk: their parameters get requires_grad=False and the modules are KEPT in eval() by
                   `train(mode)`, so their MinkowskiBatchNorm use the running statistics and do not update them
 
-        Values outside -1 .. min(n_outs, 4) raise ValueError.  (`norm_eval` for trainable stages and freezing neck or head layers
-        are not implemented.)"""
+        Values outside -1 .. min(n_outs, 4) raise ValueError.
+
+        norm_eval (mmdet's switch of the same name; a bool, anything else raises ValueError): after `train(True)` EVERY MinkowskiBatchNorm of
+        the backbone is in eval() — it normalises with its running statistics and leaves them alone — while the convolutions, gamma and
+        beta outside the frozen prefix keep training (the backward through such a layer: csrc/norm_eval.h).  Parameters, their names and
+        the state dict are unchanged.
+
+        What the native executor compiles: every combination of the two arguments with BasicBlock depths (executor.freeze_plan); flags
+        set by hand that no declaration implies, and the Bottleneck depths, train on the module path."""
         if depth not in self._ARCH:
             raise ValueError(f'invalid depth={depth}')
         self.BLOCK, self.LAYERS = self._ARCH[depth]
         super().__init__(in_channels, n_outs)
         if not isinstance(frozen_stages, int) or not -1 <= frozen_stages <= min(n_outs, 4):
             raise ValueError(f'invalid frozen_stages={frozen_stages!r}: -1 .. {min(n_outs, 4)}')
-        self.frozen_stages = frozen_stages
+        if not isinstance(norm_eval, bool):
+            raise ValueError(f'invalid norm_eval={norm_eval!r}: a bool')
+        self.frozen_stages, self.norm_eval = frozen_stages, norm_eval
         self._freeze_stages()
 
     def frozen_modules(self):
@@ -98,4 +107,8 @@ class MEResNet3D(ResNetBase):
     def train(self, mode=True):
         super().train(mode)
         self._freeze_stages()
+        if mode and self.norm_eval:
+            for m in self.modules():
+                if isinstance(m, MEnn.MinkowskiBatchNorm):
+                    m.eval()
         return self

@@ -180,7 +180,7 @@ def run_sequential(seq, x):
             x = m(x, act=mods[i + 1].act)
             i += 2
         elif isinstance(m, _CONVS) and i + 1 < len(mods) and isinstance(mods[i + 1], MinkowskiBatchNorm):
-            x = m(x, want_stats=True)                  # the BatchNorm behind it takes its statistics from this launch's epilogue
+            x = m(x, want_stats=mods[i + 1].training)  # the BatchNorm behind it takes its statistics from this launch's epilogue (eval mode: none)
             i += 1
         else:
             x = m(x)
@@ -203,8 +203,8 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         residual = x if self.downsample is None else run_sequential(self.downsample, x)
-        out = self.norm1(self.conv1(x, want_stats=True), act='relu')
-        out = self.conv2(out, want_stats=True)
+        out = self.norm1(self.conv1(x, want_stats=self.norm1.training), act='relu')      # (a BatchNorm in eval mode reads no batch statistics)
+        out = self.conv2(out, want_stats=self.norm2.training)
         assert out.cmap is residual.cmap
         return self.norm2(out, act='relu', residual=residual.F)      # relu(bn(conv) + residual), one pass
 

@@ -39,9 +39,10 @@ extern "C" {
  * of indoor_eval on the device), -> 13 (fc_eiou3d_fwd_bwd added: the enclosing-box losses GIoU3DLoss / DIoU3DLoss), -> 14
  * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch), -> 15
  * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask), -> 16 (fc_adamw_groups_table_bytes /
- * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers).  A caller built against
+ * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers), -> 17 (fc_bn_eval_bwd / fc_bn_eval_bwd_ws_bytes /
+ * fc_bn_eval_bwd_route added: the backward through a BatchNorm that reads its running statistics).  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 16
+#define FC_ABI_VERSION 17
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -453,12 +454,30 @@ enum { FC_NFORM_TRAIN, FC_NFORM_SMALL, FC_NFORM_SEG };
 enum { FC_NSTATS_INVALID, FC_NSTATS_PROLOGUE, FC_NSTATS_PARTIAL_SMALL, FC_NSTATS_PARTIAL, FC_NSTATS_TABLE };
 enum { FC_NAPPLY_NONE, FC_NAPPLY_BN1, FC_NAPPLY_BN2, FC_NAPPLY_ROWS };
 enum { FC_NAMAX_NONE, FC_NAMAX_FOLDED, FC_NAMAX_PASS };
-enum { FC_NRED_INVALID, FC_NRED_TABLE, FC_NRED_PARTIAL };
-enum { FC_NBAPPLY_NONE, FC_NBAPPLY_PROLOGUE, FC_NBAPPLY_FINAL };
+enum { FC_NRED_INVALID, FC_NRED_TABLE, FC_NRED_PARTIAL, FC_NRED_NONE };
+enum { FC_NBAPPLY_NONE, FC_NBAPPLY_PROLOGUE, FC_NBAPPLY_FINAL, FC_NBAPPLY_ROWS };
 enum { FC_NROUTE_SUMS, FC_NROUTE_APPLY, FC_NROUTE_AMAX, FC_NROUTE_NP, FC_NROUTE_NB, FC_NROUTE_RPB, FC_NROUTE_CG, FC_NROUTE_THREADS, FC_NROUTE_LDS,
        FC_NROUTE_GRID_X, FC_NROUTE_GRID_Y, FC_NROUTE_WS_BYTES, FC_NROUTE_LAUNCHES };
 int fc_bn_train_fwd_route(int64_t n, int C, int has_part, int64_t nb_part, int groups, int64_t small_elems, int* out);
 int fc_bn_train_bwd_route(int64_t n, int C, int nseg, int has_part, int64_t nb_part, int64_t small_elems, int form, int* out);
+
+/* The backward through a BatchNorm in eval mode whose layer still trains (mmdet's norm_eval; ME.MinkowskiBatchNorm after .eval(),
+ * me_resnet.py:3, :56-63; fcaf3d_neck_with_head.py:53, :62, :68): y = act(xhat gamma + beta (+ res)), xhat = (x - running_mean) rstd,
+ * rstd = 1 / sqrt(running_var + eps), both statistics constants.  With g' = (gy (+ gy2)) act'(pre) — act' recomputed from x where y == NULL
+ * (no residual in the forward), else read from y, as fc_bn_train_bwd —: gx = g' gamma rstd, gres = g' (nullable), sums (2, C) = [d beta =
+ * sum g', d gamma = sum g' xhat].  gx depends on neither sum, so the rows are read ONCE, by one kernel.
+ * sums == NULL (gamma and beta frozen): pure elementwise, one launch, no workspace.  sums != NULL: the same pass leaves per-row-block
+ * partial sums in ws (fc_bn_eval_bwd_ws_bytes) and a second launch adds them in a fixed order — no float atomics, bit-reproducible.
+ * amax_gx (nullable): max |gx| folded into the caller's zeroed FC_AMAX_SLOT_BYTES slot, for the convolution that gathers gx.
+ * n == 0: FC_OK, sums zero-filled, nothing else launched.  n < 0, C < 4, C % 4, C > 1024, act outside 0..2: FC_EINVAL; a short workspace:
+ * FC_EWS; nothing is launched on a refused call.  fc_bn_eval_bwd_route: the route as data, out[] as fc_bn_train_bwd_route (FC_NROUTE_*):
+ * sums FC_NRED_PARTIAL or FC_NRED_NONE, apply FC_NBAPPLY_ROWS (FC_NBAPPLY_NONE: no rows), row blocks / rows per block of the row-blocked
+ * pass, threads / LDS / grid of the kernel, the workspace bytes the entry point checks, the launches. */
+int fc_bn_eval_bwd(const float* x, const float* y, const float* gy, const float* gy2, int64_t n, int C, const float* running_mean,
+                   const float* running_var, float eps, const float* gamma, const float* beta, int act, float* gx, float* gres,
+                   float* sums, unsigned* amax_gx, void* ws, int64_t ws_bytes, hipStream_t stream);
+int64_t fc_bn_eval_bwd_ws_bytes(int64_t n, int C, int want_sums);
+int fc_bn_eval_bwd_route(int64_t n, int C, int want_sums, int* out);
 
 /* ME.MinkowskiMaxPooling(k=2,s=2) — me_resnet.py:24. */
 int fc_maxpool_fwd(const float* in, const int* nbr, int64_t n_out, int K, int C, float* out, int* argrow,

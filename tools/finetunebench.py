@@ -1,8 +1,10 @@
-"""What fine-tuning costs on the chip (tools/, not product), on bench.py's primary shape, in ONE process:
+"""What fine-tuning costs on the chip (tools/, not product; DESIGN.md sections 18, 19), on bench.py's primary shape, in ONE process:
 
   * ms per training step and the number of backward operator rows for backbone.frozen_stages = -1, 0, 1, 2, 4: alternating
     windows (one variant after the other, `--rounds` times), each window behind its own warm-up steps, and the -1 variant TWICE per
     round — the distance between its two windows is the spread a difference has to exceed;
+  * in the same window scheme (section 19): `norm_eval` on the backbone, `norm_eval` on backbone and neck, and
+    frozen_stages = 4 with `frozen_neck` (head only) — with the launches of their backward lists by operator;
   * the optimizer pass alone, by HIP events, on the flat buffers of the benchmark's detector (70 M floats): fc_adamw_step against
     fc_adamw_step_groups with all-ones multipliers (one run) and with the README's recipe (custom_keys backbone lr_mult 0.1,
     norm_decay_mult 0), the plain entry twice per round for its own spread.
@@ -36,12 +38,18 @@ def pop(flag, default):
     return default
 
 
-def build(args, dev, frozen):
+def build(args, dev, frozen, norm_eval=(False, False), frozen_neck=False):
     import fcaf3d_amd as fa
     cfg = fa.get_config(bench.CONFIG_OF[args.workload], voxel_size=args.voxel_size)
     m = cfg.model
     if frozen >= 0:
         m.backbone['frozen_stages'] = frozen
+    if norm_eval[0]:
+        m.backbone.update(norm_eval=True)
+    if norm_eval[1]:
+        m.neck_with_head.update(norm_eval=True)
+    if frozen_neck:
+        m.neck_with_head.update(frozen_neck=True)
     torch.manual_seed(0)
     model = fa.build_detector(m, train_cfg=m.get('train_cfg'), test_cfg=m.get('test_cfg')).to(dev).train()
     model.async_maps = True
@@ -62,10 +70,12 @@ def main():
     Fn.WGRAD_ASYNC = True
     batches = bench.make_batches(args, 0, dev)
     R.reserve_device_memory(args.reserve_gb, dev)
-    variants = [('-1', -1), ('-1 again', -1), ('0', 0), ('1', 1), ('2', 2), ('4', 4)]
+    variants = [('-1', -1), ('-1 again', -1), ('0', 0), ('1', 1), ('2', 2), ('4', 4),
+                ('norm_eval backbone', (-1, (True, False), False)), ('norm_eval backbone + neck', (-1, (True, True), False)),
+                ('4 + frozen_neck (head only)', (4, (False, False), True))]
     runs = {}
     for name, k in variants:
-        model, tr = build(args, dev, k)
+        model, tr = build(args, dev, *(k if isinstance(k, tuple) else (k,)))
         runs[name] = dict(model=model, tr=tr, ms=[], i=0)
 
     def steps(r, n):
@@ -83,13 +93,14 @@ def main():
             torch.cuda.synchronize()
             r['ms'].append((time.perf_counter() - t0) / window * 1e3)
     out = dict(what='tools/finetunebench.py', workload=args.workload, scenes_per_step=args.batch, rounds=rounds, window=window,
-               source_hash=__import__('fcaf3d_amd.build', fromlist=['x']).source_hash(), frozen_stages={})
+               source_hash=__import__('fcaf3d_amd.build', fromlist=['x']).source_hash(), frozen_stages={}, norm_eval={})
     for name, k in variants:
         r = runs[name]
         prog = EX.program_for(r['model'], True)
-        out['frozen_stages'][name] = dict(ms_per_step=[round(x, 3) for x in r['ms']], median_ms=round(median(r['ms']), 3),
-                                          rows_backward=int(len(prog.ops_b)), rows_forward=int(len(prog.ops_f)),
-                                          trainable_floats=int(r['tr'].flat.n))
+        ops = {n[3:].lower(): int((prog.ops_b[:, EX.ROW_OP] == v).sum()) for n, v in vars(EX).items() if n.startswith('OP_') and isinstance(v, int)}
+        out['frozen_stages' if not isinstance(k, tuple) else 'norm_eval'][name] = dict(
+            ms_per_step=[round(x, 3) for x in r['ms']], median_ms=round(median(r['ms']), 3), rows_backward=int(len(prog.ops_b)),
+            rows_forward=int(len(prog.ops_f)), trainable_floats=int(r['tr'].flat.n), backward_launches={n: c for n, c in ops.items() if c})
     base = out['frozen_stages']
     out['spread_ms'] = round(abs(base['-1']['median_ms'] - base['-1 again']['median_ms']), 3)
 
