@@ -561,18 +561,30 @@ int fc_x6_weight_image(const float* W, void* img, int K, int R, int C, int trans
   return FC_OK;
 }
 
-int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, hipStream_t stream) {
-  if (!desc || n < 1 || total_blocks < 1 || total_blocks > 0x7fffffffll) return FC_EINVAL;
+int64_t fc_x6_amax_units(void) { return X6_AMAX_UNITS; }
+
+// passes: bit 0 zero the amax slots, bit 1 the amax pass, bit 2 the image pass (split mode 2; other modes have the image pass alone)
+int fc_x6_weight_images_passes(const int64_t* desc, int n, int64_t total_blocks, const int64_t* amax_chunks, int64_t amax_blocks,
+                               int passes, hipStream_t stream) {
+  if (!desc || n < 1 || total_blocks < 1 || total_blocks > 0x7fffffffll || amax_blocks < 0 || amax_blocks > 0x7fffffffll ||
+      (amax_blocks && !amax_chunks))
+    return FC_EINVAL;
   const long long* d = reinterpret_cast<const long long*>(desc);
   if (split_mode() == 2) {
-    k_x6_weight_images<4><<<(unsigned)fc_cdiv(n, 4), 256, 0, stream>>>(d, n);
-    k_x6_weight_images<3><<<(unsigned)total_blocks, 256, 0, stream>>>(d, n);
-    k_x6_weight_images<2><<<(unsigned)total_blocks, 256, 0, stream>>>(d, n);
-  } else {
+    if (passes & 1) k_x6_weight_images<4><<<(unsigned)fc_cdiv(n, 4), 256, 0, stream>>>(d, n);
+    if ((passes & 2) && amax_blocks)
+      k_x6_weight_amax<X6_AMAX_UNITS><<<(unsigned)amax_blocks, 256, 0, stream>>>(d, reinterpret_cast<const long long*>(amax_chunks));
+    if (passes & 4) k_x6_weight_images<2><<<(unsigned)total_blocks, 256, 0, stream>>>(d, n);
+  } else if (passes & 4) {
     k_x6_weight_images<0><<<(unsigned)total_blocks, 256, 0, stream>>>(d, n);
   }
   FC_CHECK_LAUNCH();
   return FC_OK;
+}
+
+int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, const int64_t* amax_chunks, int64_t amax_blocks,
+                        hipStream_t stream) {
+  return fc_x6_weight_images_passes(desc, n, total_blocks, amax_chunks, amax_blocks, 7, stream);
 }
 
 }  // extern "C"

@@ -257,7 +257,7 @@ __device__ __forceinline__ void h3_weight_image_unit_lds(const float* __restrict
   }
 }
 
-template <int MODE>           // 0 / 2: the image pass of that mode; 3: the amax pass of h3; 4: zero the amax slots (one wave per entry)
+template <int MODE>           // 0 / 2: the image pass of that mode; 4: zero the amax slots (one wave per entry); the amax pass of h3: k_x6_weight_amax
 __global__ __launch_bounds__(256) void k_x6_weight_images(const long long* __restrict__ desc, int n) {
   if (MODE == 4) {
     const int e = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6), l = threadIdx.x & 63;
@@ -277,24 +277,6 @@ __global__ __launch_bounds__(256) void k_x6_weight_images(const long long* __res
   const float* W = reinterpret_cast<const float*>(d[0]);
   u32x4* img = reinterpret_cast<u32x4*>(d[1]);
   const bool vec = (reinterpret_cast<uintptr_t>(W) & 15) == 0;
-  if (MODE == 3) {
-    if (d[7]) return;                           // shares its sibling's slot
-    unsigned m = 0u;
-    if (live && vec) {                          // the unit's 256 x 8 weights, flat
-      const float4* w4 = reinterpret_cast<const float4*>(W + t * 8);
-      const float4 x0 = w4[0], x1 = w4[1];
-      const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const unsigned v = __float_as_uint(xs[e]) & 0x7fffffffu;
-        m = (v > m && v < 0x7f800000u) ? v : m;  // finite weights only (k_amax)
-      }
-    } else if (live) {
-      m = h3_weight_unit_amax(W, t, R, C, (int)d[5]);
-    }
-    h3_block_amax(m, reinterpret_cast<unsigned*>(img) + X6_IMG_AMAX_WORD);
-    return;
-  }
   if (MODE == 2) {
     __shared__ float tile[32 * X6_IMG_LD];
     const unsigned* slot = d[7] ? reinterpret_cast<const unsigned*>(d[7]) + X6_IMG_AMAX_WORD : reinterpret_cast<const unsigned*>(img) + X6_IMG_AMAX_WORD;
@@ -306,6 +288,44 @@ __global__ __launch_bounds__(256) void k_x6_weight_images(const long long* __res
     return;
   }
   if (live) x6_weight_image_unit(W, img, t, R, C, (int)d[5]);
+}
+
+// The amax pass of h3 over MANY kernels, streaming: a grid of its own over the entries that own a slot (desc word 7 == 0; an entry that
+// shares its sibling's gets no block).  chunks[b] = entry << 32 | chunk: block b folds the units [chunk U, chunk U + U) of that
+// entry — contiguous weights, 8 KB a unit — with all of its 2 U 16-byte loads per thread requested before the first compare (a short
+// last chunk reads its own last 16 bytes again: a maximum does not mind), then registers -> wave shuffle -> LDS -> ONE polled atomicMax
+// (amax_commit).  The table is built once on the host (weight_images.py): no search, no dependent load besides the row of desc.
+// Which sub-word a block's maximum lands in differs from the per-unit pass this replaces; the slot's maximum does not.
+#ifndef X6_AMAX_UNITS
+#define X6_AMAX_UNITS 8                // U: units per block = 64 KB in flight per block (fc_x6_amax_units; measured: r7_notes.md section 13)
+#endif
+template <int U>
+__global__ __launch_bounds__(256) void k_x6_weight_amax(const long long* __restrict__ desc, const long long* __restrict__ chunks) {
+  const long long ch = chunks[blockIdx.x];
+  const long long* d = desc + 8 * (ch >> 32);
+  const int K = (int)d[2], R = (int)d[3], C = (int)d[4];
+  const int64_t units = (int64_t)K * (R / 32) * (C / 64), u0 = (ch & 0xffffffffll) * U;
+  const int nu = (int)(units - u0 < U ? units - u0 : U);                  // (>= 1: the host lists no empty chunk)
+  const float* W = reinterpret_cast<const float*>(d[0]);
+  unsigned m = 0u;
+  if ((reinterpret_cast<uintptr_t>(W) & 15) == 0) {
+    const float4* w4 = reinterpret_cast<const float4*>(W + u0 * 2048);
+    const int last = nu * 512 - 1;                                         // the chunk's last 16-byte word
+    float4 x[2 * U];
+#pragma unroll
+    for (int i = 0; i < 2 * U; ++i) {
+      const int j = i * 256 + (int)threadIdx.x;
+      x[i] = w4[j < last ? j : last];
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * U; ++i) { amax_fold(m, x[i].x); amax_fold(m, x[i].y); amax_fold(m, x[i].z); amax_fold(m, x[i].w); }      // finite weights only
+  } else {                                                                 // W not 16-byte aligned: the element path, unit by unit
+    for (int u = 0; u < nu; ++u) {
+      const unsigned v = h3_weight_unit_amax(W, (u0 + u) * 256 + threadIdx.x, R, C, (int)d[5]);
+      m = v > m ? v : m;
+    }
+  }
+  amax_commit(m, reinterpret_cast<unsigned*>(d[1]) + X6_IMG_AMAX_WORD);
 }
 
 #define X6_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)

@@ -69,7 +69,13 @@ def word(op, field):
 
 ALIGN = 256
 S_MAIN, S_HEAD, S_WGRAD = 0, 1, 2
-EV_FORK, EV_HEAD_DONE, EV_W0, EV_W1, EV_WEND, EV_BWD0, EV_HB = 0, 8, 9, 10, 11, 12, 16       # EV_FORK + level, EV_HB + level
+EV_FORK, EV_HEAD_DONE, EV_W0, EV_W1, EV_WEND, EV_BWD0, EV_IMG, EV_HB = 0, 8, 9, 10, 11, 12, 13, 16       # EV_FORK + level, EV_HB + level
+# Who waits for the weight images that runner.TrainStep builds on the weight-gradient stream after the optimizer step (DESIGN.md
+# section 6a): 'first_reader' — a training program with `wgrad_async` carries a record on S_WGRAD / wait on S_MAIN of EV_IMG behind the
+# stem's operators, which read no image, and NetProgram.forward leaves the host-side wait out; 'entry' — the main stream waits
+# before the program's first operator (every other program does, whatever this says).  Part of the program cache key.
+# FC_IMAGE_WAIT=entry: the A/B run of the benchmark.
+IMAGE_WAIT = os.environ.get('FC_IMAGE_WAIT', 'first_reader')
 
 
 def _f(x):
@@ -92,7 +98,7 @@ _FORWARD_SINGLE = _NECK_FORWARD = None       # set by fcaf3d_neck_with_head at i
 
 
 class NetProgram:
-    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None, frozen=-1, plan=None):
+    def __init__(self, det, training, wgrad_async, head_overlap, tail0=False, keep_state=None, frozen=-1, plan=None, image_wait='entry'):
         """frozen: the backbone's frozen prefix of a training program (`frontier`: -1 none, 0 the stem, k the stem and layer1 .. layerk).
         plan: the verdict of `freeze_plan` this program was asked for (None: `frozen`).  Either only NAMES the program: what a layer
         emits is read from its own flags as they are now (its kernel's requires_grad, its BatchNorm's mode), which the caller has checked
@@ -108,6 +114,11 @@ class NetProgram:
         self.frozen = int(frozen) if training else -1
         self.plan = plan if training else None
         self.wgrad_async = wgrad_async and training
+        # image_wait: who waits for a weight-image build on stream 2 (IMAGE_WAIT above; `program_for` hands the switch in, a program
+        # built directly is the 'entry' one unless asked)
+        assert image_wait in ('first_reader', 'entry')
+        self.image_wait = image_wait if self.wgrad_async else 'entry'
+        self.img_pair = False       # ops_f carries the EV_IMG pair: the program itself waits for a build on its stream 2
         bb, nh = det.backbone, det.neck_with_head
         self.nl = min(bb.n_outs, 4)
         self.head_overlap = head_overlap and self.nl > 1
@@ -238,6 +249,11 @@ class NetProgram:
         levels, then neck level i and the head of level i from the coarsest down; last the backward schedule"""
         bb, nh = self.det.backbone, self.det.neck_with_head
         x = em.stem(bb.conv1[0], bb.conv1[1])
+        if self.image_wait == 'first_reader':
+            # the stem's three operators read the fp32 kernel and no image: the main stream joins the build (enqueued on stream 2 by
+            # ImageSet.rebuild_after_step) here, in front of the first operator with an image word
+            em.sync(self.ops_f, S_WGRAD, S_MAIN, EV_IMG)
+            self.img_pair = True
         levels = []
         for li in range(1, self.nl + 1):
             x = em.level(li, getattr(bb, f'layer{li}'), x)
@@ -412,7 +428,10 @@ class NetProgram:
         """-> (cent_all, bbox_all, cls_all, cmax_all) for all head locations (levels finest first), autograd-connected in training"""
         # the previous call's images are believed only under runner.TrainStep's lease or, in eval mode, a detector's `static_weights`
         self.w.ensure(trusted=ImageSet.held is self.w or (not self.training and getattr(self.det, 'static_weights', False)))
-        self.w.wait()                                      # they may have been built on another stream (runner: after the optimizer step)
+        # they may have been built on another stream (runner: after the optimizer step).  A build on the weight-gradient stream is waited
+        # for by the program's own EV_IMG pair, behind the stem (IMAGE_WAIT); any other build by the main stream, here
+        if not (self.img_pair and self.w._built_on == Fn.wgrad_stream(self.dev).cuda_stream):
+            self.w.wait()
         if self.training:
             return _NetFn.apply(self._anchor, self, st)
         return self._forward(st)
@@ -960,6 +979,7 @@ class _Emitter:
         x, rows, _ = x
         hs = S_HEAD if (p.head_overlap and i > 0) else S_MAIN
         if hs == S_HEAD:
+            assert p.img_pair or p.image_wait == 'entry', 'a head branch (it reads the packed head image) forked in front of the image wait'
             self.sync(F, S_MAIN, S_HEAD, EV_FORK + i)
             self.tape = []
             self.branches[i] = (x, self.tape)
@@ -1111,12 +1131,13 @@ def program_for(det, training, tail0=False):
     mode = Fn.split_mode() if Fn.X6 else -1
     cache = det.__dict__.setdefault('_programs', {})
     sig = NetProgram.signature(det)
+    key += (IMAGE_WAIT,)                       # ... and who waits for the weight images (a training program with wgrad_async carries the pair or not)
     prog = cache.get(key + (fuse, mode, keep, front))
     if prog is None or prog._sig != sig:
         if by_plan:
-            prog = NetProgram(det, *key, keep_state=keep, frozen=getattr(det.backbone, 'frozen_stages', -1), plan=front)
+            prog = NetProgram(det, *key[:4], keep_state=keep, frozen=getattr(det.backbone, 'frozen_stages', -1), plan=front, image_wait=IMAGE_WAIT)
         else:
-            prog = NetProgram(det, *key, keep_state=keep, frozen=front)
+            prog = NetProgram(det, *key[:4], keep_state=keep, frozen=front, image_wait=IMAGE_WAIT)
         cache[key + (fuse, mode, keep, front)] = prog
     return prog
 

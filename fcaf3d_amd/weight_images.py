@@ -55,11 +55,18 @@ class WeightImages:
         self.n = len(desc) // 8
         self.blocks = blk
         self.desc = torch.tensor(desc, dtype=torch.int64).to(dev)
+        # the amax pass's own grid (csrc/conv_x6.h k_x6_weight_amax): one block per chunk of U units of every entry that owns its slot
+        # (word 7 == 0), as entry << 32 | chunk; made once, here
+        self.amax_units = U = L.query('fc_x6_amax_units')
+        chunks = [e << 32 | c for e in range(self.n) if desc[8 * e + 7] == 0
+                  for c in range(-(-(desc[8 * e + 2] * (desc[8 * e + 3] // 32) * (desc[8 * e + 4] // 64)) // U))]
+        self.amax_blocks = len(chunks)
+        self.amax_chunks = torch.tensor(chunks, dtype=torch.int64).to(dev)
 
     def build(self):
         """enqueue the build on the CURRENT stream; records the event consumers on other streams wait for"""
         if self.n:
-            L.call('fc_x6_weight_images', L.ptr(self.desc), self.n, self.blocks, L.stream())
+            L.call('fc_x6_weight_images', L.ptr(self.desc), self.n, self.blocks, L.ptr(self.amax_chunks), self.amax_blocks, L.stream())
             self.event = torch.cuda.Event()
             self.event.record()
 

@@ -40,9 +40,10 @@ extern "C" {
  * (fc_batch_augment_voxelize added: the input pipeline of a whole batch from a resident arena in one launch), -> 15
  * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask), -> 16 (fc_adamw_groups_table_bytes /
  * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers), -> 17 (fc_bn_eval_bwd / fc_bn_eval_bwd_ws_bytes /
- * fc_bn_eval_bwd_route added: the backward through a BatchNorm that reads its running statistics).  A caller built against
+ * fc_bn_eval_bwd_route added: the backward through a BatchNorm that reads its running statistics), -> 18 (fc_x6_weight_images takes the
+ * grid of its amax pass, amax_chunks / amax_blocks; fc_x6_amax_units / fc_x6_weight_images_passes added).  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 17
+#define FC_ABI_VERSION 18
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -252,8 +253,16 @@ int fc_x6_weight_image(const float* W, void* img, int K, int R, int C, int trans
  * of n entries of 8 int64 {W pointer, image pointer, K, R, C, transposed, first block, sibling}; sibling (split mode 2): 0, or
  * the address of another image of the SAME weights listed earlier (the forward image of a backward-data entry) whose amax slot
  * this entry shares instead of making its own pass over W; entry e owns the blocks from its
- * first block up to the next entry's, K (R / 32) (C / 64) of them; total_blocks = the last entry's first block + its blocks. */
-int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, hipStream_t stream);
+ * first block up to the next entry's, K (R / 32) (C / 64) of them; total_blocks = the last entry's first block + its blocks.
+ * amax_chunks (split mode 2; a DEVICE array of amax_blocks int64, built once by the caller): the grid of the amax pass, which runs
+ * over the entries WITHOUT a sibling only — with U = fc_x6_amax_units(), an entry of u units (8 KB of weights each) lists its
+ * ceil(u / U) chunks as  entry index << 32 | chunk,  one block of the pass each, in any order.  An entry with a sibling lists none. */
+int64_t fc_x6_amax_units(void);
+int fc_x6_weight_images(const int64_t* desc, int n, int64_t total_blocks, const int64_t* amax_chunks, int64_t amax_blocks,
+                        hipStream_t stream);
+/* the same with a choice of passes (No reference counterpart: measurement, tools/imgbench.py): bit 0 zero the amax slots, bit 1 the amax pass, bit 2 the image pass */
+int fc_x6_weight_images_passes(const int64_t* desc, int n, int64_t total_blocks, const int64_t* amax_chunks, int64_t amax_blocks,
+                               int passes, hipStream_t stream);
 
 /* ME.MinkowskiConvolution forward (me_resnet.py:19-21,56-62; BasicBlock; fcaf3d_neck_with_head.py:52,69),
  * its backward-data pass (call with the transposed table and fc_transpose_weight'ed kernel), and with
