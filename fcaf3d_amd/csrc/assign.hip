@@ -59,15 +59,33 @@ __device__ static inline float centerness_of(const Face6& f) {
 __global__ void k_count(const float* __restrict__ pts, const int* __restrict__ scene, const int* __restrict__ level, int64_t N,
                         const float* __restrict__ boxes, const int* __restrict__ box_count, int M, int L,
                         const float* __restrict__ trig, int* __restrict__ counts) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  int s = scene[i], l = level[i];
-  float px = pts[i * 3], py = pts[i * 3 + 1], pz = pts[i * 3 + 2];
-  int m = box_count[s];
-  for (int j = 0; j < m; ++j) {
-    const float* b = boxes + ((int64_t)s * M + j) * 7;
-    Face6 f = face_distances(b, ld_f(&trig[2 * (s * M + j)]), ld_f(&trig[2 * (s * M + j) + 1]), px, py, pz);
-    if (is_inside(f)) atomicAdd(&counts[((int64_t)s * M + j) * L + l], 1);
+  // Locations are grouped by level and scene, so the hits of a wave on box j mostly share ONE counter: the lanes that hit the same
+  // counter elect their first lane, which adds their number (integer sums: any grouping is exact).  The loops are uniform over
+  // the wave (a lane past N or past its scene's boxes has no hit) so that every lane takes part in the ballots.
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int s = 0, l = 0, m = 0;
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (i < N) {
+    s = scene[i]; l = level[i];
+    px = pts[i * 3]; py = pts[i * 3 + 1]; pz = pts[i * 3 + 2];
+    m = box_count[s];
+  }
+  for (int j = 0; __any(j < m); ++j) {
+    bool hit = false;
+    if (j < m) {
+      const float* b = boxes + ((int64_t)s * M + j) * 7;
+      Face6 f = face_distances(b, ld_f(&trig[2 * (s * M + j)]), ld_f(&trig[2 * (s * M + j) + 1]), px, py, pz);
+      hit = is_inside(f);
+    }
+    const int64_t c = ((int64_t)s * M + j) * L + l;
+    unsigned long long rem = __ballot(hit);
+    while (rem) {
+      const int leader = __ffsll((long long)rem) - 1;
+      const unsigned long long same = __ballot(hit && c == __shfl(c, leader, 64));
+      if (lane == leader) atomicAdd(&counts[c], __popcll(same));
+      rem &= ~same;
+    }
   }
 }
 

@@ -575,8 +575,8 @@ __global__ void k_child_rows(const int4* __restrict__ q, int64_t n, const unsign
     rows[i] = r < 0 ? -1 : 8 * r + bits;
     hit = r >= 0;
   }
-  const unsigned long long bal = __ballot(hit);
-  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_found, __popcll(bal));
+  const int hits = __syncthreads_count(hit);        // one atomic per block: every block of the launch adds to the same word
+  if (threadIdx.x == 0 && hits) atomicAdd(n_found, hits);
 }
 
 int fc_child_rows(const int* query_coords, int64_t n, const unsigned long long* parent_keys, const int* parent_vals,

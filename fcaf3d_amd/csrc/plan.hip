@@ -542,7 +542,7 @@ int fc_plan_levels(const int64_t* cfg, const int64_t* scenes, void* arena1, int6
       FC_CHECK_LAUNCH();
     }
     // ---- the chain: two launches per set ----
-    const unsigned gB = (unsigned)fc_cdiv(T, 1024), gF = (unsigned)fc_cdiv(T, 256);
+    const unsigned gB = (unsigned)fc_cdiv(T, 1024);  // both kernels: one block per 1 024 input rows
     for (int s = 0; s < S; ++s) {
       int* meta_s = meta + METAW * s;
       const int* n_in_dev = s ? meta + METAW * (s - 1) + META_ROWS : nullptr;
@@ -557,7 +557,7 @@ int fc_plan_levels(const int64_t* cfg, const int64_t* scenes, void* arena1, int6
       if (probe) stage1_pp[s] = pp0;
       const bool more = s + 1 < S;
       Bracket br(probe, PK_FINALIZE, 0.0, stream);
-      k_plan_finalize<<<gF, 256, 0, stream>>>(src, n_in_dev, T, 1 << s, flags, blocksums, coarse, slots[s & 1], vals, (int4*)p[10 + s],
+      k_plan_finalize<<<gB, 1024, 0, stream>>>(src, n_in_dev, T, 1 << s, flags, blocksums, coarse, slots[s & 1], vals, (int4*)p[10 + s],
                                              s == 0 ? feats_raw : nullptr, s == 0 ? F0 : nullptr, nfeat,
                                              meta + METAW * S + (int64_t)s * B, B, meta_s, more ? keys_all + cap0 * (s + 1) : nullptr,
                                              more ? vals_all + cap0 * (s + 1) : nullptr, slots[(s + 1) & 1]);

@@ -58,8 +58,8 @@ __global__ void k_plan_insert(const int4* __restrict__ coords, int64_t n, unsign
   fc_hash_insert(keys, vals, mask, c, (int)i, slot);
 }
 
-// winners: flags + the count of every 256-row sub-block (blocksums, what k_plan_finalize works in) and of every 1 024-row block
-// (coarse).  No scan here: every block of k_plan_finalize adds up the (L2-resident, <= a few thousand) counts in front of it — and all
+// winners: flags + the count of every 256-row sub-block (blocksums: a wave quad of k_plan_finalize) and of every 1 024-row block
+// (coarse: a block of k_plan_finalize).  No scan here: every block of k_plan_finalize adds up the (L2-resident, <= a few thousand) counts in front of it — and all
 // of them, for the set's row count — itself.  (Until r6's last take the LAST block to finish scanned the counts in place: a
 // device-scope fence and a same-line atomic per block, 28 us for an EMPTY set and ~60 of the ~100 us of a full one.)
 __global__ __launch_bounds__(256) void k_plan_flags(const int* __restrict__ slot, const int* __restrict__ vals, const int* __restrict__ n_dev,
@@ -96,66 +96,104 @@ __global__ __launch_bounds__(256) void k_plan_flags(const int* __restrict__ slot
 }
 
 // positions + the set itself: winner row i -> out row p: coordinates (with its feature row for level 0), table value = p,
-// rows-per-scene counters (rows of one scene are consecutive: one atomic per wave and scene) — and, fused, the hash insert of the
-// NEXT set of the chain: row p of this set, quantised to the next stride, goes into the next table with value p (first occurrence
-// = smallest p, as an insert pass over the finished set would give).  The block's first output row = the winners in front of it =
-// the coarse counts of the 1 024-row blocks before its own + the sub-block counts inside that one; the set's row count (the next
-// table's mask; block 0 leaves it in meta_s[META_ROWS] for the kernels behind) = all coarse counts.
-__global__ __launch_bounds__(256) void k_plan_finalize(const int4* __restrict__ coords, const int* __restrict__ n_dev, int64_t n_host, int q,
-                                                       const unsigned char* __restrict__ flags, const int* __restrict__ blocksums,
-                                                       const int* __restrict__ coarse, const int* __restrict__ slot, int* vals,
-                                                       int4* __restrict__ out_coords, const float* __restrict__ feats_in,
-                                                       float* __restrict__ feats_out, int nfeat, int* __restrict__ scene_cnt, int B,
-                                                       int* __restrict__ meta_s, unsigned long long* next_keys, int* next_vals,
-                                                       int* __restrict__ next_slot) {
-  __shared__ int ws[4];
-  __shared__ int red[2][4];
+// rows-per-scene counters — and, fused, the hash insert of the NEXT set of the chain: row p of this set, quantised to the next
+// stride, goes into the next table with value p (first occurrence = smallest p, as an insert pass over the finished set would
+// give).  A block covers the 1 024 input rows of one block of k_plan_flags, one row per thread, waves 4r .. 4r + 3 its sub-block r.
+// The block's first output row = the winners in front of it = the coarse counts of the blocks before its own, a sub-block's
+// = + the sub-block counts before it; the set's row count (the next table's mask; block 0 leaves it in meta_s[META_ROWS] for
+// the kernels behind) = all coarse counts.
+//
+// Rows per scene: rows of one scene are consecutive, so a block's winners belong to a short run of scenes that begins at
+// the scene of the block's first input row.  Each wave adds its count per scene to one of PF_SCENE_SLOTS counters in LDS
+// (scene - first scene), and the block sends ONE global atomic per occupied slot; a scene outside the slots (more than
+// PF_SCENE_SLOTS scenes inside 1 024 rows, or rows that are not in scene order) takes one global atomic per wave.  All
+// counters of a set share one cache line: one atomic per wave and scene — 12 500 of them for the level-0 set of eight
+// 100 000-point scenes — queued up at that line; a block now sends one or two (~800 for that set).  The sums are
+// integers: any grouping is exact.  (profiles/r7_notes.md section 14: the seven launches of the benchmark's chain 540 -> 239 us,
+// what the kernel without any counter takes.)
+//
+// Knock-outs (tools/planbench.py --ko; never the product library, the plans are wrong):
+//   -DFC_KO_PF_NOCOUNT: no scene counters      -DFC_KO_PF_NOVALS: no vals[slot[i]] = p
+//   -DFC_KO_PF_NOINSERT: no insert into the next table (slot 0 for every row: the sets behind come out empty)
+constexpr int PF_SCENE_SLOTS = 4;
+__global__ __launch_bounds__(1024) void k_plan_finalize(const int4* __restrict__ coords, const int* __restrict__ n_dev, int64_t n_host, int q,
+                                                        const unsigned char* __restrict__ flags, const int* __restrict__ blocksums,
+                                                        const int* __restrict__ coarse, const int* __restrict__ slot, int* vals,
+                                                        int4* __restrict__ out_coords, const float* __restrict__ feats_in,
+                                                        float* __restrict__ feats_out, int nfeat, int* __restrict__ scene_cnt, int B,
+                                                        int* __restrict__ meta_s, unsigned long long* next_keys, int* next_vals,
+                                                        int* __restrict__ next_slot) {
+  __shared__ int ws[16];
+  __shared__ int red[2][16];
+  __shared__ int cnt[PF_SCENE_SLOTS];
   const int64_t n = n_dev ? *n_dev : n_host;
-  const int64_t base = (int64_t)blockIdx.x * 256;
+  const int64_t base = (int64_t)blockIdx.x * 1024;
   if (base >= n) return;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = w >> 2;
   const int64_t i = base + threadIdx.x;
   const int f = i < n ? (int)flags[i] : 0;
   const unsigned long long bal = __ballot(f);
   if (lane == 0) ws[w] = __popcll(bal);
-  const int nc = (int)((n + 1023) >> 10), mine = (int)(blockIdx.x >> 2);
+  if (threadIdx.x < PF_SCENE_SLOTS) cnt[threadIdx.x] = 0;
+  const int first_scene = coords[base].x;
+  const int nc = (int)((n + 1023) >> 10), mine = (int)blockIdx.x;
+  int sub = 0;                                     // winners of the sub-blocks in front of this wave's
+  for (int k = 0; k < r; ++k) sub += blocksums[4 * mine + k];
   int before = 0, all = 0;
-  for (int j = threadIdx.x; j < nc; j += 256) {
+  for (int j = threadIdx.x; j < nc; j += 1024) {
     const int v = coarse[j];
     all += v;
     if (j < mine) before += v;
   }
-  if (threadIdx.x < (int)(blockIdx.x & 3)) before += blocksums[4 * mine + threadIdx.x];
   for (int o = 32; o > 0; o >>= 1) {
     before += __shfl_xor(before, o, 64);
     all += __shfl_xor(all, o, 64);
   }
   if (lane == 0) { red[0][w] = before; red[1][w] = all; }
   __syncthreads();
-  int pre = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  const int total = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  int pre = sub, total = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) { pre += red[0][k]; total += red[1][k]; }
   if (blockIdx.x == 0 && threadIdx.x == 0) meta_s[META_ROWS] = total;
   const unsigned long long nmask = next_keys ? table_mask(total) : 0ull;
-  for (int k = 0; k < w; ++k) pre += ws[k];
+  for (int k = 4 * r; k < w; ++k) pre += ws[k];
   int b = -1;
   if (f) {
     const int p = pre + __popcll(bal & ((1ull << lane) - 1ull));
     const int4 c = fc_quantize(coords[i], q);
     out_coords[p] = c;
+#ifndef FC_KO_PF_NOVALS
     vals[slot[i]] = p;                             // the table now maps key -> row of the new set
+#endif
     if (feats_out)
       for (int k = 0; k < nfeat; ++k) feats_out[(int64_t)p * nfeat + k] = feats_in[i * nfeat + k];
     b = c.x;
+#ifndef FC_KO_PF_NOINSERT
     if (next_keys) fc_hash_insert(next_keys, next_vals, nmask, fc_quantize(c, 2 * q), p, next_slot);
+#else
+    if (next_keys) next_slot[p] = 0;
+#endif
   }
+#ifndef FC_KO_PF_NOCOUNT
   unsigned long long rem = bal;                    // rows per scene
   while (rem) {
     const int leader = __ffsll((long long)rem) - 1;
     const int lb = __shfl(b, leader, 64);
     const unsigned long long same = __ballot(f && b == lb);
-    if (lane == leader && lb >= 0 && lb < B) atomicAdd(&scene_cnt[lb], __popcll(same));
+    if (lane == leader) {
+      const unsigned k = (unsigned)lb - (unsigned)first_scene;
+      if (k < (unsigned)PF_SCENE_SLOTS) atomicAdd(&cnt[k], __popcll(same));
+      else if (lb >= 0 && lb < B) atomicAdd(&scene_cnt[lb], __popcll(same));
+    }
     rem &= ~same;
   }
+  __syncthreads();
+  if (threadIdx.x < PF_SCENE_SLOTS) {
+    const int64_t sc = (int64_t)first_scene + threadIdx.x;
+    const int v = cnt[threadIdx.x];
+    if (v && sc >= 0 && sc < B) atomicAdd(&scene_cnt[sc], v);
+  }
+#endif
 }
 
 }  // namespace

@@ -150,8 +150,8 @@ __global__ void k_plan_gen_rows(Batch<GenRowsJob> bt, const unsigned long long* 
     }
     j.rows[i] = r;
   }
-  const unsigned long long bal = __ballot(hit);
-  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(j.n_found, __popcll(bal));
+  const int hits = __syncthreads_count(hit);        // one atomic per block: all blocks of a job add to the same word
+  if (threadIdx.x == 0 && hits) atomicAdd(j.n_found, hits);
 }
 // compulsory bytes: coords, row written, slot probed
 inline double probe_bytes(const Batch<GenRowsJob>& b, double by = 0) {

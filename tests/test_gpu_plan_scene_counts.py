@@ -1,0 +1,116 @@
+"""-m gpu: the rows-per-scene counters of the coordinate chain (csrc/plan_chain.h k_plan_finalize: a block of 1 024 input rows adds
+its winners per scene in LDS and sends one atomic per scene; PF_SCENE_SLOTS = 4 scenes per block, the rest per wave).
+fc_plan_levels is called with pre-voxelised coordinates (C_COORDS_IN), so that row positions are exact: scene boundaries at the
+wave, sub-block and block edges, more scenes inside one block than LDS slots, an empty scene, a scene of one voxel, duplicates
+across a block edge, a single row.  For every set of the chain the counters must equal numpy.bincount of the batch column of the set
+the plan returned, and the sets (with the level-0 feature rows) must be those of the per-operator path (sparse.CoordMap)."""
+import numpy as np
+import pytest
+import torch
+
+from fcaf3d_amd import _lib as L
+from fcaf3d_amd import plan as PL
+from fcaf3d_amd import sparse as SP
+
+pytestmark = pytest.mark.gpu
+
+NL = 4
+S = 3 + NL              # sets of the chain, strides 1 .. 64
+
+
+def grid(b, ks):
+    """rows of scene b that stay distinct in every set of the chain (multiples of 128 >= 2 * the coarsest stride)"""
+    ks = np.asarray(ks, dtype=np.int64)
+    return np.stack([np.full_like(ks, b), 128 * (ks % 32), 128 * ((ks // 32) % 32), 128 * (ks // 1024)], axis=1).astype(np.int32)
+
+
+def cloud(b, n, seed, extent=24):
+    """rows of scene b with duplicates at every stride"""
+    c = np.random.default_rng(seed).integers(0, extent, size=(n, 4))
+    c[:, 0] = b
+    return c.astype(np.int32)
+
+
+def voxel(b, n, at=(5, 5, 5)):
+    return np.tile(np.array([[b, *at]], dtype=np.int32), (n, 1))
+
+
+def _cases():
+    cs = {}
+    for nb in (63, 64, 65, 255, 256, 257, 1023, 1024, 1025):       # B = 2: the boundary of scenes 0 | 1 at input row nb of EVERY set
+        cs[f'boundary_{nb}'] = (2, [grid(0, range(nb)), cloud(1, 1500, nb)])
+    cs['one_scene'] = (1, [cloud(0, 3000, 1)])
+    cs['single_row'] = (1, [grid(0, [7])])                          # T = 1
+    cs['single_row_of_two_scenes'] = (2, [grid(0, []), grid(1, [3])])
+    # B = 5: an empty scene in the middle, a scene of one voxel (one winner among 300), a boundary at row 1 023
+    cs['empty_and_one_voxel'] = (5, [grid(0, range(1023)), cloud(1, 700, 2), grid(2, []), voxel(3, 300), cloud(4, 2000, 3)])
+    # B = 9: nine scenes inside one 1 024-row block (more than the LDS slots): all rows winners in every set / with duplicates
+    cs['nine_scenes_distinct'] = (9, [grid(b, range(100)) for b in range(9)])
+    cs['nine_scenes_clouds'] = (9, [cloud(b, 100, 10 + b, extent=6) for b in range(9)])
+    cs['nine_scenes_two_blocks'] = (9, [grid(0, range(1000))] + [cloud(b, 100, 20 + b, extent=8) for b in range(1, 9)])
+    # duplicates of one voxel across the edge of block 0 (rows 1 010 .. 1 039; the winner is row 1 010), then the next scene
+    cs['duplicates_across_a_block_edge'] = (2, [np.concatenate([grid(0, range(1010)), np.tile(grid(0, [1100]), (30, 1)), grid(0, range(1040, 1200))]),
+                                                cloud(1, 900, 4)])
+    return cs
+
+
+CASES = _cases()
+
+
+def _plan_levels(coords, feats, B):
+    """fc_plan_levels alone on pre-voxelised rows -> (coordinate sets, rows per (set, scene), level-0 features)"""
+    dev = coords.device
+    T, nfeat = coords.shape[0], feats.shape[1]
+    lib = L.lib()
+    cfg = np.zeros(lib.fc_plan_cfg_words(), dtype=np.int64)
+    cfg[PL.C_B], cfg[PL.C_NL], cfg[PL.C_NFEAT], cfg[PL.C_TOTAL] = B, NL, nfeat, T
+    cfg[PL.C_COORDS_IN], cfg[PL.C_FEATS_IN] = coords.data_ptr(), feats.data_ptr()
+    scenes = np.zeros((B, 3), dtype=np.int64)
+    out = np.zeros(lib.fc_plan_out_words(B, NL), dtype=np.int64)
+    counts = torch.zeros(PL.pinned_words(B, NL)[0], dtype=torch.int32).pin_memory()
+    arena = torch.empty(L.query('fc_plan_stage1_bytes', T, B, NL, nfeat), dtype=torch.uint8, device=dev)
+    rc = lib.fc_plan_levels(cfg.ctypes.data, scenes.ctypes.data, arena.data_ptr(), arena.numel(), out.ctypes.data, counts.data_ptr(), L.stream())
+    assert rc == 0 and not out[PL.H_BAD] and out[PL.H_S] == S
+    torch.cuda.synchronize()
+    ar = PL._Arenas(arena, arena)
+    cn = counts.numpy()
+    sets = []
+    for s in range(S):
+        o = out[PL.HDR + PL.SETW * s:PL.HDR + PL.SETW * (s + 1)]
+        assert int(o[PL.S_N]) == int(cn[PL.METAW * s + PL.META_ROWS]) and int(o[PL.S_STRIDE]) == 1 << s
+        sets.append(ar.view(int(o[PL.S_COORDS]), (int(o[PL.S_N]), 4)).clone())
+    per_scene = cn[PL.METAW * S:PL.METAW * S + S * B].reshape(S, B).copy()
+    F0 = ar.view(int(out[PL.H_F0]), (sets[0].shape[0], nfeat), torch.float32).clone()
+    return sets, per_scene, F0
+
+
+@pytest.mark.parametrize('case', sorted(CASES))
+def test_rows_per_scene_equal_bincount_and_sets_equal_the_per_operator_path(case):
+    dev = torch.device('cuda:0')
+    B, scenes = CASES[case]
+    rows = np.concatenate(scenes)
+    coords = torch.from_numpy(rows).to(dev)
+    feats = torch.arange(len(rows), dtype=torch.float32, device=dev).view(-1, 1)      # feature = input row: F0 names the winners
+    sets, per_scene, F0 = _plan_levels(coords, feats, B)
+    print(case, 'rows per (set, scene):', per_scene.tolist())
+    for s, c in enumerate(sets):
+        want = np.bincount(c[:, 0].cpu().numpy(), minlength=B)
+        assert per_scene[s].tolist() == want.tolist(), (s, per_scene[s], want)
+        assert int(per_scene[s].sum()) == c.shape[0]
+    # the per-operator path: unique rows of floor(coords / q) * q in order of first occurrence, set by set
+    cm, first, _ = SP.CoordMap.from_coords(coords, 1, B, want_first=True)
+    assert torch.equal(F0[:, 0], first.float())
+    for s in range(S):
+        assert cm.n == sets[s].shape[0] and cm.stride == 1 << s, s
+        assert torch.equal(cm.coords, sets[s]), f'set {s}'
+        assert cm.scene_counts == per_scene[s].tolist(), s
+        if s + 1 < S:
+            cm = cm.strided(2)
+    if case.startswith('boundary_'):                                 # the boundary sits at the same input row in every set
+        nb = int(case.split('_')[1])
+        assert all(int(per_scene[s, 0]) == nb for s in range(S))
+    if case == 'nine_scenes_distinct':
+        assert per_scene.tolist() == [[100] * 9] * S
+    if case == 'empty_and_one_voxel':
+        assert all(int(per_scene[s, 2]) == 0 and int(per_scene[s, 3]) == 1 for s in range(S))
+    torch.cuda.synchronize()
