@@ -23,6 +23,7 @@ import torch
 import fcaf3d_amd.functional as Fn
 from fcaf3d_amd import _lib as L
 from tests import norm_cases as NC
+from tests.amax_slots import _amax_bits, _amax_word, _new_slot
 
 pytestmark = pytest.mark.gpu
 SWEPT = NC.sweep()
@@ -53,20 +54,6 @@ def _poisoned_workspace(nbytes):
     ws = L.workspace(max(int(nbytes), 16), _dev())
     ws.fill_(255)                                  # the WHOLE cached buffer: 0xFFFFFFFF is a NaN
     return ws
-
-
-def _new_slot():
-    return torch.zeros(512, dtype=torch.int32, device=_dev())
-
-
-def _amax_word(slot):
-    """the amax as its consumers read it: the maximum of the slot's 32 sub-words (fc_common.h fc_amax_read)"""
-    return int(slot.view(32, 16)[:, 0].max())
-
-
-def _amax_bits(t):
-    t = t[torch.isfinite(t)]
-    return int(t.abs().max().reshape(1).view(torch.int32)) if t.numel() else 0
 
 
 def _miss(name, got, want, bound):
