@@ -64,7 +64,7 @@ def parse_enums(path=EXEC_OPS):
     return blocks
 
 
-ABI_VERSION = 18       # include/fcaf3d_hip.h FC_ABI_VERSION
+ABI_VERSION = 19       # include/fcaf3d_hip.h FC_ABI_VERSION
 _lib = None
 _protos = None
 

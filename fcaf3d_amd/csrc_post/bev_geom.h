@@ -1,6 +1,6 @@
-// Rotated-BEV rectangle overlap for the post-processing kernels (csrc_post/eval.hip).
+// Rotated-BEV rectangle overlap for the post-processing kernels (csrc_post/eval.hip, csrc_post/vote.hip).
 //
-// THIS IS A COPY of the geometry of csrc/nms.hip:16-103 (seg_cross / in_box_bev / box_corners / bev_overlap_rotated), kept
+// THIS IS A COPY of the geometry of csrc/nms.hip:16-117 (seg_cross / in_box_bev / box_corners / bev_overlap_rotated and the two IoUs), kept
 // operation for operation so that the two give the same fp32 value.  It is duplicated, not shared, on purpose: nothing under
 // csrc/ may change without retaking every profile under profiles/ — build.source_hash() covers csrc/*.hip and csrc/*.h and
 // tests/test_host_logic.py pins the committed profiles to it — and moving these functions into a header both files include
@@ -100,6 +100,22 @@ __device__ static float bev_overlap_rotated(const float* a, const float* b) {
     area += ux * vy - uy * vx;
   }
   return fabsf(area) / 2.f;
+}
+
+// csrc/nms.hip:105-117, the two BEV IoUs of the NMS (what fc_nms_bev compares with its threshold and fc_boxes_iou_bev stores), the
+// same fp32 operations in the same order (csrc_post/vote.hip: a = the kept box, b = the candidate)
+__device__ static inline float iou_bev_rotated(const float* a, const float* b) {
+  float sa = a[3] * a[4], sb = b[3] * b[4];
+  float ov = bev_overlap_rotated(a, b);
+  return ov / fmaxf(sa + sb - ov, EVG_EPS);
+}
+
+__device__ static inline float iou_bev_aligned(const float* a, const float* b) {
+  float left = fmaxf(a[0] - a[3] / 2, b[0] - b[3] / 2), right = fminf(a[0] + a[3] / 2, b[0] + b[3] / 2);
+  float top = fmaxf(a[1] - a[4] / 2, b[1] - b[4] / 2), bottom = fminf(a[1] + a[4] / 2, b[1] + b[4] / 2);
+  float w = fmaxf(right - left, 0.f), h = fmaxf(bottom - top, 0.f);
+  float inter = w * h;
+  return inter / fmaxf(a[3] * a[4] + b[3] * b[4] - inter, EVG_EPS);
 }
 
 // csrc/nms.hip:105-109 (what fc_boxes_iou_bev stores), then fcaf3d_amd/nms.py:86-96 (boxes_iou3d_gpu) on that value, the same

@@ -8,6 +8,7 @@ loader whose batches are built by ONE kernel launch from a descriptor table (csr
   ResidentScenes               every scene's raw points once, in one arena (ΣN, C) fp32 on the device, plus offsets
   DeviceLoader                 the FCAF3D train pipeline (or the single-augmentation test pipeline) drawn on the host from a
                                counter-based generator, applied in the batch kernel: no device read-back, no sort, one launch
+  AugDeviceLoader              test-time augmentation: the A copies MultiScaleFlipAug3D asks for of each of B scenes, one launch
 
 Stated differences to the reference:
   * filter_empty_gt=True DROPS scenes without boxes when the dataset is built; the reference keeps them in the list and re-draws
@@ -219,6 +220,38 @@ def parse_pipeline(pipeline_cfg):
     return P
 
 
+def parse_aug_pipeline(pipeline_cfg):
+    """A test pipeline whose MultiScaleFlipAug3D may ask for several augmentations (test-time augmentation: flip=True with BEV flips,
+    several pts_scale_ratio) -> (P, augs): the parameters `parse_pipeline` returns for the pipeline with ONE augmentation, and the list
+    of (pts_scale_ratio, pcd_horizontal_flip, pcd_vertical_flip) in the loop order of pipelines.MultiScaleFlipAug3D (img_scale ->
+    pts_scale_ratio -> horizontal -> vertical).  A pipeline without MultiScaleFlipAug3D: one identity augmentation.  More than one
+    img_scale, or with flip=True more than one flip_direction (they would repeat every copy), flips or scales asked for without the inner step that applies
+    them, or an inner step the batch kernel does not implement: an error that names it."""
+    augs, single = [(1.0, False, False)], []
+    for st in pipeline_cfg:
+        if st['type'] != 'MultiScaleFlipAug3D':
+            single.append(st)
+            continue
+        for key in ('img_scale', 'flip_direction'):
+            if isinstance(st.get(key), list) and len(st[key]) != 1 and (key == 'img_scale' or st.get('flip', False)):
+                raise NotImplementedError(f'AugDeviceLoader: MultiScaleFlipAug3D with {len(st[key])} entries in {key!r} is not '
+                                          'implemented (every augmentation would be repeated once per entry)')
+        ratios = st.get('pts_scale_ratio', 1.0)
+        ratios = [float(r) for r in (ratios if isinstance(ratios, (list, tuple)) else [ratios])]
+        flip = bool(st.get('flip', False))
+        h_aug = [False, True] if flip and st.get('pcd_horizontal_flip', False) else [False]
+        v_aug = [False, True] if flip and st.get('pcd_vertical_flip', False) else [False]
+        augs = [(r, h, v) for r in ratios for h in h_aug for v in v_aug]
+        inner = {t['type'] for t in st['transforms']}
+        if any(h or v for _, h, v in augs) and 'RandomFlip3D' not in inner:
+            raise NotImplementedError("AugDeviceLoader: MultiScaleFlipAug3D asks for flips but its transforms hold no 'RandomFlip3D'")
+        if any(r != 1.0 for r, _, _ in augs) and 'GlobalRotScaleTrans' not in inner:
+            raise NotImplementedError("AugDeviceLoader: MultiScaleFlipAug3D asks for pts_scale_ratio but its transforms hold no "
+                                      "'GlobalRotScaleTrans'")
+        single.append(dict(st, flip=False, pts_scale_ratio=ratios[0]))
+    return parse_pipeline(single), augs
+
+
 def draw(P, seed, epoch, index):
     """The draws of one scene — flips, angle, scale, translation, sample seed — as a pure function of (seed, epoch, dataset
     index): Philox keyed on them, a counter-based generator (no state carried from one scene to the next)."""
@@ -386,3 +419,65 @@ class DeviceLoader:
 
     def __iter__(self):
         return iter(self.batches())
+
+
+# ---- test-time augmentation batches ------------------------------------------------------------------------------------------------------
+class AugBatch(list):
+    """`points` of a test-time augmentation batch: points[a][b] = augmentation a of scene b, as aug_test takes it, and `.flat`, ONE
+    DeviceBatch over the A * B copies (copy a of scene b at descriptor a * B + b) that voxelises them all in one launch"""
+
+    def __init__(self, flat, A, B):
+        self.flat = flat
+        super().__init__([flat[a * B + b] for b in range(B)] for a in range(A))
+
+
+class AugDeviceLoader(DeviceLoader):
+    """Test-time augmentation batches of a ResidentScenes set, with DeviceLoader's surface in test mode: a batch is
+    dict(points=AugBatch, img_metas=img_metas[a][b]).  The A augmentations are those of the pipeline's MultiScaleFlipAug3D
+    (parse_aug_pipeline), applied to B scenes by ONE launch over A * B <= 256 descriptors.  Every copy samples its own points, as
+    the reference's per-copy IndoorPointSample does: copy a of dataset index i draws with Philox keyed on (seed, (a << 40) ^ i) — a
+    pure function of (seed, index, a), and for a = 0 the draw of DeviceLoader for (seed, i): when augmentation 0 is the identity,
+    copy 0 is the scene DeviceLoader gives."""
+
+    def __init__(self, resident, pipeline_cfg, samples_per_gpu, seed=0, rank=0, world_size=1):
+        from .boxes import DepthInstance3DBoxes
+        self.resident = resident
+        self.P, self.augs = parse_aug_pipeline(pipeline_cfg)
+        if self.P['train']:
+            raise NotImplementedError('AugDeviceLoader: a pipeline without MultiScaleFlipAug3D is a training pipeline (DeviceLoader)')
+        self.samples_per_gpu, self.seed, self.rank, self.world_size = int(samples_per_gpu), int(seed), int(rank), int(world_size)
+        A = len(self.augs)
+        if self.samples_per_gpu < 1 or A * self.samples_per_gpu > MAX_SCENES:
+            raise ValueError(f'{A} augmentations x samples_per_gpu={self.samples_per_gpu} = {A * self.samples_per_gpu} copies in one '
+                             f'launch: at most {MAX_SCENES}')
+        self.shuffle, self.epoch = False, 0
+        self._box_type = DepthInstance3DBoxes
+        if any(a is None for a in resident.align) and self.P['align'] and len(resident.align):
+            raise AssertionError('axis_align_matrix is not provided in GlobalAlignment')
+
+    def draw(self, epoch, index, a=0):
+        """the draws of copy a of dataset index `index` (the same in every epoch): augmentation a's scale and flips, its own sample seed"""
+        s, h, v = self.augs[a]
+        return dict(draw(self.P, self.seed, a, index), scale=s, flip_h=h, flip_v=v)
+
+    def batch(self, epoch, idx):
+        r, P = self.resident, self.P
+        A, B = len(self.augs), len(idx)
+        desc = np.zeros((A * B, DESC_WORDS), np.int64)
+        metas, off = [], 0
+        for a in range(A):
+            metas.append([])
+            for b, i in enumerate(idx):
+                k = int(r.slot[i])
+                p = self.draw(epoch, int(i), a)
+                n_src = int(r.count[k])
+                n_out = P['num_points'] if P['num_points'] is not None else n_src
+                d = a * B + b
+                desc[d, :6] = r.start[k], n_src, n_out, off, 0, 0
+                desc[d, 4:5].view(np.uint64)[0] = p['sample_seed']
+                desc[d, 6:] = xform_words(r.align[k] if P['align'] else None, p)
+                off += n_out
+                metas[a].append(dict(box_type_3d=self._box_type, sample_idx=r.metas[k]['sample_idx'],
+                                     pts_filename=r.metas[k]['pts_filename'], dataset_index=int(i), pcd_horizontal_flip=p['flip_h'],
+                                     pcd_vertical_flip=p['flip_v'], pcd_scale_factor=p['scale']))
+        return dict(points=AugBatch(DeviceBatch(r, desc), A, B), img_metas=metas)

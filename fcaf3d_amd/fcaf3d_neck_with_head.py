@@ -491,6 +491,11 @@ class Fcaf3DNeckWithHead(nn.Module):
 
     # set to a list: get_bboxes_aug appends a (start, end) pair of device events around its merge stage (tools/ttabench.py)
     merge_events = None
+    # likewise around the merge NMS and around the voting launch, and the voting launch's member counts as (members (B * C, S1) int32,
+    # kept counts (B * C,)) device tensors (tools/ttaevalbench.py); None: nothing is recorded
+    nms_events = None
+    vote_events = None
+    vote_members = None
 
     def get_bboxes_aug(self, centernesses, bbox_preds, cls_scores, points, img_metas, rescale=False):
         """Test-time augmentation (merge_augs.py:7-91 for a batch): the head outputs are those of B * A scenes, augmentation a of
@@ -512,7 +517,7 @@ class Fcaf3DNeckWithHead(nn.Module):
                                       for a in range(A)], img_metas_b, self.test_cfg)
                     for b, img_metas_b in enumerate(zip(*img_metas))]
         from .merge_augs import (MERGE_TO_BOTTOM, MERGE_WITH_YAW, aug_params, merge_cfg, merge_sorted_segments,
-                                 transform_word)
+                                 transform_word, vote_cfg, vote_segments)
         P, PB, ordr, kept, kcount, n_max, C, yaw_flag = self._first_stage(centernesses, bbox_preds, cls_scores, points, A * B)
         dev = P.device
         nms_thr, rotated, max_num = merge_cfg(self.test_cfg, yaw_flag)
@@ -537,13 +542,35 @@ class Fcaf3DNeckWithHead(nn.Module):
         seg_bytes = S1 * ((S1 + 63) // 64) * 8
         per = max(1, min(B, self.NMS_WS_BUDGET // max(1, C * seg_bytes)))
         keep_l, kc_l = [], []
+        nev = None
+        if self.nms_events is not None:
+            nev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            nev[0].record()
         for b0 in range(0, B, per):
             b1 = min(B, b0 + per)
             k_, c_n = _nms_run(mb[b0 * C:b1 * C], mcount[b0 * C:b1 * C], nms_thr, rotated)
             keep_l.append(k_)
             kc_l.append(c_n)
+        if nev is not None:
+            nev[1].record()
+            self.nms_events.append(nev)
         keep2 = keep_l[0] if len(keep_l) == 1 else torch.cat(keep_l)
         kc2 = kc_l[0] if len(kc_l) == 1 else torch.cat(kc_l)
+        # ---- box voting (test_cfg.vote_thr; off: nothing is launched): every kept box becomes the score-weighted mean of the
+        # segment's candidates that overlap it, in a full copy of the table that the second merge reads in place of `mb` ----------
+        vote_thr = vote_cfg(self.test_cfg)
+        if vote_thr is not None:
+            vev = None
+            if self.vote_events is not None:
+                vev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                vev[0].record()
+            mb = vote_segments(mb, ms, mcount, keep2, kc2, vote_thr, rotated, yaw_flag, members=self.vote_members is not None)
+            if self.vote_members is not None:
+                mb, mem = mb
+                self.vote_members.append((mem, kc2))
+            if vev is not None:
+                vev[1].record()
+                self.vote_events.append(vev)
         # ---- scene: the C class lists into one descending list, cut to max_num ---------------------------------------------
         g = np.arange(B * C, dtype=np.int64)
         desc2 = np.stack((g, g * S1, g * S1, np.full_like(g, transform_word(1.0, False, False))), -1)

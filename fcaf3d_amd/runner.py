@@ -479,15 +479,38 @@ def evaluate(model, batches, gt_annos, metric=(0.25, 0.5), label2cat=None, in_fl
     evaluation.indoor_eval_device ONCE, after the last batch.  More than one rank: each passes its own batches, gt_annos and
     global scene_ids (default rank + world_size * i); the ranks' tables are gathered over `group`, every rank returns the same
     dict.  Runs in eval mode under no_grad and leaves the model in the mode it found it in.  label2cat=None names a class by its
-    number."""
+    number.
+    Test-time augmentation: a batch whose img_metas is nested (img_metas[a][b], points[a][b] as aug_test takes them; a
+    data.AugDeviceLoader batch carries all copies as `points.flat`) goes through extract_feat on the flat batch and
+    get_bboxes_aug, whose merge runs on the device; its two read-backs are not deferred, so before they are waited for the NEXT
+    batch's coordinate phase is started on the planner's worker thread (model.prefetch on its `.flat`)."""
     from .evaluation import indoor_eval_device
     modes = [(m, m.training) for m in model.modules()]                 # every module's own flag: frozen parts stay frozen
     if any(t for _, t in modes):
         model.eval()
     pending, dets = [], []
+
+    def nested(item):
+        return len(item[1]) > 0 and isinstance(item[1][0], (list, tuple))
+
+    def flat_of(points):
+        return points.flat if hasattr(points, 'flat') else [p for pa in points for p in pa]
     try:
         with torch.no_grad():
-            for points, img_metas in batches:
+            it = iter(batches)
+            cur = next(it, None)
+            while cur is not None:
+                nxt = next(it, None)                                   # one item ahead: the batch after this one
+                points, img_metas = cur
+                cur = nxt
+                if nested((points, img_metas)):
+                    x = model.extract_feat(flat_of(points), [m for ma in img_metas for m in ma])
+                    if nxt is not None and nested(nxt) and hasattr(nxt[0], 'flat') and hasattr(model, 'prefetch'):
+                        model.prefetch(nxt[0].flat, gt=False)
+                    while pending:                                     # results stay in batch order
+                        dets.extend(pending.pop(0)())
+                    dets.extend(model.neck_with_head.get_bboxes_aug(*x, img_metas))
+                    continue
                 x = model.extract_feat(points, img_metas)
                 pending.append(model.neck_with_head.get_bboxes(*x, img_metas, defer=True))
                 if len(pending) >= max(int(in_flight), 1):
@@ -583,7 +606,8 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                          BEFORE the TrainStep builds its flat buffers, the run starts at epoch 1, iteration 0 with a fresh
                          optimizer, and the load report is written once to the log as a record with mode 'load'
 
-    train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`).  Under
+    train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`; a validation
+    pipeline that asks for test-time augmentation, MultiScaleFlipAug3D(flip=True), gets a data.AugDeviceLoader: build_val_loader).  Under
     torch.distributed every rank calls fit: the loaders shard, rank 0 alone writes files, evaluate gathers over the group.
     on_batch(epoch, iteration, batch): called before every step (tests, progress bars).  step: a TrainStep to reuse (default:
     TrainStep.from_config(model, cfg)).  Returns the log records (dicts, train and val, in order)."""
@@ -598,7 +622,7 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     ev_interval = int(ev.get('interval', 0) or 0)
     if val_loader is None and ev_interval > 0 and cfg.get('data', {}).get('val') is not None:
         vs = DT.build_dataset(cfg.data.val)
-        val_loader = DT.DeviceLoader(DT.ResidentScenes(vs, device, max_gb), vs.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
+        val_loader = build_val_loader(DT.ResidentScenes(vs, device, max_gb), vs.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
     if load_from is None:
         load_from = cfg.get('load_from')
     load_report = None
@@ -657,6 +681,15 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
             res = {k: float(v) if isinstance(v, (int, float, np.generic)) else v for k, v in res.items()}
             log.write(dict(mode='val', epoch=epoch + 1, iter=len(batches), lr=tr.optimizer.param_groups[0]['lr'], **res))
     return log.records
+
+
+def build_val_loader(resident, pipeline_cfg, samples_per_gpu, seed=0, rank=0, world_size=1):
+    """the validation loader of `fit`: data.AugDeviceLoader when the pipeline's MultiScaleFlipAug3D asks for more than one augmentation
+    (test-time augmentation: flip=True, several pts_scale_ratio), data.DeviceLoader otherwise"""
+    from . import data as DT
+    _, augs = DT.parse_aug_pipeline(pipeline_cfg)
+    cls = DT.AugDeviceLoader if len(augs) > 1 else DT.DeviceLoader
+    return cls(resident, pipeline_cfg, samples_per_gpu, seed, rank, world_size)
 
 
 def validate(model, val_loader, metric=(0.25, 0.5), label2cat=None):

@@ -273,7 +273,8 @@ class SingleStageSparse3DDetector(nn.Module):
         B = len(points[0])
         assert all(len(p) == B for p in points) and all(len(m) == B for m in img_metas), \
             'every augmentation must hold the same B scenes'
-        flat_points = [p for pa in points for p in pa]
+        # a batch that carries its copies as one DeviceBatch (data.AugBatch): all A * B voxelised by one launch
+        flat_points = points.flat if hasattr(points, 'flat') else [p for pa in points for p in pa]
         flat_metas = [m for ma in img_metas for m in ma]
         x = self.extract_feat(flat_points, flat_metas)
         bbox_list = self.neck_with_head.get_bboxes_aug(*x, img_metas, rescale=rescale)

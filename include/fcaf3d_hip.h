@@ -41,9 +41,10 @@ extern "C" {
  * (fc_norm_act_maxpool8_mask_fwd / fc_maxpool8_mask_norm_act_bwd added: the stem's tail with a per-child arg-max mask), -> 16 (fc_adamw_groups_table_bytes /
  * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers), -> 17 (fc_bn_eval_bwd / fc_bn_eval_bwd_ws_bytes /
  * fc_bn_eval_bwd_route added: the backward through a BatchNorm that reads its running statistics), -> 18 (fc_x6_weight_images takes the
- * grid of its amax pass, amax_chunks / amax_blocks; fc_x6_amax_units / fc_x6_weight_images_passes added).  A caller built against
+ * grid of its amax pass, amax_chunks / amax_blocks; fc_x6_amax_units / fc_x6_weight_images_passes added), -> 19 (fc_vote_boxes added: box
+ * voting between the merge NMS and the per-scene merge of test-time augmentation).  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
-#define FC_ABI_VERSION 18
+#define FC_ABI_VERSION 19
 #ifndef FC_AMAX_SLOT_BYTES
 #define FC_AMAX_SLOT_BYTES 2048
 #endif
@@ -678,6 +679,29 @@ int fc_merge_sorted_segments(const int64_t* desc, int nseg_out, int K, const int
                              const int64_t* ord, int ord_stride, const float* scores, int score_stride, const float* boxes,
                              int flags, int max_total, int cap, float* out_boxes, float* out_scores, int* out_src,
                              int* out_count, int stride_out, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+/* ---- test-time augmentation: box voting (fcaf3d_amd/csrc_post/vote.hip) -------------------------------------------------- */
+
+/* `flags` of fc_vote_boxes: FC_VOTE_ROTATED takes the rotated BEV IoU (as fc_nms_bev with rotated = 1; otherwise the axis-aligned
+ * one), FC_VOTE_WITH_YAW lets a member whose yaw differs from the kept box's by about a quarter turn vote with its sides exchanged. */
+#define FC_VOTE_ROTATED 1
+#define FC_VOTE_WITH_YAW 2
+/* No reference counterpart (merge_aug_bboxes_3d keeps the NMS survivors as they are): box voting on the tables of fc_nms_bev.
+ * boxes (nseg, stride, 7) and scores (nseg, stride), segment s holding counts_dev[s] <= max_count <= stride rows by descending
+ * score; keep (nseg, keep_stride) the ascending kept positions fc_nms_bev wrote, keep_counts_dev[s] <= max_keep <= keep_stride of
+ * them (max_count / max_keep: host bounds, larger device counts are cut to them; max_keep sizes the grid).  For every kept
+ * position i of segment s the members are M = {i} and every j != i, j < count, with iou(i, j) >= vote_thr — the fp32 BEV IoU of
+ * the NMS with a = box i, b = box j; a NaN is not a member — and
+ *   out[i][k] = fp32( sum_{j in M} score_j * box_j[k] / sum_{j in M} score_j ), k = 0..5, both sums in fp64 over ascending j;
+ *   out[i][6] = boxes[i][6].
+ * FC_VOTE_WITH_YAW: d = remainder(yaw_j - yaw_i, fp32 pi); |d| > pi / 4: member j contributes (box_j[4], box_j[3]) to columns
+ * (3, 4).  A weight sum that is not positive and finite leaves box i unchanged.  Rows that are not kept are copied to out_boxes
+ * (nseg, stride, 7); rows at or past counts_dev[s] are neither read nor written; out_boxes must not alias boxes.  out_members
+ * (nseg, keep_stride) int32, nullable: |M| per kept position.  0 < vote_thr <= 1.  One launch, no atomics: deterministic.
+ * nseg == 0 or max_count == 0 launches nothing. */
+int fc_vote_boxes(const float* boxes, const float* scores, const int* counts_dev, int nseg, int stride, int max_count,
+                  const int* keep, const int* keep_counts_dev, int keep_stride, int max_keep, float vote_thr, int flags,
+                  float* out_boxes, int* out_members, hipStream_t stream);
 
 /* ---- evaluation: detection-to-ground-truth matching (fcaf3d_amd/csrc_post/eval.hip) ----------------------------------- */
 
