@@ -24,6 +24,16 @@ __device__ static inline bool fc_coord_out_of_range(int4 c) {
          c.w < -FC_COORD_LIMIT || c.w > FC_COORD_LIMIT;
 }
 
+// the same for a voxel ALREADY rounded down to stride q (fc_hash_unique builds a strided set from an accepted one): rounding takes
+// -FC_COORD_LIMIT to -(FC_COORD_LIMIT + 1) = -510 * 64, a multiple of every stride of the pyramid, and that voxel is a member of the
+// set like any other — its key fields still hold the largest kernel offset (128 - 64 >= 0).  The plan's chain checks the raw rows of
+// level 0 only and accepts it; held to the raw limit, the per-operator path refused every scene with a voxel at -32 639 as soon as
+// it was strided (tests/test_gpu_coords_exact.py: range_limit, edge_*_neg_32639).  q = 1 is the raw rule.
+__device__ static inline bool fc_voxel_out_of_range(int4 c, int q) {
+  const int lo = q > 1 ? -(FC_COORD_LIMIT + 1) : -FC_COORD_LIMIT;
+  return c.x < 0 || c.x > 32767 || c.y < lo || c.y > FC_COORD_LIMIT || c.z < lo || c.z > FC_COORD_LIMIT || c.w < lo || c.w > FC_COORD_LIMIT;
+}
+
 // row i into the voxel hash (linear probing): the first occurrence (smallest row) wins — SURVEY.md Appendix A.2; slot[i] = where.
 // I: the caller's row index type
 template <typename I>

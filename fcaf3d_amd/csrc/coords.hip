@@ -264,13 +264,13 @@ __global__ void k_table_init(unsigned long long* __restrict__ keys, int* __restr
   }
 }
 
-// `bad` (nullable): set when a coordinate is out of the range of the hash keys (fc_coord_out_of_range).
+// `bad` (nullable): set when a voxel is out of the range of the hash keys (fc_voxel_out_of_range: the raw rule for q = 1).
 __global__ void k_hash_insert(const int4* __restrict__ coords, int64_t n, int q, unsigned long long* keys, int* vals,
                               unsigned long long mask, int* __restrict__ slot, int* __restrict__ bad) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int4 c = fc_quantize(coords[i], q);
-  if (bad && fc_coord_out_of_range(c)) *bad = 1;
+  if (bad && fc_voxel_out_of_range(c, q)) *bad = 1;
   fc_hash_insert(keys, vals, mask, c, i, slot);
 }
 

@@ -181,7 +181,9 @@ class KernelMap(_Lazy):
     def _sort_table(nbr, n_rows, K):
         masks = torch.empty(n_rows, dtype=torch.int32, device=nbr.device)
         L.call('fc_nbr_row_masks', L.ptr(nbr), n_rows, K, L.ptr(masks), L.stream())
-        order = torch.argsort(masks).to(torch.int32)
+        # stable: rows of one mask stay in row order — the native plan's radix argsort is, and the two phases promise the same tables
+        # (the default argsort is not on short inputs: tests/test_gpu_coords_exact.py, every case of a few dozen rows)
+        order = torch.argsort(masks, stable=True).to(torch.int32)
         tab = torch.empty_like(nbr)
         L.call('fc_permute_nbr', L.ptr(nbr), L.ptr(order), n_rows, K, L.ptr(tab), L.stream())
         return _rec(tab, order)

@@ -1,7 +1,12 @@
 """-m gpu: the native coordinate phase (fcaf3d_amd/plan.py + csrc/plan.hip: fc_plan_levels + fc_plan_maps, two read-backs per step)
-against the per-operator coordinate phase (fcaf3d_amd/sparse.py + csrc/coords.hip, itself held bit-exact against oracle/me_oracle.py
-by tests/test_gpu_ops.py): every coordinate set, voxel hash LOOKUP, kernel map, derived table, union row and head array must be
-identical — integer work, bit for bit (indices / kernel maps bit-exact)."""
+against the per-operator coordinate phase (fcaf3d_amd/sparse.py + csrc/coords.hip): every coordinate set, voxel hash LOOKUP, kernel
+map, derived table, union row and head array must be identical — integer work, bit for bit (indices / kernel maps
+bit-exact).  This is HIP against HIP on synthetic rooms: both phases inline csrc/coord_rules.h and the hash of csrc/fc_common.h, so a
+mistake in a shared rule is equal on both sides.  What holds either phase to something else: tests/test_gpu_ops.py compares the
+per-operator phase with oracle/me_oracle.py on the same rooms (sets at strides 1 / 2 / 4, the ks 3 / 2 / 1 maps of one scene pair, pair
+lists, generate / union) — nearly all coordinates positive, tables half empty; tests/test_gpu_coords_exact.py (per-operator) and
+tests/test_gpu_plan_exact.py (the plan) compare each phase with the numpy references of tests/coord_cases.py on crafted rows:
+negative and odd coordinates, the range limit, probe chains that wrap, block edges, offsets without pairs, up to 65 scenes."""
 import numpy as np
 import pytest
 import torch

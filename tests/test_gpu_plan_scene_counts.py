@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from fcaf3d_amd import _lib as L
-from fcaf3d_amd import plan as PL
 from fcaf3d_amd import sparse as SP
+from tests.plan_abi import plan_levels
 
 pytestmark = pytest.mark.gpu
 
@@ -59,29 +58,7 @@ CASES = _cases()
 
 def _plan_levels(coords, feats, B):
     """fc_plan_levels alone on pre-voxelised rows -> (coordinate sets, rows per (set, scene), level-0 features)"""
-    dev = coords.device
-    T, nfeat = coords.shape[0], feats.shape[1]
-    lib = L.lib()
-    cfg = np.zeros(lib.fc_plan_cfg_words(), dtype=np.int64)
-    cfg[PL.C_B], cfg[PL.C_NL], cfg[PL.C_NFEAT], cfg[PL.C_TOTAL] = B, NL, nfeat, T
-    cfg[PL.C_COORDS_IN], cfg[PL.C_FEATS_IN] = coords.data_ptr(), feats.data_ptr()
-    scenes = np.zeros((B, 3), dtype=np.int64)
-    out = np.zeros(lib.fc_plan_out_words(B, NL), dtype=np.int64)
-    counts = torch.zeros(PL.pinned_words(B, NL)[0], dtype=torch.int32).pin_memory()
-    arena = torch.empty(L.query('fc_plan_stage1_bytes', T, B, NL, nfeat), dtype=torch.uint8, device=dev)
-    rc = lib.fc_plan_levels(cfg.ctypes.data, scenes.ctypes.data, arena.data_ptr(), arena.numel(), out.ctypes.data, counts.data_ptr(), L.stream())
-    assert rc == 0 and not out[PL.H_BAD] and out[PL.H_S] == S
-    torch.cuda.synchronize()
-    ar = PL._Arenas(arena, arena)
-    cn = counts.numpy()
-    sets = []
-    for s in range(S):
-        o = out[PL.HDR + PL.SETW * s:PL.HDR + PL.SETW * (s + 1)]
-        assert int(o[PL.S_N]) == int(cn[PL.METAW * s + PL.META_ROWS]) and int(o[PL.S_STRIDE]) == 1 << s
-        sets.append(ar.view(int(o[PL.S_COORDS]), (int(o[PL.S_N]), 4)).clone())
-    per_scene = cn[PL.METAW * S:PL.METAW * S + S * B].reshape(S, B).copy()
-    F0 = ar.view(int(out[PL.H_F0]), (sets[0].shape[0], nfeat), torch.float32).clone()
-    return sets, per_scene, F0
+    return plan_levels(coords, feats, B, NL)
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
