@@ -1,15 +1,14 @@
-// Rotated-BEV rectangle overlap for the post-processing kernels (csrc_post/eval.hip, csrc_post/vote.hip).
+// Rotated-BEV rectangle overlap, stated once: the NMS (csrc/nms.hip) and the post-processing kernels that must agree with it to the
+// bit (csrc_post/eval.hip, csrc_post/vote.hip) all compile these functions.  The header lives in csrc/ because a csrc/ kernel depends
+// on it, so build.source_hash() has to cover it; a change here is a change of the NMS.
 //
-// THIS IS A COPY of the geometry of csrc/nms.hip:16-117 (seg_cross / in_box_bev / box_corners / bev_overlap_rotated and the two IoUs), kept
-// operation for operation so that the two give the same fp32 value.  It is duplicated, not shared, on purpose: nothing under
-// csrc/ may change without retaking every profile under profiles/ — build.source_hash() covers csrc/*.hip and csrc/*.h and
-// tests/test_host_logic.py pins the committed profiles to it — and moving these functions into a header both files include
-// would change that hash.  tests/test_gpu_eval.py compares the evaluation kernel's IoU with nms.boxes_iou3d_gpu; a change
-// to csrc/nms.hip's geometry has to be repeated here.
-//
-// The including file sets `#pragma clang fp contract(off)` first (exact products, as in csrc/nms.hip).
+// Exact products, as the reference's torch / host code computes them (e.g. num == 0 for parallel edges): every function that does
+// arithmetic switches FMA contraction off in its own body, so the result does not depend on the including file and the including
+// file's setting is left alone.
 #pragma once
+#ifdef __HIP__                 // the host emulators (tools/*_host_emu.cpp) compile this text as plain C++ with the qualifiers defined away
 #include <hip/hip_runtime.h>
+#endif
 
 #define EVG_EPS 1e-8f
 
@@ -18,11 +17,13 @@ namespace evg {
 struct P2 { float x, y; };
 
 __device__ static inline float cross3(P2 p1, P2 p2, P2 p0) {
+#pragma clang fp contract(off)
   return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
 }
 
 // proper crossing of segments p0p1 and q0q1 (touching / collinear do not count)
 __device__ static inline bool seg_cross(P2 p1, P2 p0, P2 q1, P2 q0, P2* out) {
+#pragma clang fp contract(off)
   bool overlap = fminf(p0.x, p1.x) <= fmaxf(q0.x, q1.x) && fminf(q0.x, q1.x) <= fmaxf(p0.x, p1.x) &&
                  fminf(p0.y, p1.y) <= fmaxf(q0.y, q1.y) && fminf(q0.y, q1.y) <= fmaxf(p0.y, p1.y);
   if (!overlap) return false;
@@ -44,6 +45,7 @@ __device__ static inline bool seg_cross(P2 p1, P2 p0, P2 q1, P2 q0, P2* out) {
 }
 
 __device__ static inline bool in_box_bev(const float* box, P2 p) {
+#pragma clang fp contract(off)
   const float MARGIN = 1e-2f;
   float c = cosf(-box[6]), s = sinf(-box[6]);
   float rx = (p.x - box[0]) * c + (p.y - box[1]) * (-s);
@@ -52,6 +54,7 @@ __device__ static inline bool in_box_bev(const float* box, P2 p) {
 }
 
 __device__ static inline void box_corners(const float* box, P2* c /*[5]*/) {
+#pragma clang fp contract(off)
   float hx = box[3] / 2, hy = box[4] / 2;
   float cs = cosf(box[6]), sn = sinf(box[6]);
   const float sx[4] = {-1.f, 1.f, 1.f, -1.f}, sy[4] = {-1.f, -1.f, 1.f, 1.f};
@@ -66,6 +69,7 @@ __device__ static inline void box_corners(const float* box, P2* c /*[5]*/) {
 
 // area of the intersection polygon of two rotated BEV rectangles (x,y,_,dx,dy,_,heading)
 __device__ static float bev_overlap_rotated(const float* a, const float* b) {
+#pragma clang fp contract(off)
   P2 ca[5], cb[5], pts[24];
   box_corners(a, ca);
   box_corners(b, cb);
@@ -102,15 +106,17 @@ __device__ static float bev_overlap_rotated(const float* a, const float* b) {
   return fabsf(area) / 2.f;
 }
 
-// csrc/nms.hip:105-117, the two BEV IoUs of the NMS (what fc_nms_bev compares with its threshold and fc_boxes_iou_bev stores), the
-// same fp32 operations in the same order (csrc_post/vote.hip: a = the kept box, b = the candidate)
+// the two BEV IoUs of the NMS: what fc_nms_bev compares with its threshold and fc_boxes_iou_bev stores (csrc_post/vote.hip: a = the
+// kept box, b = the candidate)
 __device__ static inline float iou_bev_rotated(const float* a, const float* b) {
+#pragma clang fp contract(off)
   float sa = a[3] * a[4], sb = b[3] * b[4];
   float ov = bev_overlap_rotated(a, b);
   return ov / fmaxf(sa + sb - ov, EVG_EPS);
 }
 
 __device__ static inline float iou_bev_aligned(const float* a, const float* b) {
+#pragma clang fp contract(off)
   float left = fmaxf(a[0] - a[3] / 2, b[0] - b[3] / 2), right = fminf(a[0] + a[3] / 2, b[0] + b[3] / 2);
   float top = fmaxf(a[1] - a[4] / 2, b[1] - b[4] / 2), bottom = fminf(a[1] + a[4] / 2, b[1] + b[4] / 2);
   float w = fmaxf(right - left, 0.f), h = fmaxf(bottom - top, 0.f);
@@ -118,9 +124,10 @@ __device__ static inline float iou_bev_aligned(const float* a, const float* b) {
   return inter / fmaxf(a[3] * a[4] + b[3] * b[4] - inter, EVG_EPS);
 }
 
-// csrc/nms.hip:105-109 (what fc_boxes_iou_bev stores), then fcaf3d_amd/nms.py:86-96 (boxes_iou3d_gpu) on that value, the same
-// fp32 operations in the same order: a = detection, b = ground truth, both (x, y, z, dx, dy, dz, heading) gravity centre
+// iou_bev_rotated's value, then fcaf3d_amd/nms.py:86-96 (boxes_iou3d_gpu) on it, the same fp32 operations in the same order
+// (csrc_post/eval.hip only): a = detection, b = ground truth, both (x, y, z, dx, dy, dz, heading) gravity centre
 __device__ static inline float iou3d_rotated(const float* a, const float* b) {
+#pragma clang fp contract(off)
   const float sa = a[3] * a[4], sb = b[3] * b[4];
   const float ov = bev_overlap_rotated(a, b);
   const float iou = ov / fmaxf(sa + sb - ov, EVG_EPS);

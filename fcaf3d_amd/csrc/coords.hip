@@ -8,6 +8,7 @@
 //   fcaf3d_neck_with_head.py:101 (union), :115-116 (features_at_coordinates), :125 (pruning).
 #include "fc_common.h"
 #include "coord_rules.h"      // the rules this path shares with the native plan (plan.hip)
+#include "aug_point.h"        // the point transform k_augment_voxelize shares with csrc_post/batch.hip
 
 extern "C" {
 
@@ -57,24 +58,8 @@ __global__ void k_augment_voxelize(const float* __restrict__ pts, int64_t n_src,
   if (i >= n_out) return;
   const int64_t src = sample ? sample[i] : i;
   const float* p = pts + src * pt_stride;
-  float x = p[0], y = p[1], z = p[2];
-  const float* a = xf.v;
-  if (a[12] != 0.f) {                                   // GlobalAlignment: points.rotate(R^T) then translate
-    const float nx = (x * a[0] + y * a[1]) + z * a[2];
-    const float ny = (x * a[3] + y * a[4]) + z * a[5];
-    const float nz = (x * a[6] + y * a[7]) + z * a[8];
-    x = nx + a[9]; y = ny + a[10]; z = nz + a[11];
-  }
-  if (a[13] != 0.f) x = -x;                             // RandomFlip3D 'horizontal'
-  if (a[14] != 0.f) y = -y;                             // ... 'vertical'
-  {                                                     // GlobalRotScaleTrans: p @ rot_T, rot_T = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-    const float c = a[15], sn = a[16];
-    const float nx = x * c - y * sn;
-    const float ny = x * sn + y * c;
-    x = nx * a[17] + a[18];
-    y = ny * a[17] + a[19];
-    z = z * a[17] + a[20];
-  }
+  const AugP q = aug_point(p[0], p[1], p[2], xf.v);
+  const float x = q.x, y = q.y, z = q.z;
   int4 cd;
   cd.x = b;
   cd.y = (int)floorf(x / vs);

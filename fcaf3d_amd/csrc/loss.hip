@@ -8,18 +8,11 @@
 //     fused kernel: the gradient is propagated in forward mode (7 dual parts per value) through the
 //     same arithmetic graph torch autograd differentiates in the reference.
 #include "fc_common.h"
+#include "box_math.h"     // sort_key, tie_max / tie_min, axis_overlap, axis_iou_grad  } shared with csrc_post/eiou.hip; both set their
+#include "dual7.h"        // D7 and its operators, V2                                 } own contraction
 // exact products as in the reference's torch / host code (e.g. num == 0 for parallel edges): no FMA contraction
 #pragma clang fp contract(off)
 #include <float.h>
-
-// Angular sort key of sort_v ("sign of y, then |x| x / (x^2 + y^2)", eps 1e-8): monotone in
-// atan2(y, x) over (-pi, pi], built from +, *, / only — with contraction off it is bit-identical to the numpy restatement
-// (oracle/loss_oracle.py::sort_key), so the index order is EXACT across machines (r1/r2 used atan2f: two libms ordered
-// ~0.5 % of near-tied vertices differently).
-__device__ static inline float sort_key(float y, float x) {
-  const float r = x * fabsf(x) / (x * x + y * y + 1e-8f);
-  return y < 0.f ? r - 3.f : 1.f - r;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // t^gamma; gamma == 2 (every FCAF3D config, fcaf3d_neck_with_head.py:29-34) is the plain product — what torch's pow
@@ -59,36 +52,17 @@ __global__ void k_focal_bwd(const float* __restrict__ x, const long long* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------
-// torch.max / torch.min split the gradient evenly on ties; clamp(min=0) passes it at x >= 0.
-__device__ static inline void tie_max(float a, float b, float* v, float* wa) {
-  *v = a > b ? a : b;
-  *wa = a > b ? 1.f : (a == b ? 0.5f : 0.f);
-}
-__device__ static inline void tie_min(float a, float b, float* v, float* wa) {
-  *v = a < b ? a : b;
-  *wa = a < b ? 1.f : (a == b ? 0.5f : 0.f);
-}
-
 // p, t: [cx,cy,cz,w,l,h]; returns the IoU, writes d IoU / d p into dp[6] when dp != NULL (the gradient torch autograd
 // gives through max / min / clamp of iou3d_calculator.py:201-330, ties split evenly)
 __device__ static inline float aiou3d_eval(const float* __restrict__ p, const float* __restrict__ t, float eps, float* dp) {
   float wh[3], dwh_dc[3], dwh_ds[3], sp[3];
   float a1 = 1.f, a2 = 1.f, ov = 1.f;
   for (int a = 0; a < 3; ++a) {
-    float p1 = p[a] - p[3 + a] / 2, p2 = p[a] + p[3 + a] / 2;
-    float t1 = t[a] - t[3 + a] / 2, t2 = t[a] + t[3 + a] / 2;
-    float lt, rb, wl, wr;
-    tie_max(p1, t1, &lt, &wl);       // d lt / d p1
-    tie_min(p2, t2, &rb, &wr);       // d rb / d p2
-    float d = rb - lt;
-    float pass = d >= 0.f ? 1.f : 0.f;
-    wh[a] = d > 0.f ? d : 0.f;
-    // wh = clamp(rb - lt): d/dc = wr - wl ; d/ds = wr/2 + wl/2
-    dwh_dc[a] = pass * (wr - wl);
-    dwh_ds[a] = pass * 0.5f * (wr + wl);
-    sp[a] = p2 - p1;
+    const AxisOverlap o = axis_overlap(p[a], p[3 + a], t[a], t[3 + a]);
+    wh[a] = o.wh; dwh_dc[a] = o.dwh_dc; dwh_ds[a] = o.dwh_ds;
+    sp[a] = o.p2 - o.p1;
     a1 *= sp[a];
-    a2 *= (t2 - t1);
+    a2 *= (o.t2 - o.t1);
     ov *= wh[a];
   }
   float un = a1 + a2 - ov;
@@ -97,14 +71,9 @@ __device__ static inline float aiou3d_eval(const float* __restrict__ p, const fl
   if (dp) {
     for (int a = 0; a < 3; ++a) {
       int b = (a + 1) % 3, c = (a + 2) % 3;
-      float dov_dwh = wh[b] * wh[c];
-      float dov_dc = dov_dwh * dwh_dc[a];
-      float dov_ds = dov_dwh * dwh_ds[a];
-      float da1_ds = sp[b] * sp[c];          // area1 = prod (p2-p1): d/ds_a = prod of the others
-      float dU_dc = upass * (-dov_dc);
-      float dU_ds = upass * (da1_ds - dov_ds);
-      dp[a] = (dov_dc * U - ov * dU_dc) / (U * U);
-      dp[3 + a] = (dov_ds * U - ov * dU_ds) / (U * U);
+      const AxisIouGrad g = axis_iou_grad(wh[b], wh[c], dwh_dc[a], dwh_ds[a], sp[b], sp[c], ov, U, upass);
+      dp[a] = g.diou_dc;
+      dp[3 + a] = g.diou_ds;
     }
   }
   return ov / U;
@@ -330,35 +299,7 @@ int fc_fcaf3d_loss_bwd(const float* points, const float* bbox_pred, const float*
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------
-// rotated 3D IoU with forward-mode derivatives w.r.t. the 7 parameters of `pred`
-struct D7 {
-  float v;
-  float d[7];
-};
-__device__ static inline D7 dconst(float c) { D7 r; r.v = c; for (int i = 0; i < 7; ++i) r.d[i] = 0.f; return r; }
-__device__ static inline D7 dvar(float c, int i) { D7 r = dconst(c); r.d[i] = 1.f; return r; }
-__device__ static inline D7 operator+(const D7& a, const D7& b) { D7 r; r.v = a.v + b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
-__device__ static inline D7 operator-(const D7& a, const D7& b) { D7 r; r.v = a.v - b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
-__device__ static inline D7 operator*(const D7& a, const D7& b) { D7 r; r.v = a.v * b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
-__device__ static inline D7 operator/(const D7& a, const D7& b) {
-  D7 r; r.v = a.v / b.v; float inv = 1.f / b.v;
-  for (int i = 0; i < 7; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * inv;
-  return r;
-}
-__device__ static inline D7 dscale(const D7& a, float s) { D7 r; r.v = a.v * s; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] * s; return r; }
-__device__ static inline D7 dmin_tie(const D7& a, const D7& b) {     // torch.min(a,b): ties split the gradient
-  if (a.v < b.v) return a;
-  if (b.v < a.v) return b;
-  return dscale(a + b, 0.5f);
-}
-__device__ static inline D7 dmax_tie(const D7& a, const D7& b) {
-  if (a.v > b.v) return a;
-  if (b.v > a.v) return b;
-  return dscale(a + b, 0.5f);
-}
-
-struct V2 { D7 x, y; };
-
+// rotated 3D IoU with forward-mode derivatives w.r.t. the 7 parameters of `pred` (D7, V2: dual7.h)
 __device__ static void corners_of(const D7& cx, const D7& cy, const D7& w, const D7& h, const D7& alpha, V2* out) {
   const float sx[4] = {0.5f, -0.5f, -0.5f, 0.5f}, sy[4] = {0.5f, 0.5f, -0.5f, -0.5f};
   D7 cs, sn;

@@ -7,6 +7,7 @@
 // grad_clip max_norm 10 / norm_type 2), mmcv's OptimizerHook.after_train_iter: torch.nn.utils.clip_grad_norm_ +
 // torch.optim.AdamW.step — ~14 multi-tensor launches over 161 tensors and one extra read-modify-write of every gradient.
 #include "fc_common.h"
+#include "adamw_elem.h"     // the element update k_adamw shares with csrc_post/optim_groups.hip
 
 typedef float of4 __attribute__((ext_vector_type(4)));
 
@@ -56,9 +57,7 @@ __global__ __launch_bounds__(1024) void k_sqsum_final(const double* __restrict__
   }
 }
 
-// torch.optim.AdamW (decoupled weight decay, no amsgrad), the arithmetic of torch's own kernels:
-//   p *= 1 - lr * wd ; m += (g - m) * (1 - b1) ; v = b2 * v + (1 - b2) * g * g ;
-//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)          with g already scaled by the clip coefficient
+// torch.optim.AdamW (decoupled weight decay, no amsgrad), adamw_elem.h per element, with g scaled by the clip coefficient
 __global__ __launch_bounds__(256) void k_adamw(of4* __restrict__ p, const of4* __restrict__ g, of4* __restrict__ m,
                                                of4* __restrict__ v, int64_t n4, float lr, float b1, float b2, float eps,
                                                float wd, float step_size, float bc2_sqrt, const float* __restrict__ clip) {
@@ -69,13 +68,8 @@ __global__ __launch_bounds__(256) void k_adamw(of4* __restrict__ p, const of4* _
   const float decay = 1.f - lr * wd;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float gg = gv[j] * c;
-    float pp = pv[j] * decay;
-    const float mm = mv[j] + (gg - mv[j]) * (1.f - b1);
-    const float v2 = vv[j] * b2 + (1.f - b2) * gg * gg;
-    const float denom = sqrtf(v2) / bc2_sqrt + eps;
-    pp -= step_size * (mm / denom);
-    pv[j] = pp; mv[j] = mm; vv[j] = v2;
+    const AdamwElem r = adamw_elem(pv[j], gv[j], mv[j], vv[j], c, decay, step_size, b1, b2, eps, bc2_sqrt);
+    pv[j] = r.p; mv[j] = r.m; vv[j] = r.v;
   }
   p[i] = pv; m[i] = mv; v[i] = vv;
 }

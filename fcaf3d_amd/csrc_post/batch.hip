@@ -5,10 +5,10 @@
 //   GlobalRotScaleTrans (:493-645), then the collate of extract_feat (mmdet3d/models/detectors/single_stage_sparse.py:34-36)
 // — and what fc_augment_voxelize (csrc/coords.hip) does with one launch per scene from an index buffer somebody else drew.
 //
-// Kept apart from csrc/ as eval.hip and merge.hip are: csrc/ is what source_hash() and the profiles are pinned to.  The arithmetic
-// behind the row gather is a RESTATEMENT of k_augment_voxelize (csrc/coords.hip), operation for operation, as bev_geom.h restates
-// the BEV geometry: same products, same sums, same order, true fp32 divisions, no FMA contraction.  coords / feats are bit-equal
-// to B calls of fc_augment_voxelize with the same row indices (tests/test_gpu_batch.py).
+// Kept apart from csrc/ as eval.hip and merge.hip are: the kernel is not part of the profiled step, so source_hash() does not cover
+// it.  The transform behind the row gather is k_augment_voxelize's own (csrc/aug_point.h, shared with csrc/coords.hip), followed by
+// the same collate: true fp32 divisions, no FMA contraction.  coords / feats are bit-equal to B calls of fc_augment_voxelize with
+// the same row indices (tests/test_gpu_batch.py).
 //
 // The sampler (BATCH_* below; tests/test_batch_cpu.py restates it in numpy from this text) — all arithmetic on 32-bit unsigned
 // words, wrapping:
@@ -28,6 +28,7 @@
 //   sample_idx != NULL: the rows are read from it instead (scene s: sample_idx[idx_off + j]), nothing is drawn.
 #include "../csrc/fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "../csrc/aug_point.h"
 // exact products and sums, as csrc/coords.hip k_augment_voxelize and torch's elementwise kernels compute them: no FMA contraction
 #pragma clang fp contract(off)
 
@@ -133,26 +134,10 @@ __global__ __launch_bounds__(BATCH_THREADS) void k_batch_augment_voxelize(
   }
   const int64_t i = out_off + j;
   if (sample_out) sample_out[i] = (int)src;
-  // ---- from here on: k_augment_voxelize (csrc/coords.hip), restated ----
+  // from here on as k_augment_voxelize (csrc/coords.hip): the shared transform, then the collate
   const float* p = arena + (src_off + src) * pt_stride;
-  float x = p[0], y = p[1], z = p[2];
-  const float* a = reinterpret_cast<const float*>(d + 6);
-  if (a[12] != 0.f) {                                   // GlobalAlignment: points.rotate(R^T) then translate
-    const float nx = (x * a[0] + y * a[1]) + z * a[2];
-    const float ny = (x * a[3] + y * a[4]) + z * a[5];
-    const float nz = (x * a[6] + y * a[7]) + z * a[8];
-    x = nx + a[9]; y = ny + a[10]; z = nz + a[11];
-  }
-  if (a[13] != 0.f) x = -x;                             // RandomFlip3D 'horizontal'
-  if (a[14] != 0.f) y = -y;                             // ... 'vertical'
-  {                                                     // GlobalRotScaleTrans: p @ rot_T, rot_T = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-    const float c = a[15], sn = a[16];
-    const float nx = x * c - y * sn;
-    const float ny = x * sn + y * c;
-    x = nx * a[17] + a[18];
-    y = ny * a[17] + a[19];
-    z = z * a[17] + a[20];
-  }
+  const AugP q = aug_point(p[0], p[1], p[2], reinterpret_cast<const float*>(d + 6));
+  const float x = q.x, y = q.y, z = q.z;
   int4 cd;
   cd.x = s;
   cd.y = (int)floorf(x / vs);

@@ -3,10 +3,11 @@
 //     min_enclosing_box.py:142-172 (smallest_bounding_box over the 24 candidate lines of generate_table, :25-48);
 //   * axis-aligned boxes — iou3d_calculator.py:290-319 (mode='giou', is_aligned=True, eps = 1e-6); the aligned DIoU has no
 //     reference function: it is cal_diou_3d(enclosing_type='aligned') at yaw 0 up to the IoU's eps.
-// This file lives in csrc_post/ so that build.source_hash() — the hash every profile under profiles/ is pinned to — does not cover
-// it, and csrc/loss.hip stays as it is: the rotated intersection geometry of k_riou3d (with its forward-mode D7 derivative) and the
-// aligned IoU of aiou3d_eval are RESTATED here, as csrc_post/bev_geom.h restates the NMS geometry.  The values of iou3d / u3d are
-// computed by the same float operations in the same order as k_riou3d (contraction off), so they agree to the bit.
+// This file lives in csrc_post/ because its kernel is not part of the profiled training step: build.source_hash() — the hash every
+// profile under profiles/ is pinned to — does not cover it.  What it has in common with csrc/loss.hip is shared, not copied: the
+// forward-mode D7 numbers (csrc/dual7.h), and sort_key, tie_max / tie_min and the per-axis steps of the aligned IoU (csrc/box_math.h).
+// The rotated intersection follows k_riou3d's arithmetic graph on those operations (contraction off), so the values of iou3d / u3d
+// agree with k_riou3d's to the bit.
 //
 // What differs from k_riou3d's layout: the 24 polygon vertices are kept as plain floats (192 bytes per thread) and the derivative is
 // carried only through the <= 8 vertices of the clipped polygon, each rebuilt from the box parameters when the shoelace sum needs it;
@@ -25,6 +26,8 @@
 // with consecutive lanes, so that the geometry runs on full waves as far as the workgroup has active rows.
 #include "../csrc/fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "../csrc/box_math.h"     // sort_key, tie_max / tie_min, axis_overlap, axis_iou_grad
+#include "../csrc/dual7.h"        // D7 and its operators, V2
 // exact products as in the reference's torch code and in k_riou3d (e.g. num == 0 for parallel edges): no FMA contraction
 #pragma clang fp contract(off)
 
@@ -38,42 +41,6 @@ constexpr int EIOU_WAVES = EIOU_THREADS / 64;
 static_assert(EIOU_ROWS % EIOU_THREADS == 0 && EIOU_THREADS % 64 == 0, "a workgroup lists whole waves of rows");
 
 static inline unsigned eiou_blocks(int64_t n) { return (unsigned)((n + EIOU_ROWS - 1) / EIOU_ROWS); }
-
-// ---- forward-mode derivative w.r.t. the 7 parameters of `pred` (restated from csrc/loss.hip) -------------------------------------------
-struct D7 {
-  float v;
-  float d[7];
-};
-__device__ static inline D7 dconst(float c) { D7 r; r.v = c; for (int i = 0; i < 7; ++i) r.d[i] = 0.f; return r; }
-__device__ static inline D7 dvar(float c, int i) { D7 r = dconst(c); r.d[i] = 1.f; return r; }
-__device__ static inline D7 operator+(const D7& a, const D7& b) { D7 r; r.v = a.v + b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }
-__device__ static inline D7 operator-(const D7& a, const D7& b) { D7 r; r.v = a.v - b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
-__device__ static inline D7 operator*(const D7& a, const D7& b) { D7 r; r.v = a.v * b.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
-__device__ static inline D7 operator/(const D7& a, const D7& b) {
-  D7 r; r.v = a.v / b.v; float inv = 1.f / b.v;
-  for (int i = 0; i < 7; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * inv;
-  return r;
-}
-__device__ static inline D7 dscale(const D7& a, float s) { D7 r; r.v = a.v * s; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] * s; return r; }
-__device__ static inline D7 dsqrt(const D7& a) { D7 r; r.v = sqrtf(a.v); float h = 0.5f / r.v; for (int i = 0; i < 7; ++i) r.d[i] = a.d[i] * h; return r; }
-__device__ static inline D7 dabs(const D7& a) { return dscale(a, a.v > 0.f ? 1.f : (a.v < 0.f ? -1.f : 0.f)); }      // torch.abs: sign(0) = 0
-__device__ static inline D7 dmin_tie(const D7& a, const D7& b) {     // torch.min(a,b): ties split the gradient
-  if (a.v < b.v) return a;
-  if (b.v < a.v) return b;
-  return dscale(a + b, 0.5f);
-}
-__device__ static inline D7 dmax_tie(const D7& a, const D7& b) {
-  if (a.v > b.v) return a;
-  if (b.v > a.v) return b;
-  return dscale(a + b, 0.5f);
-}
-__device__ static inline D7 dclamp0(D7 a) {                          // clamp_min(0): the gradient passes at x >= 0
-  if (!(a.v >= 0.f)) return dconst(0.f);
-  if (a.v == 0.f) a.v = 0.f;
-  return a;
-}
-
-struct V2 { D7 x, y; };
 
 // the box whose derivative is carried: its parameters and the sine / cosine of its yaw (box2corners_th order: corner k has the
 // signs sx = +,-,-,+ and sy = +,+,-,-)
@@ -97,12 +64,6 @@ __device__ static inline void corners_f(float cx, float cy, float w, float h, fl
     x[k] = x4 * cs - y4 * sn + cx;
     y[k] = x4 * sn + y4 * cs + cy;
   }
-}
-
-// angular sort key of sort_v (restated from csrc/loss.hip: +, *, / only, bit-identical across machines)
-__device__ static inline float sort_key(float y, float x) {
-  const float r = x * fabsf(x) / (x * x + y * y + 1e-8f);
-  return y < 0.f ? r - 3.f : 1.f - r;
 }
 
 // corner (mx, my) lies inside the rectangle with corners q[0..3] (box_intersection_2d.py:57-82)
@@ -321,17 +282,8 @@ __device__ static void eiou7_row(const float* __restrict__ p, const float* __res
   for (int e = 0; e < 7; ++e) dp[e] = loss.d[e];
 }
 
-// ---- axis-aligned (restated from aiou3d_eval of csrc/loss.hip, plus the enclosing box) ---------------------------------------------------
-// torch.max / torch.min split the gradient evenly on ties; clamp(min=0) passes it at x >= 0.
-__device__ static inline void tie_max(float a, float b, float* v, float* wa) {
-  *v = a > b ? a : b;
-  *wa = a > b ? 1.f : (a == b ? 0.5f : 0.f);
-}
-__device__ static inline void tie_min(float a, float b, float* v, float* wa) {
-  *v = a < b ? a : b;
-  *wa = a < b ? 1.f : (a == b ? 0.5f : 0.f);
-}
-
+// ---- axis-aligned: the per-axis overlap and IoU gradient of aiou3d_eval (csrc/box_math.h, shared with csrc/loss.hip), with the
+// enclosing box in the same per-axis loops -------------------------------------------------------------------------------------------
 // p, t: [cx,cy,cz,w,l,h]; writes loss, iou and d loss / d p[0..5]
 __device__ static void eiou6_row(const float* __restrict__ p, const float* __restrict__ t, int kind, float* loss_o, float* iou_o,
                                  float* dp) {
@@ -339,25 +291,16 @@ __device__ static void eiou6_row(const float* __restrict__ p, const float* __res
   float wh[3], dwh_dc[3], dwh_ds[3], sp[3], ew[3], dew_dc[3], dew_ds[3];
   float a1 = 1.f, a2 = 1.f, ov = 1.f, enc = 1.f, d2 = 0.f, c2 = 0.f;
   for (int a = 0; a < 3; ++a) {
-    float p1 = p[a] - p[3 + a] / 2, p2 = p[a] + p[3 + a] / 2;
-    float t1 = t[a] - t[3 + a] / 2, t2 = t[a] + t[3 + a] / 2;
-    float lt, rb, wl, wr;
-    tie_max(p1, t1, &lt, &wl);       // d lt / d p1
-    tie_min(p2, t2, &rb, &wr);       // d rb / d p2
-    float d = rb - lt;
-    float pass = d >= 0.f ? 1.f : 0.f;
-    wh[a] = d > 0.f ? d : 0.f;
-    // wh = clamp(rb - lt): d/dc = wr - wl ; d/ds = wr/2 + wl/2
-    dwh_dc[a] = pass * (wr - wl);
-    dwh_ds[a] = pass * 0.5f * (wr + wl);
-    sp[a] = p2 - p1;
+    const AxisOverlap o = axis_overlap(p[a], p[3 + a], t[a], t[3 + a]);
+    wh[a] = o.wh; dwh_dc[a] = o.dwh_dc; dwh_ds[a] = o.dwh_ds;
+    sp[a] = o.p2 - o.p1;
     a1 *= sp[a];
-    a2 *= (t2 - t1);
+    a2 *= (o.t2 - o.t1);
     ov *= wh[a];
     // the enclosing box: lt = min, rb = max (iou3d_calculator.py:290-319)
     float elt, erb, el, er;
-    tie_min(p1, t1, &elt, &el);
-    tie_max(p2, t2, &erb, &er);
+    tie_min(o.p1, o.t1, &elt, &el);
+    tie_max(o.p2, o.t2, &erb, &er);
     float e = erb - elt;
     float epass = e >= 0.f ? 1.f : 0.f;
     ew[a] = e > 0.f ? e : 0.f;
@@ -377,22 +320,15 @@ __device__ static void eiou6_row(const float* __restrict__ p, const float* __res
   const float E = raw > eps ? raw : eps;
   for (int a = 0; a < 3; ++a) {
     int b = (a + 1) % 3, c = (a + 2) % 3;
-    float dov_dwh = wh[b] * wh[c];
-    float dov_dc = dov_dwh * dwh_dc[a];
-    float dov_ds = dov_dwh * dwh_ds[a];
-    float da1_ds = sp[b] * sp[c];          // area1 = prod (p2-p1): d/ds_a = prod of the others
-    float dU_dc = upass * (-dov_dc);
-    float dU_ds = upass * (da1_ds - dov_ds);
-    float diou_dc = (dov_dc * U - ov * dU_dc) / (U * U);
-    float diou_ds = (dov_ds * U - ov * dU_ds) / (U * U);
+    const AxisIouGrad g = axis_iou_grad(wh[b], wh[c], dwh_dc[a], dwh_ds[a], sp[b], sp[c], ov, U, upass);
     if (giou) {                            // loss = 1 - iou + (E - U) / E
       float dE_dc = Epass * ew[b] * ew[c] * dew_dc[a], dE_ds = Epass * ew[b] * ew[c] * dew_ds[a];
-      dp[a] = -diou_dc + (U * dE_dc - dU_dc * E) / (E * E);
-      dp[3 + a] = -diou_ds + (U * dE_ds - dU_ds * E) / (E * E);
+      dp[a] = -g.diou_dc + (U * dE_dc - g.dU_dc * E) / (E * E);
+      dp[3 + a] = -g.diou_ds + (U * dE_ds - g.dU_ds * E) / (E * E);
     } else {                               // loss = 1 - iou + d2 / E, E = max(c2, eps)
       float dE_dc = Epass * 2.f * ew[a] * dew_dc[a], dE_ds = Epass * 2.f * ew[a] * dew_ds[a];
-      dp[a] = -diou_dc + (2.f * (p[a] - t[a]) * E - d2 * dE_dc) / (E * E);
-      dp[3 + a] = -diou_ds + (-d2 * dE_ds) / (E * E);
+      dp[a] = -g.diou_dc + (2.f * (p[a] - t[a]) * E - d2 * dE_dc) / (E * E);
+      dp[3 + a] = -g.diou_ds + (-d2 * dE_ds) / (E * E);
     }
   }
   *iou_o = iou;

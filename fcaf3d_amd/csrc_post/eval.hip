@@ -15,9 +15,9 @@
 // Kept apart from csrc/ as merge.hip is: it never runs in the training step whose profiles csrc/ is pinned to.
 #include "../csrc/fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "../csrc/bev_geom.h"     // the NMS's BEV IoU (sets its own contraction)
 // exact products, as csrc/nms.hip and torch's elementwise kernels compute them: no FMA contraction
 #pragma clang fp contract(off)
-#include "bev_geom.h"
 
 #define EVAL_THREADS 256
 #define EVAL_GT_CHUNK 64          // ground-truth boxes staged in LDS at a time

@@ -9,14 +9,17 @@
 // of the run r its vector lies in: the run table (at most ADAMW_MAX_RUNS entries, 12 bytes each) is staged in LDS once per
 // workgroup, behind the workgroup's own loads, and every thread finds its run by binary search over the runs' first slices.
 //
-// Kept apart from csrc/ as batch.hip, eval.hip, eiou.hip and merge.hip are: csrc/ is what source_hash() and the profiles are pinned
-// to.  The arithmetic is a RESTATEMENT of k_adamw, operation for operation; with all multipliers 1 the two kernels are given the
-// same operands (lr * 1, weight_decay * 1, (lr * 1) / bias_correction1).  The host never routes that case here (runner.FlatAdamW).
+// Kept apart from csrc/ as batch.hip, eval.hip, eiou.hip and merge.hip are: the kernel is not part of the profiled step, so
+// source_hash() does not cover it.  The element update is k_adamw's own (csrc/adamw_elem.h, shared with csrc/optim.hip); with all
+// multipliers 1 the two kernels give it the same operands (lr * 1, weight_decay * 1, (lr * 1) / bias_correction1).  The host never
+// routes that case here (runner.FlatAdamW).
 //
 // tools/optim_host_emu.cpp compiles this file's text from ADAMW_THREADS to the end of the anonymous namespace for the host
-// (tests/test_finetune_cpu.py): keep that stretch free of #include lines and of anything but the constants, the search and the kernel.
+// (tests/test_finetune_cpu.py) and includes adamw_elem.h itself: keep that stretch free of #include lines and of anything but the
+// constants, the search and the kernel.
 #include "../csrc/fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "../csrc/adamw_elem.h"
 
 #include <cmath>
 #include <cstring>
@@ -74,13 +77,8 @@ __global__ __launch_bounds__(ADAMW_THREADS) void k_adamw_groups(og4* __restrict_
   const float step_size = lr_r / bc1;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float gg = gv[j] * c;
-    float pp = pv[j] * decay;
-    const float mm = mv[j] + (gg - mv[j]) * (1.f - b1);
-    const float v2 = vv[j] * b2 + (1.f - b2) * gg * gg;
-    const float denom = sqrtf(v2) / bc2_sqrt + eps;
-    pp -= step_size * (mm / denom);
-    pv[j] = pp; mv[j] = mm; vv[j] = v2;
+    const AdamwElem e = adamw_elem(pv[j], gv[j], mv[j], vv[j], c, decay, step_size, b1, b2, eps, bc2_sqrt);
+    pv[j] = e.p; mv[j] = e.m; vv[j] = e.v;
   }
   p[i] = pv; m[i] = mv; v[i] = vv;
 }

@@ -20,9 +20,9 @@
 // Kept apart from csrc/ as merge.hip is: it never runs in the training step whose profiles csrc/ is pinned to.
 #include "../csrc/fc_common.h"
 #include "../../include/fcaf3d_hip.h"
+#include "../csrc/bev_geom.h"     // the NMS's BEV IoU (sets its own contraction)
 // exact products, as csrc/nms.hip computes them: no FMA contraction
 #pragma clang fp contract(off)
-#include "bev_geom.h"
 
 #define VOTE_THREADS 256
 #define VOTE_WAVE 64

@@ -1,6 +1,6 @@
 """-m gpu: the box-voting kernel alone (csrc_post/vote.hip fc_vote_boxes) against merge_augs.vote_boxes, the per-segment statement of
 the rule in torch, on the sets of tests/vote_cases.py.  Membership on both sides comes from the same fp32 IoUs
-(nms.boxes_iou_bev = csrc/nms.hip's geometry, which csrc_post/bev_geom.h copies); the C oracle's IoUs show first that no pair
+(nms.boxes_iou_bev = csrc/nms.hip's geometry, csrc/bev_geom.h, which vote.hip includes too); the C oracle's IoUs show first that no pair
 lies within 1e-5 of the threshold, so that a last-bit difference could not move a member anyway."""
 import numpy as np
 import pytest

@@ -272,6 +272,7 @@ DEVICE_IDENTICAL_SOURCES = {
     '02ba23ed176093b4': '7094ae11604f2248',      # csrc/conv_tile.h: the kernels' shared tile prologue and weight-gradient decode; fp32 / stem kernels in headers of their own
     '2af8226cd1ab8dab': '7094ae11604f2248',      # csrc/norm_elem.h: the normalisation kernels' shared blocks; kernel families in headers of their own, norm.hip host only
     'dce6dbc252e73433': 'f5479fc07ba0b2a4',      # csrc/plan_layout.h: the coordinate plan's table layouts declared once; plan kernels in headers by family, plan.hip host only
+    '0ddbc235f7a49cfa': '4c1923be78e175fe',      # csrc/bev_geom.h, dual7.h, box_math.h, aug_point.h, adamw_elem.h: the device code csrc_post/ restated, shared instead
 }
 
 

@@ -30,6 +30,7 @@ static D3 blockIdx, gridDim;
 static std::barrier<>* g_bar;
 static void __syncthreads() { g_bar->arrive_and_wait(); }
 #pragma clang fp contract(off)
+#include "../fcaf3d_amd/csrc/aug_point.h"  // batch.hip includes it above the cut
 #include "kernels.inc"
 
 template <class F> static void launch(unsigned gx, F f) {

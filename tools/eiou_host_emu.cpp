@@ -2,7 +2,7 @@
 // __syncthreads, a barrier-backed stand-in for the wave ballot (every thread of the workgroup reaches each ballot, as in the kernel),
 // workgroups one after the other, the grid fc_eiou3d_fwd_bwd launches.  tests/test_eiou_cpu.py cuts the kernel's text (eiou.hip from
 // its EIOU_* constants to the end of its anonymous namespace: constants, grid helper, geometry, kernel — nothing is restated here)
-// into kernels.inc and builds this file with clang++ -std=c++20 -fsanitize=address,undefined: the listing of the active rows, the
+// into kernels.inc and builds this file (which includes csrc/box_math.h and csrc/dual7.h itself, as eiou.hip does above the cut) with clang++ -std=c++20 -fsanitize=address,undefined: the listing of the active rows, the
 // coalesced zero pass, every index and every bound are checked without a GPU, and the arithmetic against the float64 fixture (the
 // host's sinf / cosf are not the device's to the bit).  Every buffer has exactly the size the C ABI asks for; the outputs start as a
 // NaN pattern so that a word the kernel does not write shows.
@@ -40,6 +40,8 @@ static unsigned long long __ballot(bool p) {
 }
 static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 #pragma clang fp contract(off)
+#include "../fcaf3d_amd/csrc/box_math.h"
+#include "../fcaf3d_amd/csrc/dual7.h"
 #include "kernels.inc"
 static_assert(EIOU_THREADS <= 1024, "g_vote");
 

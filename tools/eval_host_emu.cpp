@@ -37,7 +37,7 @@ static void atomicMin(unsigned long long* p, unsigned long long v) {
   while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
 }
 #pragma clang fp contract(off)
-#include "bev_geom.h"
+#include "../fcaf3d_amd/csrc/bev_geom.h"
 #include "kernels.inc"
 
 template <class F> static void launch(unsigned gx, unsigned gy, F f) {

@@ -30,6 +30,7 @@ static void __syncthreads() { g_bar->arrive_and_wait(); }
 static float __uint_as_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
 static float fc_ld(const float* p) { return *p; }
 #pragma clang fp contract(off)
+#include "../fcaf3d_amd/csrc/adamw_elem.h"  // optim_groups.hip includes it above the cut
 #include "kernels.inc"
 
 template <class F> static void launch(unsigned gx, F f) {

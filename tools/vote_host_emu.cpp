@@ -37,7 +37,7 @@ static int __ffsll(unsigned long long v) { return __builtin_ffsll((long long)v);
 using std::max;
 using std::min;
 #pragma clang fp contract(off)
-#include "bev_geom.h"
+#include "../fcaf3d_amd/csrc/bev_geom.h"
 #include "kernels.inc"
 
 static std::barrier<>* g_wave_bar[VOTE_WAVES];
