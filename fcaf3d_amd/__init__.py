@@ -15,7 +15,7 @@ from .boxes import DepthInstance3DBoxes, bbox3d2result  # noqa: F401,E402
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401,E402
 from . import runner  # noqa: F401,E402
 from . import data  # noqa: F401,E402
-from .runner import fit  # noqa: F401,E402
+from .runner import fit, TrainStep, WeightEma  # noqa: F401,E402
 
 import os as _os
 

@@ -42,26 +42,41 @@ def load_state_dict(module, state_dict, strict=False, logger=None):
 
 
 def load_checkpoint(model, filename, map_location=None, strict=False, logger=None,
-                    revise_keys=((r'^module\.', ''),)):
+                    revise_keys=((r'^module\.', ''),), extra_keys=None):
     """mmcv.runner.load_checkpoint(model, filename, map_location, strict, logger, revise_keys) -> checkpoint dict, with the report
-    of load_state_dict (unexpected / missing / mismatched keys) under 'load_report'."""
+    of load_state_dict (unexpected / missing / mismatched keys) under 'load_report'.  extra_keys: names that are NOT the model's
+    (mmcv EMAHook's `ema_*` buffers, runner.WeightEma.names): entries under them are taken out of the state dict before the load
+    and returned under 'extra_state' (those the file holds)."""
     checkpoint = torch.load(filename, map_location=map_location, weights_only=False)
     sd = _state_dict_of(checkpoint)
     for pat, rep in revise_keys:
         sd = OrderedDict((re.sub(pat, rep, k), v) for k, v in sd.items())
+    extra = OrderedDict()
+    if extra_keys:
+        take = set(extra_keys)
+        extra = OrderedDict((k, v) for k, v in sd.items() if k in take)
+        sd = OrderedDict((k, v) for k, v in sd.items() if k not in take)
     report = load_state_dict(model, sd, strict, logger)
     if isinstance(checkpoint, dict):
         checkpoint['load_report'] = report
+        if extra_keys:
+            checkpoint['extra_state'] = extra
     return checkpoint
 
 
-def save_checkpoint(model, filename, optimizer=None, meta=None):
-    """mmcv.runner.save_checkpoint layout (weights moved to the CPU, DDP prefix stripped)."""
+def save_checkpoint(model, filename, optimizer=None, meta=None, extra_state=None):
+    """mmcv.runner.save_checkpoint layout (weights moved to the CPU, DDP prefix stripped).  extra_state: {name: tensor} written
+    into the file's state_dict behind the model's own entries (mmcv EMAHook registers its averages as module buffers, so an mmcv
+    file holds them there); a name the model already uses raises."""
     meta = dict(meta or {})
     meta.setdefault('time', time.asctime())
     meta.setdefault('fcaf3d_amd_version', __import__('fcaf3d_amd').__version__)
     module = model.module if hasattr(model, 'module') else model
     sd = OrderedDict((k, v.detach().cpu()) for k, v in module.state_dict().items())
+    for k, v in (extra_state or {}).items():
+        if k in sd:
+            raise ValueError(f'extra checkpoint entry {k!r} collides with an entry of the model')
+        sd[k] = v.detach().cpu()
     ckpt = {'meta': meta, 'state_dict': sd}
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()

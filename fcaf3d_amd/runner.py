@@ -52,14 +52,24 @@ class FlatAdamW:
         if any(mm != (1.0, 1.0) for mm in self.multipliers):
             self.runs = group_runs(flat.offsets, self.multipliers)
             self.table = torch.from_numpy(pack_runs(*self.runs, flat.n)).to(flat.data.device)      # uploaded once
+        self.ema = None                          # the weight average (enable_ema): flat.n floats laid out like flat.data
+
+    def enable_ema(self):
+        """-> the buffer of the parameters' moving average (WeightEma owns its schedule), a copy of flat.data: padding zero, and zero
+        it stays under e * keep + mu * 0"""
+        if self.ema is None:
+            self.ema = self.flat.data.clone()
+        return self.ema
 
     def zero_grad(self, set_to_none=True):
         for p in self.flat.params:
             p.grad = None                        # the flat gradient buffer is overwritten, not accumulated into
         self.flat.complete = False
 
-    def step(self, max_norm=None, gathered=False):
-        """-> the global gradient norm (0-d device tensor) when max_norm is given"""
+    def step(self, max_norm=None, gathered=False, ema=None):
+        """-> the global gradient norm (0-d device tensor) when max_norm is given.  ema: (mu, keep) of a step whose average update
+        is due (WeightEma.coeffs): the step is then ONE fc_adamw_ema_step, which updates the average of every vector it has just
+        stepped; None: exactly the call made without an average"""
         f = self.flat
         if not f.data.is_cuda:
             raise RuntimeError('FlatAdamW runs on the GPU only (HIP); CPU parameters take torch.optim.AdamW')
@@ -73,7 +83,14 @@ class FlatAdamW:
             ws = L.workspace(L.query('fc_grad_norm_ws_bytes', f.n), f.data.device)
             L.call('fc_grad_norm', L.ptr(f.grad), f.n, float(max_norm), L.ptr(self.norm_clip), L.ptr(ws), ws.numel(), L.stream())
             clip = self.norm_clip
-        if self.table is None:
+        if ema is not None:
+            if self.ema is None:
+                raise RuntimeError('FlatAdamW.step(ema=...) without an average: call enable_ema() first')
+            L.call('fc_adamw_ema_step', L.ptr(f.data), L.ptr(f.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.ema), f.n,
+                   float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']), 1.0 - b1 ** self.steps,
+                   1.0 - b2 ** self.steps, L.ptr(clip), L.ptr(self.table), len(self.runs[0]) if self.table is not None else 0,
+                   float(ema[0]), float(ema[1]), L.stream())
+        elif self.table is None:
             L.call('fc_adamw_step', L.ptr(f.data), L.ptr(f.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), f.n, float(g['lr']),
                    float(b1), float(b2), float(g['eps']), float(g['weight_decay']), 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps,
                    L.ptr(clip), L.stream())
@@ -248,6 +265,176 @@ def build_optimizer(model, cfg, flat=None):
     return torch.optim.SGD(params, **cfg)
 
 
+_EMA_KEYS = ('type', 'momentum', 'interval', 'warm_up', 'resume_from')
+
+
+def ema_hook_of(custom_hooks):
+    """-> the EMAHook dict among `cfg.custom_hooks`, or None.  EMAHook is the one custom hook implemented: any other type raises
+    KeyError naming it, and so does a key of the hook's dict that mmcv 1.3.x's EMAHook does not take"""
+    found = None
+    for hook in (custom_hooks or []):
+        kind = hook.get('type')
+        if kind != 'EMAHook':
+            raise KeyError(f'custom hook type {kind!r} is not implemented (EMAHook)')
+        for k in hook:
+            if k not in _EMA_KEYS:
+                raise KeyError(f'EMAHook key {k!r} is not implemented ({", ".join(_EMA_KEYS[1:])})')
+        if found is not None:
+            raise ValueError('custom_hooks holds more than one EMAHook')
+        found = dict(hook)
+    return found
+
+
+class WeightEma:
+    """mmcv 1.3.x EMAHook(momentum=0.0002, interval=1, warm_up=100, resume_from=None) (third party, not in the reference tree),
+    restated:
+
+      stored momentum   M = momentum ** interval                                  (0 < momentum < 1, interval an int >= 1)
+      start             every parameter gets an average e, a copy of the parameter (`attach` / `reset`)
+      step s (0-based)  s % interval != 0: nothing.  Otherwise mu = min(M, (1 + s) / (warm_up + s)) in Python floats (a zero
+                        denominator, warm_up = 0 at s = 0, counts as no bound) and, with p the parameter AFTER the optimizer step,
+                        e <- fl32( fl32(e * fl32(1 - mu)) + fl32(fl32(mu) * p) ): three fp32 roundings, no fused multiply-add
+      swap()            parameters <-> averages: `fit` swaps after every training epoch (checkpoint and validation see the
+                        average) and swaps back before the next; after the last epoch the model keeps the averaged weights
+
+    Parameters only (named_parameters): BatchNorm's running statistics are not averaged.  The average is NOT a module buffer:
+    model.state_dict(), the broadcast list and the executor's address tables stay as they are; `state_dict()` names the averages as
+    mmcv's buffers are named, 'ema_' + name.replace('.', '_'), for the checkpoint.
+    With a FlatAdamW the averages are ONE buffer laid out like flat.data and the update rides in the optimizer's launch
+    (fc_adamw_ema_step, `coeffs`); parameters outside a flat buffer (CPU, flat=False, other optimizers) keep a tensor each and take
+    three torch ops (`update`).  A frozen parameter's average is the parameter itself."""
+
+    def __init__(self, momentum=0.0002, interval=1, warm_up=100, resume_from=None):
+        if not (isinstance(interval, int) and not isinstance(interval, bool) and interval >= 1):
+            raise ValueError(f'EMAHook interval {interval!r}: an int >= 1')
+        if not 0.0 < float(momentum) < 1.0:
+            raise ValueError(f'EMAHook momentum {momentum!r}: 0 < momentum < 1')
+        if warm_up < 0:
+            raise ValueError(f'EMAHook warm_up {warm_up!r}: >= 0')
+        self.momentum = float(momentum) ** interval           # mmcv stores the power
+        self.interval, self.warm_up, self.resume_from = interval, warm_up, resume_from
+        self.swapped = False
+        self.step = None                                       # the TrainStep whose parameters are averaged (attach)
+        self.buf = None                                        # flat path: the optimizer's average buffer
+        self.named, self.tensors = [], {}                      # [(name, parameter)]; id(parameter) -> its own average tensor
+
+    @classmethod
+    def from_config(cls, hook):
+        """hook: an EMAHook dict (ema_hook_of), a WeightEma (returned as it is) or None"""
+        if hook is None or isinstance(hook, cls):
+            return hook
+        hook = ema_hook_of([hook])
+        return cls(**{k: v for k, v in hook.items() if k != 'type'})
+
+    def momentum_at(self, s):
+        """-> mu of 0-based step s, or None when no update is due"""
+        if s % self.interval:
+            return None
+        den = self.warm_up + s
+        return min(self.momentum, (1 + s) / den) if den else self.momentum
+
+    def coeffs(self, s):
+        """-> (fl32(mu), fl32(1 - mu)) as Python floats, or None when no update is due"""
+        mu = self.momentum_at(s)
+        return None if mu is None else (float(np.float32(mu)), float(np.float32(1.0 - mu)))
+
+    @staticmethod
+    def name_of(param_name):
+        return 'ema_' + param_name.replace('.', '_')
+
+    def names(self):
+        return [self.name_of(n) for n, _ in self.named]
+
+    def attach(self, step):
+        """take the averages of `step`'s model as copies of its parameters (they are final: after load_from and the broadcast)"""
+        self.step = step
+        self.named = list(step.model.named_parameters())
+        seen = {}
+        for n, _ in self.named:
+            e = self.name_of(n)
+            if e in seen:
+                raise ValueError(f'parameters {seen[e]!r} and {n!r} both map to the EMA buffer name {e!r}')
+            seen[e] = n
+        own = set(step.model.state_dict())
+        clash = [e for e in seen if e in own]
+        if clash:
+            raise ValueError(f'EMA buffer name {clash[0]!r} is an entry of the model itself')
+        self.reset()
+
+    def on_flat(self):
+        return self.step.flat is not None and isinstance(self.step.optimizer, FlatAdamW)
+
+    @torch.no_grad()
+    def reset(self):
+        """every average <- its parameter; not swapped"""
+        self.swapped, self.buf, self.tensors = False, None, {}
+        if self.on_flat():
+            opt = self.step.optimizer
+            self.buf = opt.enable_ema()
+            self.buf.copy_(opt.flat.data)
+        else:
+            self.tensors = {id(p): p.detach().clone() for _, p in self.named if p.requires_grad}
+
+    def _avg(self, p):
+        """the average of parameter p: a view of the flat buffer, its own tensor, or (frozen) the parameter itself"""
+        if p.requires_grad and self.buf is not None:
+            o = p._fc_flat[1]
+            return self.buf[o:o + p.numel()].view(p.shape)
+        return self.tensors.get(id(p), p.detach())
+
+    @torch.no_grad()
+    def update(self, s):
+        """the per-tensor path, after the optimizer step of iteration s: three torch ops, three roundings (add_(p, alpha=mu) may fuse)"""
+        c = self.coeffs(s)
+        if c is None or not self.tensors:
+            return
+        mu, keep = c
+        for _, p in self.named:
+            e = self.tensors.get(id(p))
+            if e is not None:
+                e.mul_(keep)
+                t = p.detach() * mu
+                e.add_(t)
+
+    @torch.no_grad()
+    def swap(self):
+        """parameters <-> averages.  The weights change behind every version counter: the image sets are invalidated, so the next
+        forward pass, training or inference, rebuilds the weight images before it reads them"""
+        tr = self.step
+        if self.buf is not None:
+            for s in (tr.images, getattr(tr.model, '_exec_weights', None)):
+                if s is not None:
+                    s.wait()                  # a build of the stepped weights' images on the side stream still reads them
+            f = tr.flat
+            L.call('fc_swap_f32', L.ptr(f.data), L.ptr(self.buf), f.n, L.stream())
+        for _, p in self.named:
+            e = self.tensors.get(id(p))
+            if e is not None:
+                t = p.detach().clone()
+                p.data.copy_(e)
+                e.copy_(t)
+        self.swapped = not self.swapped
+        tr.invalidate_images()
+
+    def state_dict(self):
+        """{mmcv's buffer name: the average} of every parameter, as copies (what the `ema_*` slots hold now: the raw weights while
+        swapped)"""
+        from collections import OrderedDict
+        return OrderedDict((self.name_of(n), self._avg(p).detach().clone()) for n, p in self.named)
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, swapped=True):
+        """the `ema_*` entries of a checkpoint `fit` wrote after an epoch: they hold the raw weights, the model's own entries the
+        averages, so the state is `swapped`"""
+        missing = [k for k in self.names() if k not in sd]
+        if missing:
+            raise KeyError(f'EMA state lacks {len(missing)} of {len(self.named)} entries, the first: {missing[0]!r}')
+        for n, p in self.named:
+            if p.requires_grad:
+                self._avg(p).copy_(sd[self.name_of(n)])
+        self.swapped = bool(swapped)
+
+
 class StepLrUpdater:
     """mmcv StepLrUpdaterHook with by_epoch=True: lr = base_lr * gamma ** (number of `step` entries <= epoch).
     warmup='linear' (mmcv LrUpdaterHook, warmup_by_epoch=False): before iteration `it` < warmup_iters (global, counted from 0) the
@@ -349,7 +536,9 @@ class TrainStep:
     """One optimisation step of the reference's recipe on this process's GPU (one process per GPU; gradients are averaged
     over the process group, if any, by fcaf3d_amd.dist.GradientAverager while backward is still running)."""
 
-    def __init__(self, model, optimizer_cfg, optimizer_config=None, lr_config=None, bucket_mb=64, flat=None):
+    def __init__(self, model, optimizer_cfg, optimizer_config=None, lr_config=None, bucket_mb=64, flat=None, ema=None):
+        """ema: an EMAHook dict (cfg.custom_hooks' entry) or a WeightEma: the parameters' moving average is updated with every step
+        (`self.ema`; on the flat path inside the optimizer's launch).  The average starts as a copy of the weights the model holds NOW."""
         self.model = model
         self.params = [p for p in model.parameters() if p.requires_grad]
         clip = (optimizer_config or {}).get('grad_clip')
@@ -375,10 +564,22 @@ class TrainStep:
             from .nn import MinkowskiConvolution
             self.images = ImageSet(m.kernel for m in model.modules() if isinstance(m, MinkowskiConvolution) and m.kernel.requires_grad)
         self._step_events = []
+        self.it = 0                                  # the 0-based index of the next step (set_iter; counted here otherwise)
+        self.ema = WeightEma.from_config(ema)
+        if self.ema is not None:
+            self.ema.attach(self)
 
     @classmethod
     def from_config(cls, model, cfg, **kw):
+        if kw.get('ema') is None:
+            kw['ema'] = ema_hook_of(cfg.get('custom_hooks'))
         return cls(model, cfg.optimizer, cfg.get('optimizer_config'), cfg.get('lr_config'), **kw)
+
+    def set_iter(self, it):
+        """before global iteration `it` (counted from 0): the LR updater's warm-up rate and the step index of the weight average"""
+        self.it = int(it)
+        if self.lr is not None:
+            self.lr.set_iter(it)
 
     def invalidate_images(self):
         """Call after writing the weights in a way that does not move their version counters (`p.data.copy_`,
@@ -431,12 +632,19 @@ class TrainStep:
 
     def close(self, images):
         """after the pass and the averager: clip + optimizer step, then the images of the stepped weights (weight-gradient stream)"""
+        ema = self.ema
         if isinstance(self.optimizer, FlatAdamW):    # (after finish() under data parallelism the averaged gradients sit in the flat buffer)
-            self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets))
+            if ema is None:
+                self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets))
+            else:                                    # a step whose average update is due takes it in the optimizer's launch
+                self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets), ema=ema.coeffs(self.it))
         else:
             if self.max_norm is not None:
                 self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.params, self.max_norm, norm_type=self.norm_type)
             self.optimizer.step()
+        if ema is not None:
+            ema.update(self.it)                      # parameters outside a flat buffer: three torch ops each
+        self.it += 1
         self.invalidate_images()                     # the step wrote through raw pointers (torch's fused ones too): no version counter moved
         if images is not None:
             images.rebuild_after_step(torch.cuda.current_stream(), Fn.wgrad_stream(self.flat.data.device))
@@ -576,7 +784,9 @@ def _save(model, tr, work_dir, epoch, it, seed, cfg_ck):
     import shutil
     from .checkpoint import save_checkpoint
     path = os.path.join(work_dir, f'epoch_{epoch}.pth')
-    save_checkpoint(model, path, optimizer=tr.optimizer, meta=dict(epoch=epoch, iter=it, seed=seed))
+    # with an EMAHook the file is written while swapped: the model's entries hold the averages, the `ema_*` entries the raw weights
+    save_checkpoint(model, path, optimizer=tr.optimizer, meta=dict(epoch=epoch, iter=it, seed=seed),
+                    extra_state=tr.ema.state_dict() if tr.ema is not None else None)
     shutil.copyfile(path, os.path.join(work_dir, 'latest.pth'))
     keep, interval = cfg_ck.get('max_keep_ckpts', -1), max(int(cfg_ck.get('interval', 1)), 1)
     if keep and keep > 0:
@@ -605,6 +815,11 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                          with strict=False (a head of another n_classes is reported as mismatched and keeps its initialisation)
                          BEFORE the TrainStep builds its flat buffers, the run starts at epoch 1, iteration 0 with a fresh
                          optimizer, and the load report is written once to the log as a record with mode 'load'
+      custom_hooks       [dict(type='EMAHook', momentum=0.0002, interval=1, warm_up=100)] (mmcv's, the one hook implemented): a moving
+                         average of the parameters (WeightEma).  Per epoch: swap back if swapped -> train -> epoch_end -> swap ->
+                         checkpoint -> validation, so both see the averaged weights; the file holds the raw ones as `ema_*` entries,
+                         which resume_from puts back (a file without them: the average starts from the loaded weights, one record
+                         with mode 'ema').  After the last epoch the model keeps the averaged weights
 
     train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`; a validation
     pipeline that asks for test-time augmentation, MultiScaleFlipAug3D(flip=True), gets a data.AugDeviceLoader: build_val_loader).  Under
@@ -625,6 +840,12 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
         val_loader = build_val_loader(DT.ResidentScenes(vs, device, max_gb), vs.pipeline, cfg.data.get('samples_per_gpu', 1), seed, rank, world)
     if load_from is None:
         load_from = cfg.get('load_from')
+    # the weight average (custom_hooks' EMAHook, or the one of the TrainStep handed in); its own `resume_from` key is `fit`'s
+    hook = step.ema if step is not None else WeightEma.from_config(ema_hook_of(cfg.get('custom_hooks')))
+    if hook is not None and hook.resume_from is not None:
+        if resume_from is not None and str(resume_from) != str(hook.resume_from):
+            raise ValueError(f"EMAHook resume_from {hook.resume_from!r} differs from fit's resume_from {resume_from!r}")
+        resume_from = hook.resume_from
     load_report = None
     if load_from is not None and resume_from is None:
         from .checkpoint import load_checkpoint
@@ -634,15 +855,26 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     if world > 1:
         for t in list(model.parameters()) + list(model.buffers()):
             torch.distributed.broadcast(t.data, 0)            # every rank starts from rank 0's weights, as DDP's constructor does
-    tr = step if step is not None else TrainStep.from_config(model, cfg)
+    tr = step if step is not None else TrainStep.from_config(model, cfg, ema=hook)
     if world > 1 and step is not None:
         tr.invalidate_images()                                # the broadcast wrote the weights through .data behind an existing TrainStep
+    ema = tr.ema
+    if ema is not None and step is not None:
+        ema.reset()                                           # the weights are final only now (load_from, the broadcast)
     start_epoch, it = 0, 0
+    ema_note = None
     if resume_from is not None:
         from .checkpoint import load_checkpoint
-        ck = load_checkpoint(model, resume_from, map_location=device, strict=True)
+        ck = load_checkpoint(model, resume_from, map_location=device, strict=True, extra_keys=ema.names() if ema is not None else None)
         start_epoch, it = int(ck['meta']['epoch']), int(ck['meta']['iter'])
         tr.load_state_dict(dict(optimizer=ck['optimizer'], epoch=start_epoch))
+        if ema is not None:
+            if ck['extra_state']:
+                ema.load_state_dict(ck['extra_state'], swapped=True)      # the file's own entries are the averages, these the raw weights
+            else:
+                ema.reset()
+                ema_note = dict(mode='ema', resume_from=str(resume_from),
+                                note='the checkpoint holds no ema_* entries: the average starts from the loaded weights')
     log_path = None
     if rank == 0:
         os.makedirs(work_dir, exist_ok=True)
@@ -651,10 +883,14 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     if load_report is not None:
         log.write(dict(mode='load', load_from=str(load_from), unexpected=list(load_report['unexpected']), missing=list(load_report['missing']),
                        mismatched=[[k, list(a), list(b)] for k, a, b in load_report['mismatched']]))
+    if ema_note is not None:
+        log.write(ema_note)
     ck_cfg = cfg.get('checkpoint_config') or {}
     max_epochs = int(cfg.runner['max_epochs'])
     model.train()
     for epoch in range(start_epoch, max_epochs):
+        if ema is not None and ema.swapped:
+            ema.swap()                                        # back to the raw weights (mmcv EMAHook.before_train_epoch)
         if tr.lr is not None:
             tr.lr.set_epoch(epoch)
         train_loader.set_epoch(epoch)
@@ -662,8 +898,7 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
         batches = train_loader.batches(epoch)
         t_data = (time.perf_counter() - t_data0) / max(len(batches), 1)
         for k, batch in enumerate(batches):
-            if tr.lr is not None:
-                tr.lr.set_iter(it)
+            tr.set_iter(it)
             if on_batch is not None:
                 on_batch(epoch, it, batch)
             t0 = time.perf_counter()
@@ -674,6 +909,8 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                 log.flush('train', epoch + 1, k + 1, tr.optimizer.param_groups[0]['lr'])
         log.flush('train', epoch + 1, len(batches), tr.optimizer.param_groups[0]['lr'])
         tr.epoch_end()
+        if ema is not None:
+            ema.swap()                                        # the checkpoint and the validation see the averaged weights (after_train_epoch)
         if rank == 0 and ck_cfg.get('interval', 1) > 0 and (epoch + 1) % int(ck_cfg.get('interval', 1)) == 0:
             _save(model, tr, work_dir, epoch + 1, it, seed, ck_cfg)
         if val_loader is not None and ev_interval > 0 and (epoch + 1) % ev_interval == 0:

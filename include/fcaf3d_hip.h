@@ -42,7 +42,10 @@ extern "C" {
  * fc_adamw_groups_pack / fc_adamw_step_groups added: AdamW with per-parameter rate and decay multipliers), -> 17 (fc_bn_eval_bwd / fc_bn_eval_bwd_ws_bytes /
  * fc_bn_eval_bwd_route added: the backward through a BatchNorm that reads its running statistics), -> 18 (fc_x6_weight_images takes the
  * grid of its amax pass, amax_chunks / amax_blocks; fc_x6_amax_units / fc_x6_weight_images_passes added), -> 19 (fc_vote_boxes added: box
- * voting between the merge NMS and the per-scene merge of test-time augmentation).  A caller built against
+ * voting between the merge NMS and the per-scene merge of test-time augmentation).  fc_adamw_ema_step / fc_swap_f32
+ * (AdamW with the weight average of mmcv's EMAHook in the same launch, the exchange of two flat buffers) were added at 19 WITHOUT a
+ * bump: nothing existing changed, tests/test_vote_cpu.py pins 19, and a library that lacks a declared symbol is refused by
+ * _lib.lib() whatever its version.  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
 #define FC_ABI_VERSION 19
 #ifndef FC_AMAX_SLOT_BYTES
@@ -766,6 +769,23 @@ int fc_adamw_groups_pack(const int64_t* begin, const float* lr_mult, const float
 int fc_adamw_step_groups(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float bias_correction1, float bias_correction2, const float* norm_and_clip,
                          const void* table_dev, int R, hipStream_t stream);
+
+/* mmcv EMAHook(momentum, interval, warm_up) (custom_hooks; mmcv/runner/hooks/ema.py of mmcv 1.3.x, third party and in no file of
+ * the tree: No reference counterpart; the rule is restated at runner.WeightEma) riding in the optimizer's launch:
+ * fc_adamw_step_groups' pass over p, g, m, v, and for every element, with p_new the parameter just computed,
+ *     ema <- fl32( fl32(ema * ema_keep) + fl32(ema_mu * p_new) )          (three fp32 roundings, no fused multiply-add)
+ * in the same thread: 36 B per parameter, one launch.  `ema`: n floats laid out like p (padding stays zero).  The caller forms
+ * ema_keep = fl32(1 - mu) and calls this entry only on steps whose update is due.  table_dev == NULL with R == 0: no multipliers,
+ * p / m / v come out as fc_adamw_step's; otherwise table_dev is the packed table of fc_adamw_groups_pack on the device and they
+ * come out as fc_adamw_step_groups'.  FC_EINVAL: what fc_adamw_step_groups refuses (a table without 1 .. FC_ADAMW_MAX_RUNS runs, or
+ * runs without a table), a null `ema` with n > 0, ema_mu or ema_keep outside [0, 1] or not finite. */
+int fc_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float bias_correction1, float bias_correction2, const float* norm_and_clip,
+                      const void* table_dev, int R, float ema_mu, float ema_keep, hipStream_t stream);
+/* mmcv EMAHook's exchange of the parameters and their averages at the epoch edges (after_train_epoch / before_train_epoch):
+ * No reference counterpart in the tree.  a <-> b over n floats (n % 4 == 0) in 16-byte vectors, one launch, none for n == 0.
+ * FC_EINVAL: a == b, overlapping ranges, a null pointer with n > 0, n < 0, n % 4 != 0. */
+int fc_swap_f32(float* a, float* b, int64_t n, hipStream_t stream);
 
 /* SURVEY.md 8(f) rank 4 "bf16 fast mode" (No reference counterpart: the reference trains in fp32 throughout, configs/fcaf3d/fcaf3d.py:30-33
  * sets no fp16 hook).  A process-global, flagged NON-PARITY switch: while on, the split-bf16 convolution launches that read a
