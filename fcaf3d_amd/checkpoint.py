@@ -64,10 +64,11 @@ def load_checkpoint(model, filename, map_location=None, strict=False, logger=Non
     return checkpoint
 
 
-def save_checkpoint(model, filename, optimizer=None, meta=None, extra_state=None):
+def save_checkpoint(model, filename, optimizer=None, meta=None, extra_state=None, grad_accum=None):
     """mmcv.runner.save_checkpoint layout (weights moved to the CPU, DDP prefix stripped).  extra_state: {name: tensor} written
     into the file's state_dict behind the model's own entries (mmcv EMAHook registers its averages as module buffers, so an mmcv
-    file holds them there); a name the model already uses raises."""
+    file holds them there); a name the model already uses raises.  grad_accum: runner.TrainStep's open accumulation group
+    (dict(iters, grads)), written as a top-level key beside 'optimizer' (tensors moved to the CPU); None: no such key."""
     meta = dict(meta or {})
     meta.setdefault('time', time.asctime())
     meta.setdefault('fcaf3d_amd_version', __import__('fcaf3d_amd').__version__)
@@ -80,5 +81,7 @@ def save_checkpoint(model, filename, optimizer=None, meta=None, extra_state=None
     ckpt = {'meta': meta, 'state_dict': sd}
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
+    if grad_accum is not None:
+        ckpt['grad_accum'] = dict(iters=int(grad_accum['iters']), grads=[t.detach().cpu() for t in grad_accum['grads']])
     torch.save(ckpt, filename)
     return ckpt

@@ -53,6 +53,7 @@ class FlatAdamW:
             self.runs = group_runs(flat.offsets, self.multipliers)
             self.table = torch.from_numpy(pack_runs(*self.runs, flat.n)).to(flat.data.device)      # uploaded once
         self.ema = None                          # the weight average (enable_ema): flat.n floats laid out like flat.data
+        self.acc = None                          # an open accumulation group's gradient sum (accumulate): flat.n floats, allocated on first use
 
     def enable_ema(self):
         """-> the buffer of the parameters' moving average (WeightEma owns its schedule), a copy of flat.data: padding zero, and zero
@@ -66,10 +67,32 @@ class FlatAdamW:
             p.grad = None                        # the flat gradient buffer is overwritten, not accumulated into
         self.flat.complete = False
 
-    def step(self, max_norm=None, gathered=False, ema=None):
+    def accumulate(self, scale, first, gathered=False, ema=None):
+        """a micro-iteration that does not step (mmcv GradientCumulativeOptimizerHook): acc = g * scale (`first` of its group) or
+        acc = acc + g * scale, ONE fc_grad_accum over the flat buffers; the gradient buffer is left as it is.  scale: 1 / factor, rounded
+        to fp32 by the call.  ema: (mu, keep) of an average update that is due on this iteration (WeightEma.coeffs): the average moves
+        towards the unchanged parameters in the same launch"""
+        f = self.flat
+        if not f.data.is_cuda:
+            raise RuntimeError('FlatAdamW runs on the GPU only (HIP); CPU parameters take torch.optim.AdamW')
+        if not gathered and not getattr(f, 'complete', False):
+            f.gather()
+        if self.acc is None:
+            if not first:
+                raise RuntimeError('FlatAdamW.accumulate(first=False) without an open group')
+            self.acc = torch.zeros_like(f.grad)
+        if ema is not None and self.ema is None:
+            raise RuntimeError('FlatAdamW.accumulate(ema=...) without an average: call enable_ema() first')
+        mu, keep = (float(ema[0]), float(ema[1])) if ema is not None else (0.0, 0.0)
+        L.call('fc_grad_accum', L.ptr(self.acc), L.ptr(f.grad), f.n, float(scale), 1 if first else 0,
+               L.ptr(self.ema) if ema is not None else None, L.ptr(f.data) if ema is not None else None, mu, keep, L.stream())
+
+    def step(self, max_norm=None, gathered=False, ema=None, accum_scale=None):
         """-> the global gradient norm (0-d device tensor) when max_norm is given.  ema: (mu, keep) of a step whose average update
         is due (WeightEma.coeffs): the step is then ONE fc_adamw_ema_step, which updates the average of every vector it has just
-        stepped; None: exactly the call made without an average"""
+        stepped; None: exactly the call made without an average.  accum_scale: the stepping iteration of an open group (accumulate):
+        fc_grad_accum_norm writes acc + g * accum_scale over the gradient and takes its norm in the same pass, in place of fc_grad_norm;
+        None: exactly the calls made without accumulation"""
         f = self.flat
         if not f.data.is_cuda:
             raise RuntimeError('FlatAdamW runs on the GPU only (HIP); CPU parameters take torch.optim.AdamW')
@@ -79,7 +102,14 @@ class FlatAdamW:
         self.steps += 1
         b1, b2 = g['betas']
         clip = None
-        if max_norm is not None:
+        if accum_scale is not None:
+            if self.acc is None:
+                raise RuntimeError('FlatAdamW.step(accum_scale=...) without an open group: call accumulate() first')
+            ws = L.workspace(L.query('fc_grad_accum_norm_ws_bytes', f.n), f.data.device)
+            clip = self.norm_clip if max_norm is not None else None
+            L.call('fc_grad_accum_norm', L.ptr(f.grad), L.ptr(self.acc), f.n, float(accum_scale), float(max_norm) if clip is not None else 0.0,
+                   L.ptr(clip), L.ptr(ws), ws.numel(), L.stream())
+        elif max_norm is not None:
             ws = L.workspace(L.query('fc_grad_norm_ws_bytes', f.n), f.data.device)
             L.call('fc_grad_norm', L.ptr(f.grad), f.n, float(max_norm), L.ptr(self.norm_clip), L.ptr(ws), ws.numel(), L.stream())
             clip = self.norm_clip
@@ -532,14 +562,64 @@ def reserve_device_memory(gigabytes, device=None, streams=None, chunk_gb=8):
     return got
 
 
+_OPTIMIZER_HOOKS = (None, 'OptimizerHook', 'GradientCumulativeOptimizerHook')
+_OPTIMIZER_CONFIG_KEYS = ('type', 'grad_clip', 'cumulative_iters')
+
+
+def cumulative_iters_of(optimizer_config):
+    """-> k of `optimizer_config` (mmcv: OptimizerHook, the default type, or GradientCumulativeOptimizerHook(cumulative_iters=k)); 1
+    without accumulation.  Any other hook type raises KeyError naming it, and so does any key beside grad_clip and cumulative_iters;
+    a k that is not an int >= 1 raises ValueError"""
+    cfg = optimizer_config or {}
+    kind = cfg.get('type')
+    if kind not in _OPTIMIZER_HOOKS:
+        raise KeyError(f'optimizer hook type {kind!r} is not implemented ({", ".join(_OPTIMIZER_HOOKS[1:])})')
+    for key in cfg:
+        if key not in _OPTIMIZER_CONFIG_KEYS:
+            raise KeyError(f'optimizer_config key {key!r} is not implemented ({", ".join(_OPTIMIZER_CONFIG_KEYS[1:])})')
+    if 'cumulative_iters' not in cfg:
+        return 1
+    k = cfg['cumulative_iters']
+    if not (isinstance(k, int) and not isinstance(k, bool) and k >= 1):
+        raise ValueError(f'cumulative_iters {k!r}: an int >= 1')
+    if kind != 'GradientCumulativeOptimizerHook' and k != 1:
+        raise KeyError(f"cumulative_iters={k} needs optimizer_config type 'GradientCumulativeOptimizerHook', not {kind!r}")
+    return k
+
+
+def accum_factor(it, k, max_iters=None):
+    """mmcv GradientCumulativeOptimizerHook: what the gradients of 0-based global iteration `it` are divided by: k, or in the run's
+    last, shorter group (max_iters % k iterations) that group's length.  max_iters None: k throughout"""
+    if max_iters is None:
+        return k
+    r = max_iters % k
+    return k if it < max_iters - r else r
+
+
+def accum_steps(it, k, max_iters=None):
+    """whether the optimizer steps after 0-based global iteration `it`: every k-th, and the run's last"""
+    return (it + 1) % k == 0 or (max_iters is not None and it == max_iters - 1)
+
+
 class TrainStep:
     """One optimisation step of the reference's recipe on this process's GPU (one process per GPU; gradients are averaged
-    over the process group, if any, by fcaf3d_amd.dist.GradientAverager while backward is still running)."""
+    over the process group, if any, by fcaf3d_amd.dist.GradientAverager while backward is still running).
 
-    def __init__(self, model, optimizer_cfg, optimizer_config=None, lr_config=None, bucket_mb=64, flat=None, ema=None):
+    Gradient accumulation (optimizer_config type 'GradientCumulativeOptimizerHook', cumulative_iters=k > 1): a
+    call is then a MICRO-iteration.  Its gradients, divided by accum_factor(it), are added to the open group's sum, and the optimizer
+    steps on the iterations accum_steps(it) names — groups are counted on the global iteration `it` (set_iter) and may straddle an epoch.
+    On the flat path the sum is FlatAdamW.acc and the division happens after the backward pass (fc_grad_accum / fc_grad_accum_norm);
+    on the per-tensor path it is mmcv's `loss / factor` with the sum left in `p.grad`.  `acc_iters` is the open group's length so far."""
+
+    def __init__(self, model, optimizer_cfg, optimizer_config=None, lr_config=None, bucket_mb=64, flat=None, ema=None, max_iters=None):
         """ema: an EMAHook dict (cfg.custom_hooks' entry) or a WeightEma: the parameters' moving average is updated with every step
-        (`self.ema`; on the flat path inside the optimizer's launch).  The average starts as a copy of the weights the model holds NOW."""
+        (`self.ema`; on the flat path inside the optimizer's launch).  The average starts as a copy of the weights the model holds NOW.
+        max_iters: the run's total of iterations (fit passes max_epochs x iterations per epoch), for the factor of the last, shorter
+        accumulation group; None: every group counts cumulative_iters (`flush` steps an open one)"""
         self.model = model
+        self.cumulative_iters = cumulative_iters_of(optimizer_config)
+        self.max_iters = None if max_iters is None else int(max_iters)
+        self.acc_iters = 0                           # micro-iterations in the open accumulation group
         self.params = [p for p in model.parameters() if p.requires_grad]
         clip = (optimizer_config or {}).get('grad_clip')
         self.max_norm = clip['max_norm'] if clip else None
@@ -571,6 +651,7 @@ class TrainStep:
 
     @classmethod
     def from_config(cls, model, cfg, **kw):
+        """kw: bucket_mb, flat, ema, max_iters of the constructor"""
         if kw.get('ema') is None:
             kw['ema'] = ema_hook_of(cfg.get('custom_hooks'))
         return cls(model, cfg.optimizer, cfg.get('optimizer_config'), cfg.get('lr_config'), **kw)
@@ -600,7 +681,10 @@ class TrainStep:
             losses = self.model(return_loss=True, **batch)
             loss = parse_losses(losses)
             t2 = time.perf_counter()
-            loss.backward()
+            if self.cumulative_iters > 1 and not isinstance(self.optimizer, FlatAdamW):
+                (loss / self.factor()).backward()    # the per-tensor path follows mmcv literally; the flat path scales the gradient
+            else:
+                loss.backward()
             t3 = time.perf_counter()
         self.averager.finish()
         self.close(images)
@@ -614,7 +698,8 @@ class TrainStep:
         self._bound_run_ahead()
         if next_batch is not None and hasattr(self.model, 'prefetch'):
             self.model.prefetch(next_batch['points'], gt=True)
-        self.optimizer.zero_grad(set_to_none=True)
+        if self.acc_iters == 0 or isinstance(self.optimizer, FlatAdamW):      # (an open group's sum sits in p.grad on the per-tensor path)
+            self.optimizer.zero_grad(set_to_none=True)
         Fn._flat_pass_done()                         # a backward pass that raised never ran its final callback: start clean
         if self.flat is not None and hasattr(self.model, 'backbone') and self.model.training:
             prog = executor.program_for(self.model, True)
@@ -631,9 +716,13 @@ class TrainStep:
             yield
 
     def close(self, images):
-        """after the pass and the averager: clip + optimizer step, then the images of the stepped weights (weight-gradient stream)"""
+        """after the pass and the averager: clip + optimizer step, then the images of the stepped weights (weight-gradient stream);
+        under gradient accumulation, on the iterations that do not step: the accumulation alone"""
         ema = self.ema
-        if isinstance(self.optimizer, FlatAdamW):    # (after finish() under data parallelism the averaged gradients sit in the flat buffer)
+        if self.cumulative_iters > 1:
+            if not self._close_accumulating():
+                return                               # no step: the weights did not move, the images stay current
+        elif isinstance(self.optimizer, FlatAdamW):    # (after finish() under data parallelism the averaged gradients sit in the flat buffer)
             if ema is None:
                 self.last_grad_norm = self.optimizer.step(self.max_norm, gathered=bool(self.averager.buckets))
             else:                                    # a step whose average update is due takes it in the optimizer's launch
@@ -645,6 +734,64 @@ class TrainStep:
         if ema is not None:
             ema.update(self.it)                      # parameters outside a flat buffer: three torch ops each
         self.it += 1
+        self._after_step(images)
+
+    def factor(self):
+        """what the gradients of the iteration at hand are divided by (accum_factor)"""
+        return accum_factor(self.it, self.cumulative_iters, self.max_iters)
+
+    def _close_accumulating(self):
+        """`close` with cumulative_iters > 1, up to the optimizer step -> whether the optimizer stepped.  The average keeps mmcv's
+        cadence: its update is due by the iteration, stepped or not"""
+        ema, opt = self.ema, self.optimizer
+        f, stepping = self.factor(), accum_steps(self.it, self.cumulative_iters, self.max_iters)
+        on_flat = isinstance(opt, FlatAdamW)
+        coeffs = ema.coeffs(self.it) if ema is not None and on_flat else None
+        if on_flat:
+            gathered = bool(self.averager.buckets)
+            if not stepping:
+                opt.accumulate(1.0 / f, self.acc_iters == 0, gathered=gathered, ema=coeffs)
+            elif self.acc_iters == 0 and f == 1:     # a group of one (the run's last iteration alone): the plain step, no extra pass
+                self.last_grad_norm = opt.step(self.max_norm, gathered=gathered, ema=coeffs)
+            else:
+                if self.acc_iters == 0:              # a group that lost its earlier iterations (resumed without them): sum from zero
+                    if opt.acc is None:
+                        opt.acc = torch.zeros_like(opt.flat.grad)
+                    opt.acc.zero_()
+                self.last_grad_norm = opt.step(self.max_norm, gathered=gathered, ema=coeffs, accum_scale=1.0 / f)
+        elif stepping:
+            self._torch_step()
+        if not stepping:
+            self.last_grad_norm = None
+            self.acc_iters += 1
+            if ema is not None:
+                ema.update(self.it)
+            self.it += 1
+            return False
+        self.acc_iters = 0
+        return True
+
+    def _torch_step(self):
+        if self.max_norm is not None:
+            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.params, self.max_norm, norm_type=self.norm_type)
+        self.optimizer.step()
+
+    def flush(self):
+        """step an open accumulation group at once, with the sum it holds (a loop outside `fit` that ends inside a group); nothing
+        without one.  Not an iteration: `it` and the weight average stay as they are.  -> whether the optimizer stepped"""
+        if self.acc_iters == 0:
+            return False
+        opt = self.optimizer
+        if isinstance(opt, FlatAdamW):
+            opt.flat.grad.copy_(opt.acc)             # the sum as the gradient; the plain step's launches follow
+            self.last_grad_norm = opt.step(self.max_norm, gathered=True)
+        else:
+            self._torch_step()
+        self.acc_iters = 0
+        self.invalidate_images()                     # the next pass rebuilds the weight images before it reads them
+        return True
+
+    def _after_step(self, images):
         self.invalidate_images()                     # the step wrote through raw pointers (torch's fused ones too): no version counter moved
         if images is not None:
             images.rebuild_after_step(torch.cuda.current_stream(), Fn.wgrad_stream(self.flat.data.device))
@@ -670,13 +817,46 @@ class TrainStep:
             self.lr.epoch_end()
 
     def state_dict(self):
-        return dict(optimizer=self.optimizer.state_dict(), epoch=self.lr.epoch if self.lr else 0)
+        """while an accumulation group is open also `grad_accum` = dict(iters=its length so far, grads=[the sum per parameter, in
+        optimizer order]): mmcv loses the partial sum when it resumes, this keeps it"""
+        sd = dict(optimizer=self.optimizer.state_dict(), epoch=self.lr.epoch if self.lr else 0)
+        ga = self.grad_accum_state()
+        if ga is not None:
+            sd['grad_accum'] = ga
+        return sd
+
+    def grad_accum_state(self):
+        """-> dict(iters, grads) of the open accumulation group (copies), or None"""
+        if not self.acc_iters:
+            return None
+        if isinstance(self.optimizer, FlatAdamW):
+            grads = [v.clone() for v in self.optimizer._views(self.optimizer.acc)]
+        else:
+            grads = [p.grad.detach().clone() if p.grad is not None else torch.zeros_like(p) for p in self.params]
+        return dict(iters=self.acc_iters, grads=grads)
 
     def load_state_dict(self, sd):
         self.invalidate_images()
         self.optimizer.load_state_dict(sd['optimizer'])
         if self.lr is not None:
             self.lr.set_epoch(sd.get('epoch', 0))
+        ga = sd.get('grad_accum')
+        self.acc_iters = 0
+        if ga is not None and self.cumulative_iters > 1:
+            opt = self.optimizer
+            params = opt.flat.params if isinstance(opt, FlatAdamW) else self.params
+            if len(ga['grads']) != len(params):
+                raise ValueError(f"grad_accum holds {len(ga['grads'])} gradients for {len(params)} parameters")
+            with torch.no_grad():
+                if isinstance(opt, FlatAdamW):
+                    if opt.acc is None:
+                        opt.acc = torch.zeros_like(opt.flat.grad)
+                    for v, t in zip(opt._views(opt.acc), ga['grads']):
+                        v.copy_(t)
+                else:
+                    for p, t in zip(params, ga['grads']):
+                        p.grad = t.detach().to(p.device).clone()
+            self.acc_iters = int(ga['iters'])
 
 
 def evaluate(model, batches, gt_annos, metric=(0.25, 0.5), label2cat=None, in_flight=2, scene_ids=None, group=None):
@@ -750,24 +930,30 @@ class _Log:
     def __init__(self, path, interval):
         self.path, self.interval = path, max(int(interval), 1)
         self.records, self.acc, self.keys, self.n, self.t_step, self.t_data = [], None, None, 0, 0.0, 0.0
+        self.gn, self.gn_n = None, 0                     # the gradient norm has a count of its own: under accumulation only the stepping iterations bring one
 
     def add(self, loss, losses, grad_norm, t_step, t_data):
         items = [(k, v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.dim() == 0] + [('loss', loss.detach())]
-        if grad_norm is not None:
-            items.append(('grad_norm', grad_norm.detach() if torch.is_tensor(grad_norm) else torch.as_tensor(float(grad_norm))))
         keys, vals = [k for k, _ in items], [v.to(loss.device) for _, v in items]
         row = torch.stack([v.float().reshape(()) for v in vals])
         self.acc = row if self.acc is None else self.acc + row
+        if grad_norm is not None:
+            gn = (grad_norm.detach() if torch.is_tensor(grad_norm) else torch.as_tensor(float(grad_norm))).to(loss.device).float().reshape(1)
+            self.gn, self.gn_n = gn if self.gn is None else self.gn + gn, self.gn_n + 1
         self.keys, self.n, self.t_step, self.t_data = keys, self.n + 1, self.t_step + t_step, self.t_data + t_data
 
     def flush(self, mode, epoch, it, lr):
         if not self.n:
             return None
-        vals = (self.acc / self.n).tolist()              # the interval's ONE read-back
+        keys, mean = list(self.keys), self.acc / self.n
+        if self.gn_n:                                    # averaged over the iterations that stepped; no key if none did
+            keys, mean = keys + ['grad_norm'], torch.cat([mean, self.gn / self.gn_n])
+        vals = mean.tolist()                             # the interval's ONE read-back
         rec = dict(mode=mode, epoch=epoch, iter=it, lr=lr)
-        rec.update({k: float(v) for k, v in zip(self.keys, vals)})
+        rec.update({k: float(v) for k, v in zip(keys, vals)})
         rec.update(time=self.t_step / self.n, data_time=self.t_data / self.n)
         self.acc, self.n, self.t_step, self.t_data = None, 0, 0.0, 0.0
+        self.gn, self.gn_n = None, 0
         return self.write(rec)
 
     def write(self, rec):
@@ -785,8 +971,9 @@ def _save(model, tr, work_dir, epoch, it, seed, cfg_ck):
     from .checkpoint import save_checkpoint
     path = os.path.join(work_dir, f'epoch_{epoch}.pth')
     # with an EMAHook the file is written while swapped: the model's entries hold the averages, the `ema_*` entries the raw weights
+    # an accumulation group open at the epoch's end: its sum goes into the file as the top-level key `grad_accum` (other readers ignore it)
     save_checkpoint(model, path, optimizer=tr.optimizer, meta=dict(epoch=epoch, iter=it, seed=seed),
-                    extra_state=tr.ema.state_dict() if tr.ema is not None else None)
+                    extra_state=tr.ema.state_dict() if tr.ema is not None else None, grad_accum=tr.grad_accum_state())
     shutil.copyfile(path, os.path.join(work_dir, 'latest.pth'))
     keep, interval = cfg_ck.get('max_keep_ckpts', -1), max(int(cfg_ck.get('interval', 1)), 1)
     if keep and keep > 0:
@@ -820,6 +1007,12 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                          checkpoint -> validation, so both see the averaged weights; the file holds the raw ones as `ema_*` entries,
                          which resume_from puts back (a file without them: the average starts from the loaded weights, one record
                          with mode 'ema').  After the last epoch the model keeps the averaged weights
+
+      optimizer_config   dict(type='GradientCumulativeOptimizerHook', cumulative_iters=k, grad_clip=...) (mmcv's): the gradients of k
+                         iterations, each divided by k, make one optimizer step (TrainStep; the run's last max_iters % k iterations are
+                         divided by their number).  grad_norm enters a log line from the stepping iterations only.  A group open at an
+                         epoch's end goes into the checkpoint (`grad_accum`) and resume_from puts it back (a file without it, inside
+                         a group: the group starts empty, one record with mode 'accum')
 
     train_loader / val_loader: data.DeviceLoader (default: built from cfg.data.train / cfg.data.val, resident on `device`; a validation
     pipeline that asks for test-time augmentation, MultiScaleFlipAug3D(flip=True), gets a data.AugDeviceLoader: build_val_loader).  Under
@@ -855,19 +1048,29 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
     if world > 1:
         for t in list(model.parameters()) + list(model.buffers()):
             torch.distributed.broadcast(t.data, 0)            # every rank starts from rank 0's weights, as DDP's constructor does
-    tr = step if step is not None else TrainStep.from_config(model, cfg, ema=hook)
+    max_epochs = int(cfg.runner['max_epochs'])
+    max_iters = None                                          # the run's total of iterations: asked for under gradient accumulation only
+    if (step.cumulative_iters if step is not None else cumulative_iters_of(cfg.get('optimizer_config'))) > 1:
+        max_iters = max_epochs * len(train_loader)
+    tr = step if step is not None else TrainStep.from_config(model, cfg, ema=hook, max_iters=max_iters)
+    if step is not None and max_iters is not None:
+        tr.max_iters = max_iters
     if world > 1 and step is not None:
         tr.invalidate_images()                                # the broadcast wrote the weights through .data behind an existing TrainStep
     ema = tr.ema
     if ema is not None and step is not None:
         ema.reset()                                           # the weights are final only now (load_from, the broadcast)
     start_epoch, it = 0, 0
-    ema_note = None
+    ema_note = accum_note = None
     if resume_from is not None:
         from .checkpoint import load_checkpoint
         ck = load_checkpoint(model, resume_from, map_location=device, strict=True, extra_keys=ema.names() if ema is not None else None)
         start_epoch, it = int(ck['meta']['epoch']), int(ck['meta']['iter'])
-        tr.load_state_dict(dict(optimizer=ck['optimizer'], epoch=start_epoch))
+        tr.load_state_dict(dict(optimizer=ck['optimizer'], epoch=start_epoch, grad_accum=ck.get('grad_accum')))
+        if tr.cumulative_iters > 1 and ck.get('grad_accum') is None and it % tr.cumulative_iters:
+            accum_note = dict(mode='accum', resume_from=str(resume_from),
+                              note=f'the checkpoint holds no grad_accum entry at iteration {it}, inside a group of {tr.cumulative_iters}: '
+                                   'the group starts empty')
         if ema is not None:
             if ck['extra_state']:
                 ema.load_state_dict(ck['extra_state'], swapped=True)      # the file's own entries are the averages, these the raw weights
@@ -885,8 +1088,9 @@ def fit(model, cfg, work_dir, train_loader=None, val_loader=None, resume_from=No
                        mismatched=[[k, list(a), list(b)] for k, a, b in load_report['mismatched']]))
     if ema_note is not None:
         log.write(ema_note)
+    if accum_note is not None:
+        log.write(accum_note)
     ck_cfg = cfg.get('checkpoint_config') or {}
-    max_epochs = int(cfg.runner['max_epochs'])
     model.train()
     for epoch in range(start_epoch, max_epochs):
         if ema is not None and ema.swapped:

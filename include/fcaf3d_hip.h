@@ -45,7 +45,8 @@ extern "C" {
  * voting between the merge NMS and the per-scene merge of test-time augmentation).  fc_adamw_ema_step / fc_swap_f32
  * (AdamW with the weight average of mmcv's EMAHook in the same launch, the exchange of two flat buffers) were added at 19 WITHOUT a
  * bump: nothing existing changed, tests/test_vote_cpu.py pins 19, and a library that lacks a declared symbol is refused by
- * _lib.lib() whatever its version.  A caller built against
+ * _lib.lib() whatever its version.  fc_grad_accum / fc_grad_accum_norm / fc_grad_accum_norm_ws_bytes (gradient accumulation over
+ * the flat buffers) were added the same way, for the same reason.  A caller built against
  * another version must not go on: tests/test_cabi.py pins the number the Python host was written for. */
 #define FC_ABI_VERSION 19
 #ifndef FC_AMAX_SLOT_BYTES
@@ -786,6 +787,30 @@ int fc_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, 
  * No reference counterpart in the tree.  a <-> b over n floats (n % 4 == 0) in 16-byte vectors, one launch, none for n == 0.
  * FC_EINVAL: a == b, overlapping ranges, a null pointer with n > 0, n < 0, n % 4 != 0. */
 int fc_swap_f32(float* a, float* b, int64_t n, hipStream_t stream);
+
+/* mmcv GradientCumulativeOptimizerHook(cumulative_iters=k) (optimizer_config; mmcv/runner/hooks/optimizer.py of mmcv 1.3.x, third
+ * party and in no file of the tree: No reference counterpart; the rule is restated at runner.TrainStep) for a micro-iteration that
+ * does NOT step, over flat buffers of n floats (n % 4 == 0): with scale = fl32(1 / factor),
+ *     first != 0:  acc <- fl32(g * scale)                      (acc is not read: 8 B per parameter)
+ *     first == 0:  acc <- fl32( acc + fl32(g * scale) )        (two fp32 roundings, no fused multiply-add: 12 B per parameter)
+ * g is not written; padding that is zero in g stays zero in acc.  `ema` (nullable) with `p`: mmcv EMAHook's update falls due on
+ * this iteration although the parameters did not move, and rides in the launch: ema <- fl32( fl32(ema * ema_keep) +
+ * fl32(ema_mu * p) ) as in fc_adamw_ema_step, + 12 B per parameter.  One launch, none for n == 0.  FC_EINVAL: n < 0, n % 4 != 0,
+ * a scale that is not finite or not positive, ema_mu or ema_keep outside [0, 1] or not finite (pass 0 without `ema`), `ema` without
+ * `p`, a null acc or g with n > 0, acc overlapping g, ema overlapping acc, g or p. */
+int fc_grad_accum(float* acc, const float* g, int64_t n, float scale, int first, float* ema, const float* p, float ema_mu,
+                  float ema_keep, hipStream_t stream);
+/* The STEPPING iteration of a group of more than one micro-iteration (mmcv GradientCumulativeOptimizerHook with grad_clip,
+ * configs/fcaf3d/fcaf3d.py:31 for the clip): g_inout <- G = fl32( acc + fl32(g_inout * scale) ), the group's gradient, and in the
+ * same pass out2 = [the global 2-norm of G, min(1, max_norm / (norm + 1e-6))] — bit for bit what fc_grad_norm returns for the
+ * materialised G (its block assignment and order), so the pair of launches REPLACES fc_grad_norm (12 B per parameter instead of
+ * 4; G is not re-read) and fc_adamw_step / fc_adamw_step_groups / fc_adamw_ema_step follows unchanged.  acc is not written.
+ * out2 == NULL: the sum only, one launch, ws not used.  n == 0: nothing is launched and out2 is not written.  FC_EINVAL: n < 0,
+ * n % 4 != 0, a scale that is not finite or not positive, a null buffer with n > 0, acc overlapping g_inout; FC_EWS: ws null or
+ * smaller than fc_grad_accum_norm_ws_bytes(n) with out2 given. */
+int64_t fc_grad_accum_norm_ws_bytes(int64_t n);
+int fc_grad_accum_norm(float* g_inout, const float* acc, int64_t n, float scale, float max_norm, float* out2, void* ws,
+                       int64_t ws_bytes, hipStream_t stream);
 
 /* SURVEY.md 8(f) rank 4 "bf16 fast mode" (No reference counterpart: the reference trains in fp32 throughout, configs/fcaf3d/fcaf3d.py:30-33
  * sets no fp16 hook).  A process-global, flagged NON-PARITY switch: while on, the split-bf16 convolution launches that read a
