@@ -7,7 +7,9 @@ arithmetic, addressing, statistics epilogue and grid shape.  This module
     the smallest row count, then the first shape in list order, that reaches the class,
   * derives the GPU case list from the representatives (`row_counts`, `cases`): row counts at the tile and row-range edges, each
     confirmed by the route query to stay in the class, times crafted neighbour tables,
-  * makes the tables, the integer operands and the exact float64 references.
+  * makes the tables, the integer operands and the exact float64 references,
+  * makes, for the classes with a statistics epilogue, the inputs, the option combinations and the float64 reference of that
+    epilogue's backward form, with the one-token mutations of the reference the CPU test holds the cases against (last section).
 
 Operands are small integers stored as fp32 (x, gout in [-8, 8], w in [-4, 4], a third of them zero): every arithmetic mode of the
 library is exact on them (fp32: integers below 2^24; six-product / bf16-fast: the first bf16 piece holds the value; h3: the
@@ -74,7 +76,8 @@ WgradClass = namedtuple('WgradClass', 'family bm bn ko mode split wbuf table bkr
 # a call of the sweep's grid: square (n_in = n_out = n); kind: KINDS / WGRAD_KINDS; env: the process-global switches it needs
 Rep = namedtuple('Rep', 'n Cin Cout K kind flags env')
 # one GPU launch: rep's shape at other row counts, on a crafted table, with one operand variant ('int', 'zero': x all zero,
-# 'stats': the statistics entry point on 0 / 1 operands)
+# 'stats': the statistics entry point on 0 / 1 operands, 'bn<i>': the BACKWARD form of that epilogue on the same operands with the
+# option combination BN_COMBOS[i])
 Case = namedtuple('Case', 'n_in n_out table variant')
 
 _NAMES = {}
@@ -301,39 +304,77 @@ def cases(direction, cls, rep):
     """the GPU launches of a class: every row count of `row_counts` x EDGE_TABLES (BIG_TABLES from BIG_ROWS rows), at the
     representative's row count also EXTRA_TABLES, an all-zero x, and `perm` tables over n_in = 2 n + 3 and n // 8 + 1 input rows (the
     strided and the generative shape); classes with a statistics epilogue run every edge table through the statistics entry point
-    as well.  Table-free classes (K = 1, the row itself is the index) have the row counts and the all-zero x only.  Each case is
+    as well, and a third time through its BACKWARD form ('bn<i>', the option combinations BN_COMBOS in turn) — that form also on
+    the two `perm` shapes, on `fan_in` and `first_only`, and, where a sum kernel writes the table, at RB_ROWS; every such class sees
+    every combination, and `empty` only combinations that pass `add` (both asserted here).  Table-free classes (K = 1, the row itself is the index) have the row counts and the all-zero x only.  Each case is
     confirmed by the route query: for the linear pair-list launch the class depends on the table's own live-tile count, and a
     table without any pair (live_tiles = 0) IS the 3-D launch, so those cases belong to the sibling class and are left to it.
     Call under rep.env."""
     tile, S = tile_of(direction, rep)
     out = []
+    epi = has_stats(direction, cls)
+    turn = [0]                                   # the next option combination of the backward epilogue
 
     def add(n_in, n_out, table, variant):
         live = 0
         if rep.kind == 'pairs_linear':
             live = live_tiles_of(make_table(table, rep.K, n_in, n_out, tile, S))
-        stats = variant == 'stats'
+        stats = variant == 'stats' or is_bn(variant)
         if fast_class(direction, n_in, n_out, rep.K, rep.Cin, rep.Cout, rep.flags, rep.kind, live, stats) == cls:
             out.append(Case(n_in, n_out, table, variant))
+            return True
+        return False
+
+    def add_bn(n_in, n_out, table):
+        """the backward-epilogue twin of a statistics case, the option combinations in turn; without any pair the result is zero and
+        every sum with it unless `add` is passed, so `empty` takes the next combination that passes one"""
+        i = turn[0]
+        while table == 'empty' and not BN_COMBOS[i % len(BN_COMBOS)].add:
+            i += 1
+        if add(n_in, n_out, table, bn_variant(i % len(BN_COMBOS))):
+            turn[0] = i + 1
     for n in row_counts(direction, cls, rep):
         if rep.kind == 'none':
             add(n, n, 'identity', 'int')
-            if has_stats(direction, cls):
+            if epi:
                 add(n, n, 'identity', 'stats')
+                add_bn(n, n, 'identity')
             continue
         for t in (EDGE_TABLES if n < BIG_ROWS else BIG_TABLES):
             add(n, n, t, 'int')
-            if has_stats(direction, cls):
+            if epi:
                 add(n, n, t, 'stats')
+                add_bn(n, n, t)
     n = rep.n
     if rep.kind == 'none':
         add(n, n, 'identity', 'zero')
-        return out
-    for t in EXTRA_TABLES:
-        add(n, n, t, 'int')
-    add(n, n, 'full', 'zero')
-    for n_in in (2 * n + 3, n // 8 + 1):
-        add(n_in, n, 'perm', 'int')
+    else:
+        for t in EXTRA_TABLES:
+            add(n, n, t, 'int')
+        add(n, n, 'full', 'zero')
+        for n_in in (2 * n + 3, n // 8 + 1):
+            add(n_in, n, 'perm', 'int')
+    if epi:
+        base = 'identity' if rep.kind == 'none' else 'full'
+        if rep.kind != 'none':
+            # the strided and the generative shape of a real backward-data pass (bn_x has n_out rows, x has not), and the two tables
+            # that leave most rows (fan_in: some rows) without any neighbour
+            for n_in in (2 * n + 3, n // 8 + 1):
+                add_bn(n_in, n, 'perm')
+            for t in ('fan_in', 'first_only'):
+                add_bn(n, n, t)
+        if cls.epi == E['FC_EPI_SUM']:
+            # the sum kernels' row blocks follow the row count (conv.hip fc_stat_rb: 16 rows up to 1 024, 64 up to 4 096, then 32): both
+            # steps, and the row counts whose last block ends k_sum_pairs_stats' two-rows-per-pass loop on a partial pass
+            for m, t in RB_ROWS:
+                add_bn(m, m, base if rep.kind == 'none' else t)
+        seen = {c.variant for c in out if is_bn(c.variant)}
+        for i in range(len(BN_COMBOS)):          # a short case list (table-free classes) did not get through the cycle
+            if bn_variant(i) not in seen:
+                add(n, n, base, bn_variant(i))
+        seen = {c.variant for c in out if is_bn(c.variant)}
+        assert seen == {bn_variant(i) for i in range(len(BN_COMBOS))}, (cls, rep, sorted(seen))
+        assert all(bn_combo(c.variant).add for c in out if is_bn(c.variant) and c.table == 'empty'), (cls, rep)
     return out
 
 
@@ -409,10 +450,14 @@ def int_operand(shape, amp, seed, zero_frac=1.0 / 3.0, lo=None):
     return v
 
 
-@functools.lru_cache(maxsize=64)
 def operands(n_in, n_out, K, Cin, Cout, variant):
     """(x (n_in, Cin), w (K, Cin, Cout), gout (n_out, Cout)) as read-only float32 arrays.  'int': x, gout in [-8, 8], w in [-4, 4];
-    'zero': x all zero; 'stats': x in {0, 1} (two thirds zero), w in {-1, 0, 1}"""
+    'zero': x all zero; 'stats' (and the backward epilogue's 'bn<i>'): x in {0, 1} (two thirds zero), w in {-1, 0, 1}"""
+    return _operands(n_in, n_out, K, Cin, Cout, operand_variant(variant))
+
+
+@functools.lru_cache(maxsize=64)
+def _operands(n_in, n_out, K, Cin, Cout, variant):
     key = (n_in, n_out, K, Cin, Cout)
     if variant == 'stats':
         x = int_operand((n_in, Cin), 1, _seed('x', key), 2.0 / 3.0, lo=0)
@@ -487,3 +532,235 @@ def ref_stem_col(x, nbr):
         o = np.nonzero(nbr[k] >= 0)[0]
         col[o, 3 * k:3 * k + 3] = np.asarray(x)[nbr[k, o]]
     return torch.from_numpy(col)
+
+
+# ---- the backward form of the statistics epilogue -----------------------------------------------------------------------------------------
+# fc_conv_fwd_bn_bwd_stats / fc_conv_fwd_pairs_tiles_bn_bwd_stats: the launch's result g is the gradient arriving at a BatchNorm (+ ReLU /
+# ELU) layer with input bn_x; its epilogue leaves, per row block, the column sums of g' = (g + add) act'(.) and of g' xhat.  The inputs
+# are designed as tests/norm_cases.py designs its backward inputs — bn_x integers in [-8, 8], integer mean, var in {1, 0.25} with
+# eps = 0 (1 / sqrtf(var) is exactly 1 or 2), gamma in {1, 2, 0.5}, integer beta, add integers in [-8, 8] — so xhat = (bn_x - mean) is
+# is an integer, pre = fmaf(xhat, gamma, beta) a multiple of 1/2, and both are exact in fp32.  act' is
+#   * 1 without an activation (a bn_y passed all the same — NaN throughout — must not be read into the sums),
+#   * ReLU: pre > 0, or bn_y > 0 where the layer's output is given: bn_y = relu(pre + res) with an integer residual, so that its sign
+#     disagrees with pre's on a visible share of the elements, exact zeros (res = -pre) among them; pre == 0 is planted in every
+#     64-column block (it tells ReLU's act' = 0 from ELU's expf(0) = 1 and from `pre >= 0`),
+#   * ELU from bn_y: bn_y + 1 where bn_y <= 0; the outputs are positive integers, 0, -0.5 and -0.75, so act' is 1, 0.5 or 0.25,
+#   * ELU recomputed from bn_x — the one place a transcendental enters: expf(pre) where pre <= 0.  Kept exact by construction: every
+#     element whose pre would be negative gets bn_x = mean - 2 (130 + k), k in 0..6, so that pre = -2 (130 + k) is gamma + beta <= -128
+#     (is gamma >= 1/2, beta <= 2) and pre takes only values > 0, == 0 or <= -128.  exp(-128) = 2^-184.7 lies below half the
+#     smallest fp32 denormal, 2^-150: ANY expf that is within the whole denormal range of the true value returns +0 there, and
+#     expf(0) = 1.  So act' is 1 or 0 exactly and no tolerance is needed.  Where `add` is passed, half of those elements also carry
+#     add = -g (the reference result): v = g + add = 0 exactly there, whatever act' is.
+# Every term is then a multiple of 1/4.  The cap, a condition on the REFERENCE as in the forward form: 4 sum_rows |g'| and
+# 4 sum_rows |g' xhat| stay below 2^24 per column — then every partial sum in any order is a multiple of 1/4 below 2^22, exact in
+# fp32, and the table's column totals equal the float64 reference bit for bit.
+NONE, RELU, ELU = 0, 1, 2
+# act; `add` passed; y: None (act' recomputed from bn_x), 'y' (the layer's output), 'nan' (an output that must be ignored); gamma / beta given
+BnCombo = namedtuple('BnCombo', 'act add y affine')
+BN_COMBOS = (BnCombo(NONE, False, None, False), BnCombo(NONE, True, 'nan', True), BnCombo(RELU, False, None, True),
+             BnCombo(RELU, True, 'y', True), BnCombo(RELU, False, 'y', True), BnCombo(ELU, False, None, True),
+             BnCombo(ELU, True, None, True), BnCombo(ELU, True, 'y', True), BnCombo(RELU, True, None, True))
+# fc_stat_rb's steps; 1 047 = 16 x 64 + 23 and 4 095 = 63 x 64 + 63 end on a partial pass (on `full`: its rows all have a result)
+RB_ROWS = ((1024, 'full'), (1025, 'offset_holes'), (1047, 'full'), (4095, 'full'), (4096, 'offset_holes'), (4097, 'full'))
+BnCase = namedtuple('BnCase', 'combo g x mean var gamma beta add y res')
+
+
+def is_bn(variant):
+    return variant.startswith('bn')
+
+
+def bn_variant(i):
+    return f'bn{i}'
+
+
+def bn_combo(variant):
+    return BN_COMBOS[int(variant[2:])] if is_bn(variant) else None
+
+
+def operand_variant(variant):
+    """the convolution operands of a case: the backward epilogue runs on the statistics variant's (the `int` operands push
+    sum |g' xhat| past 2^24 at 4 097 rows x 256 channels)"""
+    return 'stats' if is_bn(variant) else variant
+
+
+def stat_rb(n):
+    """conv.hip fc_stat_rb: rows per block of k_sum_parts_stats / k_sum_pairs_stats"""
+    return 16 if n <= 1024 else 64 if n <= 4096 else 32
+
+
+def sorted_order(n_out):
+    """out_index of the `sorted` launches: a seeded permutation of the rows"""
+    return np.random.default_rng(n_out).permutation(n_out).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=64)
+def stats_result(n_in, n_out, K, Cin, Cout, table, tile, S):
+    """g: the exact result of the launch on the statistics variant's operands, float64 (n_out, Cout), read-only"""
+    x, w, _ = operands(n_in, n_out, K, Cin, Cout, 'stats')
+    nbr = None if table == 'identity' else make_table(table, K, n_in, n_out, tile, S)
+    g = ref_fwd(x, w, nbr).double().numpy()
+    g.setflags(write=False)
+    return g
+
+
+@functools.lru_cache(maxsize=16)
+def _bn_base(n_out, C):
+    """what the option combinations share at one shape: (bn_x, add, res, mean, var, gamma, beta) float64"""
+    from tests import norm_cases as NC
+    key = (n_out, C)
+    gamma, beta = NC.affine(C)
+    mean, var = (a[0] for a in NC.given_stats(1, C))
+    is_ = 1.0 / np.sqrt(var)
+    rng = np.random.default_rng(_seed('bn', key))
+    x = int_operand((n_out, C), 8, _seed('bn_x', key)).astype(np.float64)
+    # pre == 0: bn_x = mean - beta / (is gamma) in the columns where that is an integer (beta = 0: every fifth column) — a tenth of
+    # their elements, and column c's row c mod n_out
+    x0 = mean - beta / (is_ * gamma)
+    ok = (x0 == np.rint(x0)) & (np.abs(x0) <= 8)
+    assert C % 64 == 0 and ok.reshape(-1, 64).any(1).all()
+    plant = rng.random((n_out, C)) < 0.1
+    plant[np.arange(C) % n_out, np.arange(C)] = True
+    x = np.where(plant & ok, x0, x)
+    add = int_operand((n_out, C), 8, _seed('bn_add', key)).astype(np.float64)
+    res = int_operand((n_out, C), 8, _seed('bn_res', key)).astype(np.float64)
+    pre = (x - mean) * is_ * gamma + beta
+    res = np.where((rng.random((n_out, C)) < 0.05) & (pre == np.rint(pre)), 0.0 - pre, res)          # exact zeros of the layer's output
+    for a in (x, add, res, mean, var, gamma, beta):
+        a.setflags(write=False)
+    return x, add, res, mean, var, gamma, beta
+
+
+@functools.lru_cache(maxsize=8)
+def bn_case(n_in, n_out, K, Cin, Cout, table, tile, S, variant):
+    """the epilogue inputs of one backward-epilogue case (float64, read-only; add / y None where the combination passes none; gamma /
+    beta hold what the kernel uses for NULL where the combination passes none) with the reference result g"""
+    combo = bn_combo(variant)
+    g = stats_result(n_in, n_out, K, Cin, Cout, table, tile, S)
+    x, add, res, mean, var, gamma, beta = _bn_base(n_out, Cout)
+    if not combo.affine:
+        gamma, beta = np.ones(Cout), np.zeros(Cout)
+    add = add if combo.add else None
+    is_ = 1.0 / np.sqrt(var)
+    r, c = np.ogrid[:n_out, :Cout]
+    if combo.act == ELU and combo.y is None:
+        neg = (x - mean) * is_ * gamma + beta < 0
+        x = np.where(neg, mean - 2.0 * (130 + (r + c) % 7), x)
+        if combo.add:
+            add = np.where(neg & ((r + c) % 2 == 0), 0.0 - g, add)
+    pre = (x - mean) * is_ * gamma + beta
+    y = None
+    if combo.y == 'nan':
+        y = np.full((n_out, Cout), np.nan)
+    elif combo.y == 'y':
+        t = pre + res
+        f = np.floor(t)
+        y = np.maximum(t, 0.0) if combo.act == RELU else np.where(f > 0, f, np.where(f == 0, 0.0, np.where(f % 2 == 0, -0.5, -0.75)))
+    for a in (x, add, y):
+        if a is not None:
+            a.setflags(write=False)
+    return BnCase(combo, g, x, mean, var, gamma, beta, add, y, res)
+
+
+# one-token mutations of the reference (tests/test_conv_routes_cpu.py: each changes a column total wherever its branch is live)
+MUTATIONS = ('act_ignored', 'add_dropped', 'pre_for_y', 'y_for_act0', 'pre_ge0', 'skip_no_neighbour', 'launch_row', 'last_row_dropped',
+             'o16_dropped')
+
+
+def bn_terms(bc, mut=None, order=None):
+    """(g', g' xhat) in float64, (n_out, C) each: g' = (g + add) act'(.), xhat = (bn_x - mean) / sqrt(var)"""
+    act = bc.combo.act
+    xh = (bc.x - bc.mean) / np.sqrt(bc.var)
+    pre = xh * bc.gamma + bc.beta
+    g = bc.g[order] if mut == 'launch_row' else bc.g          # launch row r holds the result of row out_index[r], reads bn_x / add / bn_y at r
+    add = 0.0 if (bc.add is None or mut == 'add_dropped') else bc.add
+    from_y = bc.y is not None and act != NONE
+    if mut == 'pre_for_y':
+        from_y = False
+    if mut == 'y_for_act0' and bc.y is not None and act == NONE:
+        from_y, act = True, RELU
+    if mut == 'act_ignored':
+        act = NONE
+    pos = pre >= 0 if mut == 'pre_ge0' else pre > 0
+    if act == NONE:
+        d = np.ones_like(pre)
+    elif from_y:
+        d = (bc.y > 0).astype(np.float64) if act == RELU else np.where(bc.y > 0, 1.0, bc.y + 1.0)
+    elif act == RELU:
+        d = pos.astype(np.float64)
+    else:
+        assert mut == 'pre_for_y' or ((pre > 0) | (pre == 0) | (pre <= -128)).all(), 'ELU recomputed: a pre-activation whose expf is not exact'
+        d = np.where(pos, 1.0, np.exp(np.minimum(pre, 0.0)).astype(np.float32).astype(np.float64))          # fp32: 1 at 0, +0 from -128 down
+    gp = (g + add) * d
+    return gp, gp * xh
+
+
+def o16_rows(n):
+    """rows o + 16 of the LAST pass of k_sum_pairs_stats over a row block whose rows leave that pass partial: lanes with a row o but
+    no row o + 16 beside lanes with both (the `two` guard) — the short last block of fc_stat_rb(n) >= 32 rows only"""
+    rb = stat_rb(n)
+    r0 = (n - 1) // rb * rb
+    last = (n - r0 - 1) // 32 * 32
+    m = n - r0 - last                              # rows of the last pass
+    return np.arange(r0 + last + 16, n) if 16 < m < 32 else np.arange(0)
+
+
+def bn_sums(bc, mut=None, nbr=None, order=None):
+    """(2, C) float64: the column totals of g' and of g' xhat — the reference of both planes of the table (mut: one of MUTATIONS)"""
+    gp, gx = bn_terms(bc, mut, order)
+    w = np.ones(len(gp))
+    if mut == 'skip_no_neighbour' and nbr is not None:
+        w = (nbr >= 0).any(0).astype(np.float64)
+    elif mut == 'last_row_dropped':
+        w[-1] = 0.0
+    elif mut == 'o16_dropped':
+        w[o16_rows(len(gp))] = 0.0
+    return np.stack([(w[:, None] * gp).sum(0), (w[:, None] * gx).sum(0)])
+
+
+def bn_cap(bc):
+    """the exactness cap as a fraction of 2^24 (the factor 4: the quarter-valued ELU derivatives)"""
+    gp, gx = bn_terms(bc)
+    return 4.0 * max(float(np.abs(gp).sum(0).max()), float(np.abs(gx).sum(0).max())) / EXACT
+
+
+def mutation_live(mut, bc, nbr, kinds, order):
+    """is the branch a mutation changes reached by this case — from the option combination and the table's structure alone.  kinds:
+    the launch kinds the class runs the case through; nbr None: table-free"""
+    combo, n = bc.combo, len(bc.g)
+    covered = np.ones(n, bool) if nbr is None else (nbr >= 0).any(0)          # rows with a neighbour: g is not zero there
+    some = combo.add or bool(covered.any())
+    if mut == 'act_ignored':
+        return combo.act != NONE and some
+    if mut == 'add_dropped':
+        return combo.add
+    if mut == 'pre_for_y':
+        return combo.y == 'y' and some
+    if mut == 'y_for_act0':
+        return combo.y == 'nan' and some
+    if mut == 'pre_ge0':                           # ReLU recomputed (ELU: expf(0) = 1 either way); a pre == 0 sits in one row in ten
+        return combo.act == RELU and combo.y is None and (combo.add or int(covered.sum()) >= min(n, 16))
+    if mut == 'skip_no_neighbour':
+        return combo.add and not covered.all()
+    if mut == 'launch_row':                        # a row with a result that the order moves
+        return 'sorted' in kinds and bool((covered[order] & (order != np.arange(n))).any())
+    if mut == 'last_row_dropped':
+        return combo.add or bool(covered[-1])
+    if mut == 'o16_dropped':
+        rows = o16_rows(n)
+        return any(k.startswith('pairs') for k in kinds) and len(rows) > 0 and (combo.add or bool(covered[rows].any()))
+    raise KeyError(mut)
+
+
+def bn_facts(bc, nbr):
+    """the branch facts a combination claims, recomputed from the inputs"""
+    xh = (bc.x - bc.mean) / np.sqrt(bc.var)
+    pre = xh * bc.gamma + bc.beta
+    covered = np.ones(len(bc.g), bool) if nbr is None else (nbr >= 0).any(0)
+    f = {'pre_zero_blocks': bool((pre == 0).any(0).reshape(-1, 64).any(1).all()), 'big_negative': int((pre <= -128).sum()),
+         'small_negative': int(((pre < 0) & (pre > -128)).sum()), 'lonely_rows': int((~covered).sum()),
+         'add_cancels': 0 if bc.add is None else int(((bc.g + bc.add == 0) & (pre <= -128) & (bc.g != 0)).sum())}
+    if bc.combo.y == 'y':
+        f['y_disagrees'] = float((((bc.y > 0) != (pre > 0))).mean())
+        f['y_zero'] = int((bc.y == 0).sum())
+        f['y_values'] = set(np.unique(bc.y[bc.y <= 0]).tolist())
+    return f

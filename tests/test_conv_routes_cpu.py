@@ -156,3 +156,129 @@ def test_references_agree_with_a_dense_restatement():
     assert col.shape == (n_out, 84) and np.array_equal(col[:, :3 * K], np.concatenate([G[k] @ x for k in range(K)], axis=1).astype(np.float32))
     assert not col[:, 3 * K:].any()
     assert torch.equal(CC.ref_fwd(x[:n_out], w[:1], None), torch.from_numpy((x[:n_out].astype(np.float64) @ w[0]).astype(np.float32)))
+
+
+# ---- the backward form of the statistics epilogue (conv_cases: "the backward form ...") ---------------------------------------------------
+def _bn_launch_kinds(cls, rep, case):
+    """the launch kinds tests/test_gpu_conv_exact.py runs a case through (a dense class: also `sorted` where the route query agrees)"""
+    kinds = [rep.kind]
+    if rep.kind == 'dense' and CC.fast_class(CC.FWD, case.n_in, case.n_out, rep.K, rep.Cin, rep.Cout, rep.flags, 'sorted', 0, True) == cls:
+        kinds.append('sorted')
+    return tuple(kinds)
+
+
+_BN_CHECKED = {}
+
+
+def _check_bn_case(rep, case, tile, S, kinds):
+    """cap, branch facts and mutations of one case -> the mutations that were live (cached: the classes share most of their cases)"""
+    key = (case, rep.K, rep.Cin, rep.Cout, tile, S, kinds)
+    if key in _BN_CHECKED:
+        return _BN_CHECKED[key]
+    bc = CC.bn_case(case.n_in, case.n_out, rep.K, rep.Cin, rep.Cout, case.table, tile, S, case.variant)
+    combo, n = bc.combo, case.n_out
+    nbr = None if case.table == 'identity' else CC.make_table(case.table, rep.K, case.n_in, n, tile, S)
+    what = (rep, case)
+    # the inputs keep to their design
+    lim8 = None if (combo.act == CC.ELU and combo.y is None) else 8          # (ELU recomputed plants bn_x <= -260 and add = -g)
+    for a, lim in ((bc.x, lim8), (bc.add, lim8), (bc.mean, 2), (bc.beta, 2)):
+        if a is not None:
+            assert np.array_equal(a, np.rint(a)) and (lim is None or np.abs(a).max() <= lim), what
+    assert set(np.unique(bc.var)) <= {1.0, 0.25} and set(np.unique(bc.gamma)) <= {1.0, 2.0, 0.5}
+    assert combo.affine or (np.all(bc.gamma == 1) and not bc.beta.any())
+    assert (bc.add is not None) == combo.add and (bc.y is not None) == (combo.y is not None)
+    # the cap: every partial sum is a multiple of 1/4 below 2^22
+    gp, gx = CC.bn_terms(bc)
+    assert CC.bn_cap(bc) < 1.0, (what, CC.bn_cap(bc))
+    assert np.array_equal(gp * 4, np.rint(gp * 4)) and np.array_equal(gx * 4, np.rint(gx * 4)), what
+    # the branch facts
+    f = CC.bn_facts(bc, nbr)
+    if combo.affine:
+        assert f['pre_zero_blocks'], what
+    if combo.y == 'nan':
+        assert np.isnan(bc.y).all() and combo.act == CC.NONE
+    if combo.y == 'y':
+        assert f['y_disagrees'] > 0.1 or n * rep.Cout < 256, (what, f)          # (a visible share: a one-row case has 64 elements)
+        assert f['y_disagrees'] > 0 and f['y_zero'] > 0, (what, f)
+        if combo.act == CC.ELU:
+            assert f['y_values'] <= {0.0, -0.5, -0.75} and (f['y_values'] >= {-0.5, -0.75} or n < 4), (what, f)
+            assert set(np.unique(np.where(bc.y > 0, 1.0, bc.y + 1.0))) <= {1.0, 0.5, 0.25}
+    if combo.act == CC.ELU and combo.y is None:
+        assert f['big_negative'] > 0 and f['small_negative'] == 0, (what, f)
+        if combo.add and (nbr is None or (nbr >= 0).any()):
+            assert f['add_cancels'] > 0, (what, f)
+    elif combo.y is None:
+        assert f['big_negative'] == 0
+    if combo.add and n > 1 and (case.table in ('empty', 'last_only', 'first_only') or (case.table == 'tile_holes' and n > tile)):
+        assert f['lonely_rows'] > 0, (what, f)          # the sparse tables: a result row without any neighbour still adds `add` act'
+    # the mutations
+    order = CC.sorted_order(n)
+    ref = CC.bn_sums(bc)
+    live = []
+    for m in CC.MUTATIONS:
+        if CC.mutation_live(m, bc, nbr, kinds, order):
+            got = CC.bn_sums(bc, m, nbr, order)
+            assert not np.array_equal(got, ref), (what, m, 'a live mutation leaves every column total as it was')
+            live.append(m)
+    _BN_CHECKED[key] = tuple(live)
+    return _BN_CHECKED[key]
+
+
+def test_backward_epilogue_cases_reject_what_they_are_there_to_reject(swept):
+    """every class with a statistics epilogue, every case of its backward-epilogue list: the exactness cap holds (4 x the column sums
+    of |g'| and |g' xhat| below 2^24), the branch facts each option combination claims are there, and every one-token mutation of the
+    REFERENCE (conv_cases.MUTATIONS) changes at least one column total in every case where its branch is live.  No kernel is built or
+    run; per class, every mutation that one of its launch kinds can show is live in at least one case."""
+    by_class = _cases_by_class(swept)
+    n_cases = 0
+    try:
+        for (d, cls), cs in by_class.items():
+            if not CC.has_stats(d, cls):
+                assert not any(CC.is_bn(c.variant) for c in cs)
+                continue
+            rep = swept[d][cls]
+            CC.set_env(rep.env)
+            tile, S = CC.tile_of(d, rep)
+            bn = [c for c in cs if CC.is_bn(c.variant)]
+            st = [c for c in cs if c.variant == 'stats']
+            # coverage: every statistics case has its backward twin; the perm shapes, fan_in and first_only; every combination
+            assert {(c.n_in, c.n_out, c.table) for c in st} <= {(c.n_in, c.n_out, c.table) for c in bn}, CC.class_id(d, cls)
+            assert {c.variant for c in bn} == {CC.bn_variant(i) for i in range(len(CC.BN_COMBOS))}, CC.class_id(d, cls)
+            assert all(CC.bn_combo(c.variant).add for c in bn if c.table == 'empty')
+            if rep.kind not in ('none', 'pairs_linear'):
+                assert {(2 * rep.n + 3, 'perm'), (rep.n // 8 + 1, 'perm'), (rep.n, 'fan_in'), (rep.n, 'first_only')} <= {(c.n_in, c.table) for c in bn}
+            live = set()
+            for c in bn:
+                live.update(_check_bn_case(rep, c, tile, S, _bn_launch_kinds(cls, rep, c)))
+                n_cases += 1
+            want = set(CC.MUTATIONS) - {'launch_row', 'o16_dropped'}
+            if rep.kind == 'none':
+                want -= {'skip_no_neighbour'}
+            if rep.kind == 'dense':
+                want.add('launch_row')
+            if rep.kind.startswith('pairs') and any(c.n_out > 1024 for c in bn):
+                want.add('o16_dropped')
+            assert want <= live, (CC.class_id(d, cls), sorted(want - live))
+    finally:
+        CC.set_env(CC.ENV_DEFAULT)
+    print(f'{n_cases} backward-epilogue launches, {len(_BN_CHECKED)} distinct')
+
+
+def test_backward_epilogue_cap_at_the_largest_shape():
+    """the cap's headroom at the largest call of the sweep's grid: a `full` table at 4 097 rows, K = 27, 256 -> 256 channels"""
+    worst = 0.0
+    for variant in (CC.bn_variant(i) for i in (3, 6, 7)):
+        bc = CC.bn_case(4097, 4097, 27, 256, 256, 'full', 128, 1, variant)
+        worst = max(worst, CC.bn_cap(bc))
+    print(f'4 sum |g\' xhat| / 2^24 = {worst:.3f}, max |g| = {np.abs(bc.g).max():.0f}')
+    assert worst < 1.0
+
+
+def test_backward_epilogue_row_facts():
+    """conv_cases restates fc_stat_rb and the two-rows-per-pass loop of k_sum_pairs_stats: the row counts added for them do what they
+    are there for"""
+    assert [CC.stat_rb(n) for n in (1, 1024, 1025, 4096, 4097)] == [16, 16, 64, 64, 32]
+    assert CC.o16_rows(1047).tolist() == list(range(1040, 1047)) and CC.o16_rows(4095).tolist() == list(range(4080, 4095))
+    assert all(len(CC.o16_rows(n)) == 0 for n in (1, 16, 17, 1024, 1025, 4096, 4097, CC.N_MAX))
+    order = CC.sorted_order(257)
+    assert sorted(order.tolist()) == list(range(257)) and (order != np.arange(257)).any()

@@ -7,13 +7,19 @@ One item per class, the class as its id.  Every launch of an item
   * finds `out` / `gW` / the statistics table prefilled with NaN and the cached workspace with 0xFF bytes (NaN), so that a row, tile
     or slab nobody writes shows as NaN instead of the previous launch's plausible numbers,
   * goes through the C ABI: fc_conv_fwd (dense tables, tables in a row order of the test's choosing through fc_permute_nbr, table-free
-    GEMMs), fc_conv_fwd_pairs_tiles (live_tiles 0 and exact), their *_stats twins, fc_stem_conv_fwd, fc_conv_wgrad,
+    GEMMs), fc_conv_fwd_pairs_tiles (live_tiles 0 and exact), their *_stats and *_bn_bwd_stats twins, fc_stem_conv_fwd, fc_conv_wgrad,
     fc_conv_wgrad_pairs, fc_stem_conv_wgrad; weight images from Fn._x6_image, FC_CONV_WT operands as a transposed copy.
 A dense-table class runs every case a second time through out_index where the route query puts that call in the same class.  A
 linear pair-list class has no case without a pair: live_tiles = 0 IS the 3-D launch, which its sibling class runs (conv_cases.cases).
+A class with a statistics epilogue runs its statistics cases a third time through the BACKWARD form of that epilogue (the two
+reductions of a BatchNorm backward pass: column sums of g' = (g + add) act'(.) and of g' xhat), on inputs on which every term is a
+multiple of 1/4 (conv_cases, "the backward form of the statistics epilogue"): `out` still equals the plain reference, every entry of
+the table is finite and a multiple of 1/4, and the column totals of both planes equal the float64 reference.  Four further items
+chain the table into fc_bn_train_bwd(part = ...), one per producer of it (the tile epilogues of k_conv_x6 and k_conv_h3r,
+k_sum_parts_stats, k_sum_pairs_stats).
 A further item runs the Python layer (KernelMap + Fn.sparse_conv + autograd) on injective tables.
-References are computed once per (shape, table, operands) and shared by the classes that launch them; the file's 298 items take
-about 12 s on an MI355X.  DESIGN.md section 5, "Exact-integer route tests"."""
+References are computed once per (shape, table, operands) and shared by the classes that launch them; the file's 302 items take
+11.1 s on an MI355X (9.4 s for the 298 items before the backward form).  DESIGN.md section 5, "Exact-integer route tests"."""
 import functools
 
 import numpy as np
@@ -63,7 +69,7 @@ def _pairs(name, K, n_in, n_out, tile, S):
 def _sorted(name, K, n_in, n_out, tile, S):
     """the table in a row order of the test's own choosing (a seeded permutation) through fc_permute_nbr -> (table, order)"""
     nbr, dev = _table(name, K, n_in, n_out, tile, S), _dev()
-    order = torch.from_numpy(np.random.default_rng(n_out).permutation(n_out).astype(np.int32)).to(dev)
+    order = torch.from_numpy(CC.sorted_order(n_out)).to(dev)
     tab = torch.full_like(nbr, -1)
     L.call('fc_permute_nbr', L.ptr(nbr), L.ptr(order), n_out, K, L.ptr(tab), L.stream())
     return tab, order
@@ -76,6 +82,17 @@ def _ref(what, n_in, n_out, K, Cin, Cout, variant, name, tile, S):
     nbr = None if name == 'identity' else CC.make_table(name, K, n_in, n_out, tile, S)
     r = CC.ref_fwd(x, w, nbr) if what == 'y' else CC.ref_wgrad(x, go, nbr, K) if what == 'gw' else CC.ref_stem_col(x, nbr)
     return r.to(_dev())
+
+
+@functools.lru_cache(maxsize=512)
+def _bn(n_in, n_out, K, Cin, Cout, name, tile, S, variant):
+    """the epilogue inputs of a backward-epilogue case on the device (None where the option combination passes none) and the float64
+    column totals of both planes -> (combo, bn_x, mean, var, gamma, beta, add, bn_y, totals (2, Cout))"""
+    bc = CC.bn_case(n_in, n_out, K, Cin, Cout, name, tile, S, variant)
+    f = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_dev())
+    assert CC.bn_cap(bc) < 1.0, 'backward-epilogue reference leaves the exact multiples of 1/4'
+    return (bc.combo, f(bc.x), f(bc.mean), f(bc.var), f(bc.gamma if bc.combo.affine else None), f(bc.beta if bc.combo.affine else None),
+            f(bc.add), f(bc.y), torch.from_numpy(CC.bn_sums(bc)).to(_dev()))
 
 
 def _poisoned_workspace(nbytes):
@@ -116,15 +133,34 @@ def _check_stats(tab, ref, what):
     return ''
 
 
-def _run_fwd(cls, rep, case, tile, S):
-    """-> list of failure texts of one case (every launch kind the class has for it)"""
+def _check_bn_stats(tab, want, what):
+    """the backward form: every entry finite and a multiple of 1/4, the column totals of both planes equal to the float64 reference"""
+    if not bool(torch.isfinite(tab).all()):
+        return f'{what}: statistics table has {int((~torch.isfinite(tab)).sum())} non-finite entries'
+    if not torch.equal(tab * 4, (tab * 4).round()):
+        return f'{what}: statistics table holds entries that are no multiple of 1/4'
+    t = tab.double().sum(0)
+    if not torch.equal(t, want):
+        return (f"{what}: column sums differ (g' {int((t[0] != want[0]).sum())}, g' xhat {int((t[1] != want[1]).sum())} of {want.shape[1]} "
+                f'columns)')
+    return ''
+
+
+def _run_fwd(cls, rep, case, tile, S, keep=None):
+    """-> list of failure texts of one case (every launch kind the class has for it); keep: a list that takes (kind, out, table, row
+    blocks) of every launch"""
     dev, K, Cin, Cout, flags = _dev(), rep.K, rep.Cin, rep.Cout, rep.flags
     n_in, n_out = case.n_in, case.n_out
     key = (case.table, K, n_in, n_out, tile, S)
-    x, w, _ = _operands(n_in, n_out, K, Cin, Cout, case.variant)
-    ref = _ref('y', n_in, n_out, K, Cin, Cout, case.variant, case.table, tile, S)
+    opv = CC.operand_variant(case.variant)
+    x, w, _ = _operands(n_in, n_out, K, Cin, Cout, opv)
+    ref = _ref('y', n_in, n_out, K, Cin, Cout, opv, case.table, tile, S)
     wop = _weight_operand(w, flags)
-    stats = case.variant == 'stats'
+    bn = _bn(n_in, n_out, K, Cin, Cout, case.table, tile, S, case.variant) if CC.is_bn(case.variant) else None
+    stats = case.variant == 'stats' or bn is not None
+    bn_tail = ()
+    if bn is not None:                             # (stats, bn_x, mean, var, gamma, beta, eps = 0, act, add, bn_y)
+        bn_tail = (*(L.ptr(a) for a in bn[1:6]), 0.0, bn[0].act, L.ptr(bn[6]), L.ptr(bn[7]))
     kinds = [rep.kind]
     if rep.kind == 'dense' and CC.fast_class(CC.FWD, n_in, n_out, K, Cin, Cout, flags, 'sorted', 0, stats) == cls:
         kinds.append('sorted')                     # the same class through out_index
@@ -154,21 +190,27 @@ def _run_fwd(cls, rep, case, tile, S):
             pi, _, pos, cnt = lists
             head = (L.ptr(x), L.ptr(wop), L.ptr(pi), L.ptr(cnt), L.ptr(pos), L.ptr(out), n_in, n_out, K, Cin, Cout, live, flags,
                     L.ptr(ws), ws.numel())
-            if stats:
+            if bn is not None:
+                L.call('fc_conv_fwd_pairs_tiles_bn_bwd_stats', *head, L.ptr(tab), *bn_tail, L.stream())
+            elif stats:
                 L.call('fc_conv_fwd_pairs_tiles_stats', *head, L.ptr(tab), L.stream())
             else:
                 L.call('fc_conv_fwd_pairs_tiles', *head, L.stream())
         else:
             head = (L.ptr(x), L.ptr(wop), L.ptr(nbr), L.ptr(oidx), L.ptr(out), n_in, n_out, K, Cin, Cout, flags, L.ptr(ws), ws.numel())
-            if stats:
+            if bn is not None:
+                L.call('fc_conv_fwd_bn_bwd_stats', *head, L.ptr(tab), *bn_tail, L.stream())
+            elif stats:
                 L.call('fc_conv_fwd_stats', *head, L.ptr(tab), L.stream())
             else:
                 L.call('fc_conv_fwd', *head, L.stream())
+        if keep is not None:
+            keep.append((kind, out, tab, nb if stats else 0))
         d = _diff(out, ref)
         if d:
             fails.append(f'{what}: {d}')
         if stats:
-            d = _check_stats(tab, ref, what)
+            d = _check_bn_stats(tab, bn[8], what) if bn is not None else _check_stats(tab, ref, what)
             if d:
                 fails.append(d)
     if cls.family == E['FC_FAM_STEM'] and not stats:
@@ -286,4 +328,76 @@ def test_python_layer_is_exact_on_integer_operands(x6):
         raise
     finally:
         Fn.X6 = x6_0
+    assert not fails, '\n'.join(fails)
+
+
+# ---- producer and consumer of the table: the convolution epilogue into fc_bn_train_bwd(part = ...) -----------------------------------------
+CHAIN_ROWS = (4096, 1024, 256, 128)
+_FAMILY = lambda c: CC.class_id(CC.FWD, c).split('-')[0]
+CHAIN_KINDS = {
+    'x6_tile_epilogue': lambda c, r: _FAMILY(c) == 'x6' and c.epi == E['FC_EPI_KERNEL'] and r.kind == 'dense',
+    'h3r_tile_epilogue': lambda c, r: _FAMILY(c) == 'h3r' and c.epi == E['FC_EPI_KERNEL'] and r.kind == 'dense',
+    'k_sum_parts_stats': lambda c, r: c.epi == E['FC_EPI_SUM'] and r.kind == 'dense',
+    'k_sum_pairs_stats': lambda c, r: c.epi == E['FC_EPI_SUM'] and r.kind == 'pairs',
+}
+
+
+def _chain_pick(kind_id):
+    """the first class of the epilogue kind that keeps a power-of-two row count of CHAIN_ROWS (the largest: the longest table), by the
+    route query -> (class, representative, rows)"""
+    for cls, rep in SWEPT[CC.FWD].items():
+        if CHAIN_KINDS[kind_id](cls, rep):
+            CC.set_env(rep.env)
+            for n in CHAIN_ROWS:
+                if CC.route_class(CC.FWD, n, n, rep.K, rep.Cin, rep.Cout, rep.flags, rep.kind, 0, True) == cls:
+                    return cls, rep, n
+    raise AssertionError(f'no class of {kind_id} keeps a row count of {CHAIN_ROWS}')
+
+
+@pytest.mark.parametrize('kind_id', list(CHAIN_KINDS))
+def test_backward_epilogue_table_feeds_the_batchnorm_backward(kind_id):
+    """the one place that holds producer and consumer to the same layout and entry count: the table a backward-data launch leaves
+    (ReLU with the layer's output given, and recomputed; `add` passed) goes to fc_bn_train_bwd(part = table, nb_part =
+    fc_conv_stats_blocks(...)) with gy = out and gy2 = add.  gx, gres and the sums against the float64 backward reference of
+    tests/norm_cases.py at a power-of-two row count: torch.equal where norm_cases declares the quantity exact there (the sums and
+    gres: integers; gx: where gx_premise holds), its REL_SCALE bound otherwise."""
+    from tests import norm_cases as NC
+    dev, fails = _dev(), []
+    try:
+        cls, rep, n = _chain_pick(kind_id)
+        tile, S = CC.tile_of(CC.FWD, rep)
+        C = rep.Cout
+        for variant in (CC.bn_variant(3), CC.bn_variant(8)):          # (ReLU, add, bn_y), (ReLU, add, recomputed)
+            combo = CC.bn_combo(variant)
+            assert combo.act == CC.RELU and combo.add and combo.affine
+            case = CC.Case(n, n, 'full', variant)
+            keep = []
+            fails += _run_fwd(cls, rep, case, tile, S, keep)
+            kind, out, tab, nb = keep[0]
+            assert kind == rep.kind and nb == L.query('fc_conv_stats_blocks', n, rep.K, rep.Cin, C, rep.flags, 1 if kind == 'pairs' else 0)
+            bc = CC.bn_case(n, n, rep.K, rep.Cin, C, 'full', tile, S, variant)
+            _, bn_x, mean, var, gamma, beta, add, bn_y, _ = _bn(n, n, rep.K, rep.Cin, C, 'full', tile, S, variant)
+            # the reference: NC.ref_bwd on the incoming gradient g + add; with bn_y = relu(pre + res), act'(pre + res) IS bn_y > 0
+            r = NC.ref_bwd(bc.x, bc.g + bc.add, bc.mean[None], bc.var[None], bc.gamma, bc.beta, NC.RELU, np.zeros(n, np.int64), 1, [n],
+                           bc.res if combo.y == 'y' else None)
+            assert NC.is_pow2(n) and np.abs(r['gres']).sum(0).max() < NC.EXACT and np.abs(r['gres'] * r['xh']).sum(0).max() < NC.EXACT
+            bound = {'sums': 0, 'gres': 0, 'gx': 0 if NC.gx_premise(r, np.zeros(n, np.int64), [n]) else NC.REL_SCALE}
+            gx, gres, sums = (torch.full((n, C), NAN, device=dev), torch.full((n, C), NAN, device=dev), torch.full((1, 2, C), NAN, device=dev))
+            cnt = torch.full((1,), float(n), device=dev)
+            ws = _poisoned_workspace(L.query('fc_bn_train_ws_bytes', n, C))
+            L.call('fc_bn_train_bwd', L.ptr(bn_x), L.ptr(bn_y), L.ptr(out), L.ptr(add), n, C, L.ptr(mean), L.ptr(var), L.ptr(cnt), 0.0,
+                   L.ptr(gamma), L.ptr(beta), combo.act, L.ptr(gx), L.ptr(gres), L.ptr(sums), L.ptr(tab), nb, Fn.BN_SMALL_ELEMS, L.ptr(ws),
+                   ws.numel(), L.stream())
+            for name, got in (('sums', sums), ('gres', gres), ('gx', gx)):
+                g64 = got.double().cpu().numpy().reshape(r[name].shape)
+                err = float(np.abs(g64 - r[name]).max()) if np.isfinite(g64).all() else float('inf')
+                print(f'{kind_id} n={n} {variant} {name}: bound {bound[name]:g}, max-abs error {err:.3e} of scale {np.abs(r[name]).max():.3e}')
+                if not np.isfinite(g64).all() or NC.differs(g64, r[name], bound[name]):
+                    fails.append(f'{rep} n={n} {variant} fc_bn_train_bwd {name}: bound {bound[name]:g}, max-abs error {err:.3e} of scale '
+                                 f'{np.abs(r[name]).max():.3e}, {int((~np.isfinite(g64)).sum())} non-finite')
+    except RuntimeError as e:
+        _stop_after_a_gpu_fault(e)
+        raise
+    finally:
+        CC.set_env(CC.ENV_DEFAULT)
     assert not fails, '\n'.join(fails)

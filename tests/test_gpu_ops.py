@@ -1003,8 +1003,8 @@ def test_batchnorm_backward_sums_out_of_the_convolution_epilogue(q, C, route, ac
     pairs = Fn._pair_conv(km, n, C, C)
     nb = L.query('fc_conv_stats_blocks', n, 27, C, C, fl, 1 if pairs else 0)
     assert nb > 0
-    stats = torch.zeros((nb, 2, C), device=dev)
-    out = torch.empty((n, C), device=dev)
+    stats = torch.full((nb, 2, C), float('nan'), device=dev)
+    out = torch.full((n, C), float('nan'), device=dev)
     with torch.no_grad():
         ref = Fn.sparse_conv(x, w, km, n)
     if pairs:
